@@ -8,7 +8,11 @@ sharded by rank with no hot-path collective (weak scaling: 4096 CUs per GPU).  `
 starts the N ranks itself (as a child process, before anything touches the GPU); under an existing
 torchrun launch (WORLD_SIZE set) it is one of the ranks.
 
-Prints ONE JSON line on rank 0.  See DESIGN.md "Measurement" for how roofline / cpu_baseline are defined.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the line (`value`, `ms_per_step`);
+everything else it can measure or check -- the per-kernel table and roofline (a second, profiled pass), the sustained legs, the CPU
+baselines and the parity check against the C oracle -- runs only with --full.  --dump-outputs DIR writes what the last timed step
+computed (logits, split modes) as .npy files, so that two builds can be compared output for output.
+See DESIGN.md "Measurement" for how roofline / cpu_baseline are defined.
 """
 import argparse
 import hashlib
@@ -43,8 +47,13 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=BATCH, help="CUs per GPU per step (BASELINE: 4096)")
     ap.add_argument("--size", type=int, default=SIZE)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU legs (C oracle over the whole batch = full-batch parity, torch port)")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="CUs of the batch the C oracle evaluates (default: whole batch when the host has >= 64 cores)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: profiled per-kernel pass + roofline, sustained legs, CPU baselines, "
+                         "parity against the C oracle (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's logits and split modes as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs (C oracle over the whole batch = full-batch parity, torch port)")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="with --full: CUs of the batch the C oracle evaluates (default: whole batch when the host has >= 64 cores)")
     ap.add_argument("--weight-seed", type=int, default=10, help="seed of the synthetic weight set (10 = the BASELINE workload; 13 / 24 land in the hi+lo-weights tier)")
     ap.add_argument("--weights-blob", default="", help="an MLTW file instead of the seeded set (e.g. tools/train_synth_weights.py's trained family): another WORKLOAD, never the driver's line")
     ap.add_argument("--flags", type=lambda s: int(s, 0), default=0, help="mlt_config.flags; 0 = the shipped configuration (calibrated arithmetic + flat-content guard + decision guard, what the encoder runs); "
@@ -60,12 +69,14 @@ def parse_args():
     ap.add_argument("--host-staged", action="store_true",
                     help="also time mlt_predict_batch from pinned HOST buffers (PCIe-inclusive rate; never `value`)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.sustain_s is None:
-        # the sustained legs (16 s of full-power work per rank) belong to the HEADLINE run: the default workload in the shipped configuration;
-        # sweeps, A/Bs and the other workloads skip them unless asked
+        # the sustained legs (16 s of full-power work per rank) belong to the full run of the HEADLINE workload: the default workload in the
+        # shipped configuration; sweeps, A/Bs and the other workloads skip them unless asked
         headline = (not a.weights_blob and a.weight_seed == 10 and a.flags == 0 and a.content == "texture" and a.flat_frac == 0 and a.size == 128
                     and not a.no_cpu_baseline)
-        a.sustain_s = 8.0 if headline else 0.0
+        a.sustain_s = 8.0 if headline and a.full else 0.0
     return a
 
 
@@ -101,6 +112,23 @@ def source_signature():
     measured on.  One definition, in the package's build recipe -- the library carries the same value (mlt_build_signature)."""
     import mltcnn_pkg
     return mltcnn_pkg.load().build.source_signature()
+
+
+DUMP_BUDGET_BYTES = 60 << 20   # (+ the .npy headers: under 64 MB)
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """DIR/<name>.npy (DIR/<name>_rank<r>.npy for N > 1 ranks) in float32, one row per CU.  Over the budget (64 MB for all ranks), every
+    array keeps the same seeded sample of rows, in CU order."""
+    import numpy as np
+    arrays = {k: np.asarray(v).astype(np.float32) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(v[:1].nbytes for v in arrays.values())
+    keep = min(n, DUMP_BUDGET_BYTES // world // max(row_bytes, 1))
+    rows = np.sort(np.random.default_rng(20241016).choice(n, keep, replace=False)) if keep < n else slice(None)
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + (f"_rank{rank}" if world > 1 else "") + ".npy"), v[rows])
 
 
 def main():
@@ -227,6 +255,11 @@ def main():
         elapsed = float(te.item())
         rates = [B * args.steps / float(x.item()) for x in allt]
         per_rank = {"cu_per_s": [round(r, 1) for r in rates], "min": round(min(rates), 1), "max": round(max(rates), 1)}
+    # what the last timed step handed its caller (every later pass recomputes the same batch)
+    got_logits = d_logits.cpu().numpy()
+    got_split = d_split.cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits": got_logits, "split": got_split}, rank, world)
     # ---- sustained figures (outside the timed region, every rank: the power envelope is per package) ----
     # (i) the same step back to back for --sustain-s seconds; (ii) the MFMA rate THIS box sustains over the same time on a plain fp16 GEMM
     # (hipBLASLt through torch.matmul, 8192^3, operands with post-ReLU-like statistics: |N(0,1)| activations, N(0, 1/K) weights): the part
@@ -258,15 +291,15 @@ def main():
         sustained = {"cu_per_s": B * n_sus / sus_s, "steps": n_sus, "seconds": sus_s,
                      "mfma_tflops": 2.0 * gm ** 3 * n_gemm / gemm_s / 1e12, "gemm_seconds": gemm_s, "gemm": f"{gm}^3 fp16 torch.matmul (hipBLASLt), fp32 accumulate"}
         del ga, gb, gc
-    # ---- the same steps again with HIP events around every kernel launch (on the launch stream): per-kernel table ----
-    m.profile_enable(True)
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    prof = m.profile_read()
-    m.profile_enable(False)
-    got_logits = d_logits.cpu().numpy()
-    got_split = d_split.cpu().numpy()
+    # ---- (--full) the same steps again with HIP events around every kernel launch (on the launch stream): per-kernel table ----
+    prof = []
+    if args.full:
+        m.profile_enable(True)
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        prof = m.profile_read()
+        m.profile_enable(False)
     if dist is not None:
         dist.barrier()
 
@@ -368,58 +401,59 @@ def main():
                          "selection": "the launch with the most algorithmic FLOPs (among launches within 1 % of it: the longest)",
                          "others": [{"kernel": k["name"], "avg_ms": k["avg_ms"], "bound": k["bound"], "roof_frac": k["roof_frac"]} for k in kernels if k["name"] != dom["name"] and k["flop_share"] > 0.05]})
 
-    # ---- CPU legs (rank 0, N = 1 only): the C oracle over the batch = parity of EVERY CU of the timed workload and the
+    # ---- (--full) CPU legs (rank 0, N = 1 only): the C oracle over the batch = parity of EVERY CU of the timed workload and the
     # second baseline row; the torch-CPU port timed per SURVEY.md §8(d) = cpu_baseline.value ----
     parity = None
     cpu_baseline = None
-    import oracle
-    cores = os.cpu_count() or 1
-    if world == 1 and not args.no_cpu_baseline:
-        sample = args.cpu_sample or (B if cores >= 64 else min(B, 16 * cores))
-        orc = oracle.Oracle(blob)
-        orc.forward(org[:cores], pred[:cores], poc[:cores], qp[:cores], threads=cores)  # warm-up
-        c0 = time.perf_counter()
-        ref, ref_split = orc.forward(org[:sample], pred[:sample], poc[:sample], qp[:sample], threads=cores)
-        cs = time.perf_counter() - c0
-        c_row = {"impl": "C oracle (oracle/mlt_oracle.c), fp32, OpenMP over CUs", "value": round(sample / cs, 2), "threads": cores,
-                 "sample": f"first {sample} CUs of the same batch, one pass, {cs:.1f} s"}
-        cpu_baseline = {"value": c_row["value"], "unit": "CU-inferences/s", "cores": cores, "kind": "port", "sample": c_row["sample"],
-                        "rows": [c_row]}
-        try:
-            tb = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "cpu_baseline.py"), "--size", str(size), "--json"],
-                                capture_output=True, text=True, timeout=600)
-            tl = [l for l in tb.stdout.splitlines() if l.startswith("{")]
-            if tb.returncode == 0 and tl:
-                cj = json.loads(tl[-1])
-                cpu_baseline["rows"] = cj["rows"] + [c_row]
-                cpu_baseline.update({"cpu_model": cj["cpu_model"], "physical_cores": cj["physical_cores"], "logical_cpus": cj["logical_cpus"]})
-                if cj["value"] >= c_row["value"]:  # `value` = the best CPU row, C oracle included
-                    cpu_baseline.update({"value": cj["value"], "cores": cj["cores"], "sample": cj["sample"]})
-            else:
-                cpu_baseline["torch_port_error"] = (tb.stderr or tb.stdout)[-400:]
-        except subprocess.TimeoutExpired:
-            cpu_baseline["torch_port_error"] = "timeout"
-    else:
-        sample = min(B, args.cpu_sample or (8 if args.no_cpu_baseline else 64))  # (--cpu-sample N: parity over N CUs even without the CPU baseline legs)
-        ref, ref_split = oracle.Oracle(blob).forward(org[:sample], pred[:sample], poc[:sample], qp[:sample], threads=min(cores, sample))
-    hs, lo = [], 0
-    for c in pkg.synth.HEAD_CLASSES[arch]:
-        hs.append(slice(lo, lo + c))
-        lo += c
-    dec = hs[2 if size == 128 else 0]
-    srt = np.sort(ref[:, dec].astype(np.float64), axis=1)
-    # the configuration guarantees the argmax above this reference margin: 2 x tolerance for an arithmetic with errors up to the tolerance,
-    # 4e-5 (twice the exact arithmetic's own noise) when the decision guard re-evaluates every narrower CU exactly, or the arithmetic is exact
-    guarded = bool(arith["decision_guard"]) or int(arith["exact"]) == 1
-    decisive = (srt[:, -1] - srt[:, -2]) > (4e-5 if guarded else 2 * LOGIT_TOL)
-    mism = got_split[:sample] != ref_split
-    parity = {"checked_cus": int(sample), "of_batch": int(B), "max_abs_dlogit": float(np.abs(got_logits[:sample] - ref).max()),
-              "tolerance": LOGIT_TOL, "within_tolerance": bool(np.abs(got_logits[:sample] - ref).max() <= LOGIT_TOL),
-              "split_mismatch_decisive": int((mism & decisive).sum()), "non_decisive": int((~decisive).sum()),
-              "split_mismatch_non_decisive": int((mism & ~decisive).sum()),
-              "split_identical_decisive": bool(not (mism & decisive).any()), "split_identical": bool(not mism.any()),
-              "decisive_margin": 4e-5 if guarded else 2 * LOGIT_TOL,
-              "oracle": "oracle/mlt_oracle.c (fp32 restatement pinned to the reference fixtures)"}
+    if args.full:
+        import oracle
+        cores = os.cpu_count() or 1
+        if world == 1 and not args.no_cpu_baseline:
+            sample = args.cpu_sample or (B if cores >= 64 else min(B, 16 * cores))
+            orc = oracle.Oracle(blob)
+            orc.forward(org[:cores], pred[:cores], poc[:cores], qp[:cores], threads=cores)  # warm-up
+            c0 = time.perf_counter()
+            ref, ref_split = orc.forward(org[:sample], pred[:sample], poc[:sample], qp[:sample], threads=cores)
+            cs = time.perf_counter() - c0
+            c_row = {"impl": "C oracle (oracle/mlt_oracle.c), fp32, OpenMP over CUs", "value": round(sample / cs, 2), "threads": cores,
+                     "sample": f"first {sample} CUs of the same batch, one pass, {cs:.1f} s"}
+            cpu_baseline = {"value": c_row["value"], "unit": "CU-inferences/s", "cores": cores, "kind": "port", "sample": c_row["sample"],
+                            "rows": [c_row]}
+            try:
+                tb = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "cpu_baseline.py"), "--size", str(size), "--json"],
+                                    capture_output=True, text=True, timeout=600)
+                tl = [l for l in tb.stdout.splitlines() if l.startswith("{")]
+                if tb.returncode == 0 and tl:
+                    cj = json.loads(tl[-1])
+                    cpu_baseline["rows"] = cj["rows"] + [c_row]
+                    cpu_baseline.update({"cpu_model": cj["cpu_model"], "physical_cores": cj["physical_cores"], "logical_cpus": cj["logical_cpus"]})
+                    if cj["value"] >= c_row["value"]:  # `value` = the best CPU row, C oracle included
+                        cpu_baseline.update({"value": cj["value"], "cores": cj["cores"], "sample": cj["sample"]})
+                else:
+                    cpu_baseline["torch_port_error"] = (tb.stderr or tb.stdout)[-400:]
+            except subprocess.TimeoutExpired:
+                cpu_baseline["torch_port_error"] = "timeout"
+        else:
+            sample = min(B, args.cpu_sample or (8 if args.no_cpu_baseline else 64))  # (--cpu-sample N: parity over N CUs even without the CPU baseline legs)
+            ref, ref_split = oracle.Oracle(blob).forward(org[:sample], pred[:sample], poc[:sample], qp[:sample], threads=min(cores, sample))
+        hs, lo = [], 0
+        for c in pkg.synth.HEAD_CLASSES[arch]:
+            hs.append(slice(lo, lo + c))
+            lo += c
+        dec = hs[2 if size == 128 else 0]
+        srt = np.sort(ref[:, dec].astype(np.float64), axis=1)
+        # the configuration guarantees the argmax above this reference margin: 2 x tolerance for an arithmetic with errors up to the tolerance,
+        # 4e-5 (twice the exact arithmetic's own noise) when the decision guard re-evaluates every narrower CU exactly, or the arithmetic is exact
+        guarded = bool(arith["decision_guard"]) or int(arith["exact"]) == 1
+        decisive = (srt[:, -1] - srt[:, -2]) > (4e-5 if guarded else 2 * LOGIT_TOL)
+        mism = got_split[:sample] != ref_split
+        parity = {"checked_cus": int(sample), "of_batch": int(B), "max_abs_dlogit": float(np.abs(got_logits[:sample] - ref).max()),
+                  "tolerance": LOGIT_TOL, "within_tolerance": bool(np.abs(got_logits[:sample] - ref).max() <= LOGIT_TOL),
+                  "split_mismatch_decisive": int((mism & decisive).sum()), "non_decisive": int((~decisive).sum()),
+                  "split_mismatch_non_decisive": int((mism & ~decisive).sum()),
+                  "split_identical_decisive": bool(not (mism & decisive).any()), "split_identical": bool(not mism.any()),
+                  "decisive_margin": 4e-5 if guarded else 2 * LOGIT_TOL,
+                  "oracle": "oracle/mlt_oracle.c (fp32 restatement pinned to the reference fixtures)"}
 
     tier = int(arith["exact"])  # 0 fast, 1 exact, 2 hi+lo weights on fp16 activations in every stage, 3 in the stages of w2_stages only, 4 exact stages, 5 exact-lite
     exact = tier == 1
@@ -435,7 +469,7 @@ def main():
     out = {
         "metric": f"CU-inferences/sec (batch {B}, {size}x{size})", "value": round(value, 1), "unit": "CU-inferences/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "full": args.full,
         "dtype": "f16x2 (hi+lo pairs, fp32 accumulate)" if exact else "f16x2 pairs, cross terms in scaled fp8 (exact-lite, fp32 accumulate)" if tier == 5 else "f16 weights hi+lo x f16 activations (fp32 accumulate)" if tier == 2 else f"f16, weights hi+lo in {stages} (fp32 accumulate)" if tier == 3 else f"f16x2 pairs in {xstages}, f16 with weights hi+lo in {stages or 'no stage'} (fp32 accumulate)" if tier == 4 else "f16 (fp32 accumulate)", "data": "synthetic",
         "config": {"workload": f"BASELINE configs[{1 if size == 128 else 2}]: batch {B} synthetic {size}x{size} CU patches per GPU, fp16 MFMA / fp32 accumulate, "
                                "inputs (int16 org+pred, int32 poc/qp) resident in HBM, outputs logits+split in HBM",
@@ -457,9 +491,9 @@ def main():
         "derived": {"model_tflops": round(value * FLOP_PER_CU[size] / 1e12, 1),
                     "mfma_frac_whole_net": round(value / world * FLOP_PER_CU[size] / 1e12 / MFMA_PEAK_TFLOPS, 4),
                     "hbm_layerwise_roofline_frac": round(value / world * LAYERWISE_BYTES_PER_CU[size] / 1e9 / HBM_PEAK_GBS, 4),
-                    "whole_path": {"t_bound_ms": round(t_bound_ms, 4), "t_measured_ms": round(ms_per_step, 4),
-                                   "frac": round(t_bound_ms / max(ms_per_step, 1e-9), 4),
-                                   "note": "sum over launches of max(algorithmic FLOPs / 2.5 PFLOP/s, algorithmic bytes / 8 TB/s) / measured step time"},
+                    "whole_path": None if not prof else {"t_bound_ms": round(t_bound_ms, 4), "t_measured_ms": round(ms_per_step, 4),
+                                                         "frac": round(t_bound_ms / max(ms_per_step, 1e-9), 4),
+                                                         "note": "sum over launches of max(algorithmic FLOPs / 2.5 PFLOP/s, algorithmic bytes / 8 TB/s) / measured step time"},
                     "sustained_cu_per_s": round(world * sustained["cu_per_s"], 1) if sustained else None,
                     "sustained": None if not sustained else {"steps": sustained["steps"], "seconds": round(sustained["seconds"], 2), "per_gpu_cu_per_s": round(sustained["cu_per_s"], 1),
                                                              "hbm_layerwise_roofline_frac": round(sustained["cu_per_s"] * LAYERWISE_BYTES_PER_CU[size] / 1e9 / HBM_PEAK_GBS, 4)},

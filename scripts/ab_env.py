@@ -36,7 +36,7 @@ for val in (None, "1"):
     out = f"/tmp/ab_{var}_{val}.npy"
     subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", out, str(n), str(size)], env=env)
     res[val] = np.load(out)
-    b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "10", "--size", str(size)], env=env, capture_output=True, text=True).stdout
+    b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "10", "--size", str(size)], env=env, capture_output=True, text=True).stdout
     line = [l for l in b.splitlines() if l.startswith("{")]
     if line:
         d = json.loads(line[-1])

@@ -4,7 +4,7 @@
 for v in base lo8 base lo8; do
   if [ $v = base ]; then export MLT_LIB_PATH=$PWD/fastintercu-vvc_amd/_variants/lib_base.so; else unset MLT_LIB_PATH; fi
   for s in 13 11; do
-  python bench.py --no-cpu-baseline --cpu-sample 64 --weight-seed $s --steps 20 --warmup 10 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --cpu-sample 64 --weight-seed $s --steps 20 --warmup 10 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

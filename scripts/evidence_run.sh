@@ -15,9 +15,9 @@ tag=${1:-r04k}
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-python3 bench.py > $out/bench_line.json 2> $out/bench.err
-python3 bench.py --no-cpu-baseline --latency --host-staged > $out/bench_extras.json 2>> $out/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o out -- python3 bench.py --no-cpu-baseline > $out/stats.log 2>&1
+python3 bench.py --full > $out/bench_line.json 2> $out/bench.err
+python3 bench.py --full --no-cpu-baseline --latency --host-staged > $out/bench_extras.json 2>> $out/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o out -- python3 bench.py --full --no-cpu-baseline > $out/stats.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/fetch -o out -- python3 scripts/prof_run.py 4096 2 > $out/fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/write -o out -- python3 scripts/prof_run.py 4096 2 > $out/write.log 2>&1
 for grp in "GRBM_GUI_ACTIVE" "SQ_VALU_MFMA_BUSY_CYCLES" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "SQ_WAVE_CYCLES SQ_WAIT_ANY" "SQ_BUSY_CYCLES SQ_INSTS_LDS"; do
@@ -26,23 +26,23 @@ for grp in "GRBM_GUI_ACTIVE" "SQ_VALU_MFMA_BUSY_CYCLES" "SQ_LDS_BANK_CONFLICT SQ
 done
 # round 6: every side leg checks ALL 4096 CUs of its batch against the C oracle (--cpu-sample 4096; round 5's legs checked 8) and skips the sustained legs (bench.py's default outside the headline run)
 S="--no-cpu-baseline --cpu-sample 4096"
-for s in 11 13 23 24 25 12 21 22; do python3 bench.py $S --weight-seed $s > $out/bench_seed$s.json 2>> $out/bench.err; done
-python3 bench.py $S --flags 1 --steps 20 --warmup 5 > $out/bench_exact.json 2>> $out/bench.err
-python3 bench.py $S --flags 0x41 --steps 20 --warmup 5 > $out/bench_exact_lite.json 2>> $out/bench.err   # round 5: exact-lite forced (tier 5)
-python3 bench.py $S --flags 0x20 > $out/bench_no_decision_guard.json 2>> $out/bench.err                     # ABI 4: the guard is the default; this is the round-4 headline configuration
+for s in 11 13 23 24 25 12 21 22; do python3 bench.py --full $S --weight-seed $s > $out/bench_seed$s.json 2>> $out/bench.err; done
+python3 bench.py --full $S --flags 1 --steps 20 --warmup 5 > $out/bench_exact.json 2>> $out/bench.err
+python3 bench.py --full $S --flags 0x41 --steps 20 --warmup 5 > $out/bench_exact_lite.json 2>> $out/bench.err   # round 5: exact-lite forced (tier 5)
+python3 bench.py --full $S --flags 0x20 > $out/bench_no_decision_guard.json 2>> $out/bench.err                     # ABI 4: the guard is the default; this is the round-4 headline configuration
 # round 6: the trained weight families (tools/train_synth_weights.py; blobs staged, git-ignored, under tests/data/_blobs/) on the bench content and on natural scenes; the same without the magnitude guard
 for f in tests/data/_blobs/*.mltw; do
   [ -f "$f" ] || continue
   b=$(basename $f .mltw)
-  python3 bench.py $S --weights-blob $f --steps 20 --warmup 5 > $out/bench_$b.json 2>> $out/bench.err
-  python3 bench.py $S --weights-blob $f --steps 20 --warmup 5 --content natural > $out/bench_${b}_natural.json 2>> $out/bench.err
-  python3 bench.py $S --weights-blob $f --steps 20 --warmup 5 --flags 0x80 > $out/bench_${b}_no_magnitude_guard.json 2>> $out/bench.err
+  python3 bench.py --full $S --weights-blob $f --steps 20 --warmup 5 > $out/bench_$b.json 2>> $out/bench.err
+  python3 bench.py --full $S --weights-blob $f --steps 20 --warmup 5 --content natural > $out/bench_${b}_natural.json 2>> $out/bench.err
+  python3 bench.py --full $S --weights-blob $f --steps 20 --warmup 5 --flags 0x80 > $out/bench_${b}_no_magnitude_guard.json 2>> $out/bench.err
 done
-python3 bench.py $S --flat-frac 0.25 --steps 20 --warmup 5 > $out/bench_flat25.json 2>> $out/bench.err
-python3 bench.py $S --content natural > $out/bench_natural.json 2>> $out/bench.err
-python3 bench.py $S --content natural --flags 0x20 > $out/bench_natural_no_decision_guard.json 2>> $out/bench.err
+python3 bench.py --full $S --flat-frac 0.25 --steps 20 --warmup 5 > $out/bench_flat25.json 2>> $out/bench.err
+python3 bench.py --full $S --content natural > $out/bench_natural.json 2>> $out/bench.err
+python3 bench.py --full $S --content natural --flags 0x20 > $out/bench_natural_no_decision_guard.json 2>> $out/bench.err
 python3 scripts/flush_latency.py 10 40 > $out/flush_latency.txt 2>&1
-for s in 64 32 16; do python3 bench.py --size $s > $out/bench_s$s.json 2>> $out/bench.err; done
+for s in 64 32 16; do python3 bench.py --full --size $s > $out/bench_s$s.json 2>> $out/bench.err; done
 rocprofv3 --kernel-trace --output-format csv -d $out/lat -o out -- python3 scripts/latency_run.py 60 10 0 > $out/lat.log 2>&1
 python3 scripts/latency_run.py 80 10 4 > $out/latency_modes.txt 2>&1
 python3 scripts/latency_run.py 80 13 4 >> $out/latency_modes.txt 2>&1

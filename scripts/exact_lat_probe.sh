@@ -6,13 +6,13 @@ for mode in on off; do
   python scripts/latency_run.py 80 10 1
   python scripts/latency_run.py 80 22 0
   python scripts/latency_run.py 80 12 0
-  python bench.py --no-cpu-baseline --cpu-sample 64 --content natural --steps 30 --warmup 10 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --cpu-sample 64 --content natural --steps 30 --warmup 10 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
         d=json.loads(l); print('natural', round(d['value']), d['ms_per_step'], 'reruns', d['config']['arithmetic']['guard_reruns_per_step'], '%.1e'%d['parity']['max_abs_dlogit'])
 "
-  python bench.py --no-cpu-baseline --cpu-sample 64 --size 64 --batch 64 --steps 200 --warmup 20 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --cpu-sample 64 --size 64 --batch 64 --steps 200 --warmup 20 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -8,14 +8,16 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "fastintercu-vvc_amd", "csrc", "mlt_kernels.hip")
+ASM = os.path.join(tempfile.gettempdir(), f"isa_waits-{os.getuid()}.s")   # per user: another user's file in a shared /tmp is not writable
 
 
 def collect(defs):
     """{demangled kernel name: {glds, gload, scratch, waits: [(asm line, loop depth, text)]}} of mlt_kernels.hip built with defs"""
-    out = "/tmp/isa_waits.s"
+    out = ASM
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", *defs, SRC, "-o", out],
                           stderr=subprocess.DEVNULL)
     name, in_asm, depth, stats = None, False, 0, {}
@@ -53,7 +55,7 @@ def collect(defs):
     return stats
 
 
-def scratch_in_loops(prefix, path="/tmp/isa_waits.s"):
+def scratch_in_loops(prefix, path=ASM):
     """[(asm line, depth, text)] of the scratch_* instructions of the kernels whose demangled name starts with `prefix` that sit inside a loop (collect() wrote `path`)"""
     hits, name, depth = [], None, 0
     for ln, line in enumerate(open(path), 1):

@@ -1,5 +1,5 @@
 timeout 300 python scripts/chain_check.py 2>&1 | tail -4
-for i in 1 2; do timeout 300 python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+for i in 1 2; do timeout 300 python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -11,7 +11,7 @@ for mode, steps, warm in (("default", 10, 3), ("spin", 10, 3), ("block", 10, 3),
     if mode == "block":
         env["MLT_GUARD_BLOCKING_WAIT"] = "1"
     flags = "24" if mode == "noguard" else "0"   # NO_CALIBRATION | NO_FLAT_GUARD: the device entry never synchronises
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", str(steps), "--warmup", str(warm), "--flags", flags], env=env, capture_output=True, text=True).stdout
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", str(steps), "--warmup", str(warm), "--flags", flags], env=env, capture_output=True, text=True).stdout
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     ks = sum(k['avg_ms'] for k in d['derived']['kernels'])
     print(f"{mode:8s} steps {steps:4d} warmup {warm:2d}: {d['value']:10.0f} CU/s  {d['ms_per_step']:.3f} ms/step  kernels {ks:.3f} ms  gap x steps = {(d['ms_per_step'] - ks) * steps:.2f} ms", flush=True)

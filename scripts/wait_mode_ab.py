@@ -17,7 +17,7 @@ for mode in ("default", "spin", "block") * 2:
     if mode == "block":
         env["MLT_GUARD_BLOCKING_WAIT"] = "1"
     r0 = resource.getrusage(resource.RUSAGE_CHILDREN)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "200", "--warmup", "5"], env=env, capture_output=True, text=True).stdout
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "200", "--warmup", "5"], env=env, capture_output=True, text=True).stdout
     r1 = resource.getrusage(resource.RUSAGE_CHILDREN)
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     print(f"{mode:8s} {d['value']:10.0f} CU/s  {d['ms_per_step']:.3f} ms/step  kernels {sum(k['avg_ms'] for k in d['derived']['kernels']):.3f} ms  "

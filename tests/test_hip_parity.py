@@ -863,7 +863,7 @@ def test_bench_contract_two_ranks_on_one_gpu(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MLT_BENCH_OVERSUBSCRIBE="1")
     env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "256", "--sustain-s", "0"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "256", "--sustain-s", "0"],
                          env=env, capture_output=True, text=True, timeout=900, cwd=root)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
@@ -919,7 +919,7 @@ print("RCCL_OK", hashlib.sha256(got).hexdigest()[:16], len(got))
     out = subprocess.run([sys.executable, str(probe)], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "RCCL_OK" in out.stdout, out.stdout[-1500:] + out.stderr[-1500:]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port + 1),
-           os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "256", "--no-cpu-baseline", "--sustain-s", "0"]
+           os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "256", "--no-cpu-baseline", "--sustain-s", "0"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-1500:] + out.stderr[-1500:]

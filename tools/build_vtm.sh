@@ -19,7 +19,8 @@
 set -euo pipefail
 REPO="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 REF=/root/reference/vtm-mlt-cpp
-WORK=${TMPDIR:-/tmp}/mltcnn_vtm
+# one scratch tree per user and checkout: another user's tree is not writable, another checkout's would configure against its own repository
+WORK=${TMPDIR:-/tmp}/mltcnn_vtm-$(id -u)-$(printf '%s' "$REPO" | sha256sum | cut -c1-12)
 JOBS=6
 while [ $# -gt 0 ]; do
   case "$1" in
@@ -39,6 +40,7 @@ PATCHSUM=$(cat "$REPO/patches/vtm-mlt-cpp-mltcnn.patch" "$REPO/patches/vtm-mlt-c
 if [ ! -f "$WORK/src/.patched" ] || [ "$(cat "$WORK/src/.patched")" != "$PATCHSUM" ]; then
   rm -rf "$WORK/src"; mkdir -p "$WORK/src"
   (cd "$REF" && cp -r CMakeLists.txt cmake source cfg "$WORK/src/")
+  chmod -R u+w "$WORK/src"   # the copy keeps the reference's read-only modes: patch and CMake write into it
   (cd "$WORK/src" && patch -p1 --fuzz=0 < "$REPO/patches/vtm-mlt-cpp-mltcnn.patch")
   (cd "$WORK/src" && patch -p1 --fuzz=0 < "$REPO/patches/vtm-mlt-cpp-mltcnn-n3.patch")
   echo "$PATCHSUM" > "$WORK/src/.patched"
