@@ -27,7 +27,9 @@ FLAG_NO_MAGNITUDE_GUARD = 0x80  # round 6 (measurement): never admit a tier behi
 FLAG_NO_DECISION_GUARD = 0x20  # ABI 4: no exact re-evaluation of CUs with a near-tie on the decision head (measurement only)
 EXPORTS = ["mlt_abi_version", "mlt_build_signature", "mlt_init", "mlt_num_devices", "mlt_device_ctx", "mlt_load_weights", "mlt_calibrate", "mlt_arithmetic", "mlt_predict", "mlt_predict_batch",
            "mlt_predict_batch_device", "mlt_submit", "mlt_flush", "mlt_wait", "mlt_synchronize", "mlt_set_stream", "mlt_alloc_pinned", "mlt_free_pinned",
-           "mlt_num_logits", "mlt_profile_enable", "mlt_profile_read", "mlt_last_error", "mlt_shutdown"]
+           "mlt_num_logits", "mlt_profile_enable", "mlt_profile_read", "mlt_last_error", "mlt_shutdown",
+           "mlt_set_confidence_gate", "mlt_get_confidence_gate", "mlt_predict_decision", "mlt_predict_batch_decisions", "mlt_predict_batch_device_decisions",
+           "mlt_wait_decision"]
 
 
 class MltConfig(C.Structure):
@@ -43,6 +45,17 @@ class MltArithInfo(C.Structure):
                 ("w2_stages", C.c_int32), ("guard_margin", C.c_float), ("x_stages", C.c_int32), ("w2_units", C.c_int32), ("x_units", C.c_int32), ("rounding", C.c_int32),
                 ("calib_cus", C.c_int32), ("calib_caller_cus", C.c_int32), ("mag_guard_thr", C.c_float), ("mag_guard_flagged", C.c_float),
                 ("mag_guard_kind", C.c_int32)]
+
+
+class MltDecision(C.Structure):
+    """`struct mlt_decision` (include/mltcnn.h): 48 bytes, no padding."""
+    _fields_ = [("split_mode", C.c_int32), ("raw_mode", C.c_int32), ("confidence", C.c_float), ("margin", C.c_float),
+                ("level_mode", C.c_int32 * 4), ("level_conf", C.c_float * 4)]
+
+
+# the same layout as a numpy structured dtype (what the batch calls return and decisions.from_logits builds)
+DECISION_DTYPE = np.dtype([("split_mode", "<i4"), ("raw_mode", "<i4"), ("confidence", "<f4"), ("margin", "<f4"),
+                           ("level_mode", "<i4", (4,)), ("level_conf", "<f4", (4,))])
 
 
 class MltKernelTime(C.Structure):
@@ -97,6 +110,12 @@ def load_library():
     lib.mlt_submit.argtypes = [vp, vp, i32, vp, i32, i32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     lib.mlt_flush.argtypes = [vp, i32]
     lib.mlt_wait.argtypes = [vp, i32, C.c_uint64, vp, vp]
+    lib.mlt_set_confidence_gate.argtypes = [vp, i32, C.c_float]
+    lib.mlt_get_confidence_gate.argtypes = [vp, i32, C.POINTER(C.c_float)]
+    lib.mlt_predict_decision.argtypes = [vp, vp, i32, vp, i32, i32, C.c_int32, C.c_int32, C.POINTER(MltDecision), vp]
+    lib.mlt_predict_batch_decisions.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.mlt_predict_batch_device_decisions.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.mlt_wait_decision.argtypes = [vp, i32, C.c_uint64, C.POINTER(MltDecision), vp]
     lib.mlt_synchronize.argtypes = [vp]
     lib.mlt_set_stream.argtypes = [vp, vp]
     lib.mlt_alloc_pinned.restype = vp
@@ -240,10 +259,64 @@ class MltCnn:
         self._check(self._lib.mlt_wait(self._h, size, C.c_uint64(ticket), C.byref(split), logits.ctypes.data))
         return int(split.value), logits
 
-    def predict_batch_device(self, n: int, size: int, d_org: int, d_pred: int, d_poc: int, d_qp: int, d_split: int,
-                             d_logits: int | None):
-        """Raw device pointers (e.g. torch tensor .data_ptr()); asynchronous on the context's stream."""
+    def predict_batch_device(self, n: int, size: int, d_org: int, d_pred: int, d_poc: int, d_qp: int, d_split: int | None,
+                             d_logits: int | None, d_decisions: int | None = None):
+        """Raw device pointers (e.g. torch tensor .data_ptr()); asynchronous on the context's stream.
+        d_decisions: n x 48 bytes of device memory -> the decision records instead of the split modes (mlt_predict_batch_device_decisions)."""
+        if d_decisions is not None:
+            assert d_split is None, "one call fills either the split modes or the decision records"
+            self._check(self._lib.mlt_predict_batch_device_decisions(self._h, n, size, d_org, d_pred, d_poc, d_qp, d_decisions, d_logits))
+            return
         self._check(self._lib.mlt_predict_batch_device(self._h, n, size, d_org, d_pred, d_poc, d_qp, d_split, d_logits))
+
+    # -- per-level decisions with confidence, and the confidence gate ------------------------------
+    def set_confidence_gate(self, size: int, min_confidence: float):
+        """split = -1 unless the decision head's softmax probability reaches min_confidence (0 = off); every entry point, every device."""
+        self._check(self._lib.mlt_set_confidence_gate(self._h, size, float(min_confidence)))
+
+    def confidence_gate(self, size: int, device_index: int = 0) -> float:
+        h = self._lib.mlt_device_ctx(self._h, device_index)
+        if not h:
+            raise MltError(1, "no such device index")
+        v = C.c_float(-1.0)
+        rc = self._lib.mlt_get_confidence_gate(h, size, C.byref(v))
+        if rc != MLT_OK:
+            raise MltError(rc, self._lib.mlt_last_error(h).decode())
+        return float(v.value)
+
+    @staticmethod
+    def _record(d: MltDecision) -> np.ndarray:
+        return np.frombuffer(bytes(d), DECISION_DTYPE)[0].copy()
+
+    def predict_decision(self, org: np.ndarray, pred: np.ndarray, poc: int, qp: int):
+        """`predict` returning the CU's decision record (a DECISION_DTYPE scalar) and the logits."""
+        assert org.dtype == np.int16 and pred.dtype == np.int16 and org.ndim == 2 and org.shape == pred.shape
+        S = org.shape[0]
+        assert org.shape[1] == S and org.strides[1] == 2 and pred.strides[1] == 2
+        d = MltDecision(-1, -1)
+        logits = np.zeros(self.num_logits(S) or 1, np.float32)
+        self._check(self._lib.mlt_predict_decision(self._h, org.ctypes.data, org.strides[0] // 2, pred.ctypes.data,
+                                                   pred.strides[0] // 2, S, int(poc), int(qp), C.byref(d), logits.ctypes.data))
+        return self._record(d), logits
+
+    def predict_batch_decisions(self, org: np.ndarray, pred: np.ndarray, poc, qp, want_logits: bool = True):
+        org = np.ascontiguousarray(org, np.int16)
+        pred = np.ascontiguousarray(pred, np.int16)
+        n, S, _ = org.shape
+        poc = np.ascontiguousarray(poc, np.int32)
+        qp = np.ascontiguousarray(qp, np.int32)
+        dec = np.zeros((n,), DECISION_DTYPE)
+        dec["split_mode"] = -1
+        logits = np.zeros((n, self.num_logits(S) or 1), np.float32) if want_logits else None
+        self._check(self._lib.mlt_predict_batch_decisions(self._h, n, S, org.ctypes.data, pred.ctypes.data, poc.ctypes.data,
+                                                          qp.ctypes.data, dec.ctypes.data, logits.ctypes.data if want_logits else None))
+        return dec, logits
+
+    def wait_decision(self, size: int, ticket: int):
+        d = MltDecision(-1, -1)
+        logits = np.zeros(self.num_logits(size) or 1, np.float32)
+        self._check(self._lib.mlt_wait_decision(self._h, size, C.c_uint64(ticket), C.byref(d), logits.ctypes.data))
+        return self._record(d), logits
 
     def synchronize(self):
         self._check(self._lib.mlt_synchronize(self._h))

@@ -172,6 +172,10 @@ struct SizeState {
   double guard_us[16] = {0};
   int guard_n[16] = {0};
   int size = 0, head_index = 0;
+  float min_conf = 0.f;        // confidence gate (mlt_set_confidence_gate): split = -1 unless the decision head's softmax probability reaches it.  0: off.  Not a
+                               // property of the weights: (re)loads and calibrations keep it
+  // the gate guard's band (mlt_kernels.h: MLT_CONF_BAND_FRAC x the tolerance the tier was calibrated against); 0 unless gate and decision guard are both on
+  float conf_band(float tolerance) const { return (min_conf > 0.f && margin_guard) ? MLT_CONF_BAND_FRAC * tolerance : 0.f; }
   mlt::Model model;
   mlt::Model model_exact;      // fast sizes: exact-arithmetic copy the guards re-evaluate flagged CUs with
   mlt::Model model_w2;         // hi+lo-weights copy on the fast tiling (MLT_MODEL_W2); built only when the single-pass calibration fails
@@ -191,7 +195,7 @@ struct GuardSlot {
                                // selection rides on the heads kernel, and the caller's own result copy brings the count back
 };
 // guard selection fused into the heads kernel of a single-CU launch (HeadArgs.g_*)
-struct GuardTail { int32_t *count, *idx, *flat; int flat_thr, near_thr; float margin, mag_thr; int32_t *next; };  // next != NULL: batches (HeadArgs.g_next)
+struct GuardTail { int32_t *count, *idx, *flat; int flat_thr, near_thr; float margin, mag_thr; int32_t *next; float conf_band; };  // next != NULL: batches (HeadArgs.g_next)
 
 // mlt_predict (one CU per call, the encoder's use): pinned host staging, one H2D, the kernel chain replayed from a
 // hipGraph captured once per CU size, one D2H.
@@ -248,7 +252,7 @@ struct mlt_ctx {
   int stage_chunk = 512;  // measured on 4096 x 128x128 from pinned memory: 512 -> 526 k, 1024 -> 498 k, 2048 -> 426 k CU/s
   char *h_res = nullptr;  // pinned result staging (split + logits) for the two sets
   size_t h_res_bytes = 0;
-  SingleCu single[4];
+  SingleCu single[8];   // [4 + si]: the calls that want the decision record (their graph bakes the record pointer into the heads kernel's arguments)
   Deferred deferred[4];
   // staging for the host-pointer entry points
   char *stage = nullptr;
@@ -279,6 +283,11 @@ struct mlt_ctx {
 };
 
 namespace {
+
+// the device-side record (mlt_kernels.h) is the C ABI's mlt_decision, field for field
+static_assert(sizeof(mlt_decision) == 48 && sizeof(DecisionRec) == sizeof(mlt_decision), "mlt_decision is 48 bytes");
+static_assert(offsetof(mlt_decision, confidence) == offsetof(DecisionRec, confidence) && offsetof(mlt_decision, level_mode) == offsetof(DecisionRec, level_mode) &&
+              offsetof(mlt_decision, level_conf) == offsetof(DecisionRec, level_conf) && offsetof(mlt_decision, level_conf) == 32, "mlt_decision layout");
 
 #define HIP_TRY(ctx, expr)                                                                             \
   do {                                                                                                 \
@@ -844,7 +853,7 @@ NetPlan plan_network(const mlt_ctx *ctx, const NetCfg &c, unsigned cls) {
 int run_network(mlt_ctx *ctx, SizeState &st, mlt::Model &m, int n, const int16_t *d_org, long org_rs, long org_cs, const int16_t *d_pred,
                 long pred_rs, long pred_cs, const int32_t *d_poc, const int32_t *d_qp, int32_t *d_split, float *d_logits, int32_t *d_flat = nullptr,
                 mlt::Model *mback = nullptr, unsigned back_mask = 0, const GuardTail *tail = nullptr, bool flat_is_clear = false,
-                mlt::Model *mx = nullptr, unsigned x_units = 0, float *d_mag = nullptr) {
+                mlt::Model *mx = nullptr, unsigned x_units = 0, float *d_mag = nullptr, DecisionRec *d_dec = nullptr) {
   const int S = st.size;
   if (!mx) x_units = 0;
   if (!mback) back_mask = 0;
@@ -971,7 +980,9 @@ int run_network(mlt_ctx *ctx, SizeState &st, mlt::Model &m, int n, const int16_t
       }
       ha.n_heads = m.n_heads; ha.decision_head = st.head_index; ha.poc = d_poc; ha.qp = d_qp; ha.logits = d_logits; ha.split = d_split;
       ha.mag = d_mag;
+      ha.dec = d_dec; ha.min_conf = st.min_conf;
       if (tail && (n == 1 || tail->next)) {
+        ha.g_conf_band = tail->conf_band;
         ha.g_next = tail->next;   // (NULL: mlt_predict's slot -- one CU, the count is set outright)
         ha.g_count = tail->count; ha.g_idx = tail->idx; ha.g_flat = tail->flat; ha.g_flat_thr = tail->flat_thr; ha.g_near_thr = tail->near_thr; ha.g_margin = tail->margin;
         ha.g_mag_thr = tail->mag_thr;
@@ -1044,17 +1055,18 @@ struct Planes {  // the two Pel planes of a batch in device memory (element stri
 
 int run_main(mlt_ctx *ctx, SizeState &st, int n, const int16_t *d_org, long org_rs, long org_cs, const int16_t *d_pred, long pred_rs, long pred_cs,
              const int32_t *d_poc, const int32_t *d_qp, int32_t *d_split, float *d_logits, int32_t *d_flat = nullptr, const GuardTail *tail = nullptr,
-             bool flat_is_clear = false, float *d_mag = nullptr) {
+             bool flat_is_clear = false, float *d_mag = nullptr, DecisionRec *d_dec = nullptr) {
   // (hi+lo-weights tiers: the two-plane model in the stages of w2_mask, single pass in the others)
   return run_network(ctx, st, st.model, n, d_org, org_rs, org_cs, d_pred, pred_rs, pred_cs, d_poc, d_qp, d_split, d_logits, d_flat,
-                     st.w2 ? &st.model_w2 : nullptr, st.w2 ? st.w2_units : 0u, tail, flat_is_clear, st.x_units ? &st.model_exact : nullptr, st.x_units, d_mag);
+                     st.w2 ? &st.model_w2 : nullptr, st.w2 ? st.w2_units : 0u, tail, flat_is_clear, st.x_units ? &st.model_exact : nullptr, st.x_units, d_mag, d_dec);
 }
 
 // fast network + guard selection for n CUs, everything asynchronous on ctx->stream; the count lands in g.h_count
 // (pinned) -- valid after the stream has been synchronised.  d_logits may be NULL.
 int run_guarded_async(mlt_ctx *ctx, SizeState &st, int n, const Planes &pl, const int32_t *d_poc, const int32_t *d_qp, int32_t *d_split,
-                      float *d_logits, const GuardSlot &g) {
+                      float *d_logits, const GuardSlot &g, DecisionRec *d_dec = nullptr) {
   const int S = st.size, nl = st.model.n_logits;
+  const float band = st.conf_band(ctx->tolerance);
   Launch L{ctx};
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int rc;
@@ -1063,8 +1075,8 @@ int run_guarded_async(mlt_ctx *ctx, SizeState &st, int n, const Planes &pl, cons
     // one CU (mlt_predict's captured graph): the selection is a tail of the heads kernel -- no guard_select launch, no memset of the
     // statistic (the tail clears it for the next call; it is only consumed when the first kernel is the one that produces it: aligned planes,
     // S >= 64 -- else flat_stat_kernel overwrites it), no separate copy of the count (the caller's result copy carries it)
-    const GuardTail tail{g.d_count, g.d_idx, st.flat_guard ? g.d_flat : nullptr, (S * S / 4) / st.flat_div, (S * S / 4) / 2, st.margin_guard ? st.guard_margin : 0.f, st.mag_thr, nullptr};
-    return run_main(ctx, st, 1, pl.org, pl.org_rs, pl.org_cs, pl.pred, pl.pred_rs, pl.pred_cs, d_poc, d_qp, d_split, lg, st.flat_guard ? g.d_flat : nullptr, &tail, true);
+    const GuardTail tail{g.d_count, g.d_idx, st.flat_guard ? g.d_flat : nullptr, (S * S / 4) / st.flat_div, (S * S / 4) / 2, st.margin_guard ? st.guard_margin : 0.f, st.mag_thr, nullptr, band};
+    return run_main(ctx, st, 1, pl.org, pl.org_rs, pl.org_cs, pl.pred, pl.pred_rs, pl.pred_cs, d_poc, d_qp, d_split, lg, st.flat_guard ? g.d_flat : nullptr, &tail, true, nullptr, d_dec);
   }
   if (!ctx->guard_select_kernel && g.phase) {
     // round 6: the selection is a tail of the heads kernel for batches as well -- an unordered list of the flagged CUs through an atomic append on a counter that is
@@ -1072,9 +1084,9 @@ int run_guarded_async(mlt_ctx *ctx, SizeState &st, int n, const Planes &pl, cons
     // one launch gap less per step.  (A first version counted finished workgroups to let the last one publish and re-arm a single counter: 4096 same-address atomics
     // and release fences made the heads launch 0.123 ms instead of 0.030 -- more than the launch it saved.)
     int32_t *cnt = g.d_count + *g.phase, *next = g.d_count + (*g.phase ^ 1);
-    const GuardTail tail{cnt, g.d_idx, st.flat_guard ? g.d_flat : nullptr, (S * S / 4) / st.flat_div, (S * S / 4) / 2, st.margin_guard ? st.guard_margin : 0.f, st.mag_thr, next};
+    const GuardTail tail{cnt, g.d_idx, st.flat_guard ? g.d_flat : nullptr, (S * S / 4) / st.flat_div, (S * S / 4) / 2, st.margin_guard ? st.guard_margin : 0.f, st.mag_thr, next, band};
     if ((rc = run_main(ctx, st, n, pl.org, pl.org_rs, pl.org_cs, pl.pred, pl.pred_rs, pl.pred_cs, d_poc, d_qp, d_split, lg,
-                       st.flat_guard ? g.d_flat : nullptr, &tail))) {
+                       st.flat_guard ? g.d_flat : nullptr, &tail, false, nullptr, d_dec))) {
       // a pass that failed (e.g. no memory for the workspace of an oversized batch -- the caller may come back with a smaller one) may or may not have run its heads
       // kernel: both counters back to zero, the phase stays -- whichever counter the next launch counts on is zero on entry
       (void)hipMemsetAsync(g.d_count, 0, 8, ctx->stream);
@@ -1086,7 +1098,7 @@ int run_guarded_async(mlt_ctx *ctx, SizeState &st, int n, const Planes &pl, cons
   }
   float *mg = st.mag_thr > 0.f ? g.d_mag : nullptr;
   if ((rc = run_main(ctx, st, n, pl.org, pl.org_rs, pl.org_cs, pl.pred, pl.pred_rs, pl.pred_cs, d_poc, d_qp, d_split, lg,
-                     st.flat_guard ? g.d_flat : nullptr, nullptr, false, mg))) return rc;
+                     st.flat_guard ? g.d_flat : nullptr, nullptr, false, mg, d_dec))) return rc;
   GuardSelectArgs sa{};
   sa.mag = mg; sa.mag_thr = st.mag_thr;
   sa.flat = st.flat_guard ? g.d_flat : nullptr;
@@ -1098,6 +1110,7 @@ int run_guarded_async(mlt_ctx *ctx, SizeState &st, int n, const Planes &pl, cons
   sa.flat_thr = (S * S / 4) / st.flat_div;  // >= 1/8 (exact-lite tier: 1/16) of the quads exactly flat (constant / exactly linear in both planes)
   sa.near_thr = (S * S / 4) / 2;  // or >= 1/2 of them near-flat (mlt_kernels.h: MLT_FLAT_RANGE)
   sa.margin = st.margin_guard ? st.guard_margin : 0.f;
+  sa.min_conf = st.min_conf; sa.conf_band = band;
   if ((rc = L.prof_begin("guard_select", 0.0, 0.0, e0, e1))) return rc;
   LAUNCH_TRY(ctx, mlt_launch_guard_select(sa, ctx->stream));
   if ((rc = L.prof_end(e1))) return rc;
@@ -1107,11 +1120,11 @@ int run_guarded_async(mlt_ctx *ctx, SizeState &st, int n, const Planes &pl, cons
 
 // k > 0 flagged CUs (g.d_idx) of a batch whose fast results are in d_split / d_logits: exact re-evaluation, asynchronous.
 int guard_fixup_async(mlt_ctx *ctx, SizeState &st, int k, const Planes &pl, const int32_t *d_poc, const int32_t *d_qp, int32_t *d_split,
-                      float *d_logits, const GuardSlot &g) {
+                      float *d_logits, const GuardSlot &g, DecisionRec *d_dec = nullptr) {
   const int S = st.size, nl = st.model.n_logits;
   const size_t cs = (size_t)S * S;
   const size_t plane = (cs * 2 * k + 255) / 256 * 256, small = ((size_t)k * 4 + 255) / 256 * 256, lgb = ((size_t)k * nl * 4 + 255) / 256 * 256;
-  const size_t need = 2 * plane + 3 * small + lgb;
+  const size_t need = 2 * plane + 3 * small + lgb + (d_dec ? (size_t)k * sizeof(DecisionRec) : 0);
   if (need > ctx->gstage_bytes) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->gstage) (void)hipFree(ctx->gstage);
@@ -1126,10 +1139,14 @@ int guard_fixup_async(mlt_ctx *ctx, SizeState &st, int k, const Planes &pl, cons
   ga.g_poc = (int32_t *)(ctx->gstage + 2 * plane); ga.g_qp = (int32_t *)(ctx->gstage + 2 * plane + small);
   int32_t *g_split = (int32_t *)(ctx->gstage + 2 * plane + 2 * small);
   float *g_lg = (float *)(ctx->gstage + 2 * plane + 3 * small);
+  DecisionRec *g_dec = d_dec ? (DecisionRec *)(ctx->gstage + 2 * plane + 3 * small + lgb) : nullptr;
   HIP_TRY(ctx, mlt_launch_guard_gather(ga, ctx->stream));
-  int rc = run_network(ctx, st, st.model_exact, k, ga.g_org, S, (long)cs, ga.g_pred, S, (long)cs, ga.g_poc, ga.g_qp, g_split, g_lg);
+  // (the re-run's heads kernel applies the size's confidence gate to g_split and fills the flagged CUs' records from the exact logits)
+  int rc = run_network(ctx, st, st.model_exact, k, ga.g_org, S, (long)cs, ga.g_pred, S, (long)cs, ga.g_poc, ga.g_qp, g_split, g_lg, nullptr, nullptr, 0, nullptr, false,
+                       nullptr, 0, nullptr, g_dec);
   if (rc) return rc;
   GuardScatterArgs sc{};
+  sc.g_dec = g_dec; sc.dec = d_dec;
   sc.idx = g.d_idx; sc.g_split = g_split; sc.g_logits = g_lg; sc.split = d_split; sc.logits = d_logits; sc.k = k; sc.n_logits = nl;
   HIP_TRY(ctx, mlt_launch_guard_scatter(sc, ctx->stream));
   st.reruns += (uint64_t)k;
@@ -1137,13 +1154,14 @@ int guard_fixup_async(mlt_ctx *ctx, SizeState &st, int k, const Planes &pl, cons
 }
 
 // network for n CUs with whatever guards the size has; synchronises once when guards are on (see mlt_predict_batch_device).
-int run_checked(mlt_ctx *ctx, SizeState &st, int n, const Planes &pl, const int32_t *d_poc, const int32_t *d_qp, int32_t *d_split, float *d_logits) {
+int run_checked(mlt_ctx *ctx, SizeState &st, int n, const Planes &pl, const int32_t *d_poc, const int32_t *d_qp, int32_t *d_split, float *d_logits,
+                DecisionRec *d_dec = nullptr) {
   if (!st.guards())
-    return run_main(ctx, st, n, pl.org, pl.org_rs, pl.org_cs, pl.pred, pl.pred_rs, pl.pred_cs, d_poc, d_qp, d_split, d_logits);
+    return run_main(ctx, st, n, pl.org, pl.org_rs, pl.org_cs, pl.pred, pl.pred_rs, pl.pred_cs, d_poc, d_qp, d_split, d_logits, nullptr, nullptr, false, nullptr, d_dec);
   GuardSlot g;
   int rc = guard_slot(ctx, 0, n, st.model.n_logits, &g);
   if (rc) return rc;
-  if ((rc = run_guarded_async(ctx, st, n, pl, d_poc, d_qp, d_split, d_logits, g))) return rc;
+  if ((rc = run_guarded_async(ctx, st, n, pl, d_poc, d_qp, d_split, d_logits, g, d_dec))) return rc;
   // Wait for the 4-byte count.  Default: SLEEP for most of the time the batch is expected to take (a running estimate per CU of this
   // size, learnt from the previous calls), then poll the event for the rest: the host core is idle for all but the last ~0.2 ms of a
   // 5 ms batch -- in the encoder host cores are the scarce resource -- and the caller's next batch is still enqueued the moment this one
@@ -1184,7 +1202,7 @@ int run_checked(mlt_ctx *ctx, SizeState &st, int n, const Planes &pl, const int3
   }
   const int k = *g.h_count;
   if (k < 0 || k > n) { ctx->err = "guard: bad flagged-CU count"; return MLT_ERR_HIP; }
-  return k ? guard_fixup_async(ctx, st, k, pl, d_poc, d_qp, d_split, d_logits, g) : MLT_OK;
+  return k ? guard_fixup_async(ctx, st, k, pl, d_poc, d_qp, d_split, d_logits, g, d_dec) : MLT_OK;
 }
 
 // ---- load-time calibration of the fast arithmetic against the exact one (include/mltcnn.h: mlt_load_weights) ----
@@ -1632,10 +1650,12 @@ struct CalibSession {
 };
 
 void drop_graphs(mlt_ctx *ctx, int si) {  // a captured kernel chain bakes in weight / workspace pointers
-  SingleCu &sg = ctx->single[si];
-  if (sg.exec) (void)hipGraphExecDestroy(sg.exec);
-  if (sg.graph) (void)hipGraphDestroy(sg.graph);
-  sg.exec = nullptr; sg.graph = nullptr;
+  for (int v = 0; v < 2; ++v) {
+    SingleCu &sg = ctx->single[si + 4 * v];
+    if (sg.exec) (void)hipGraphExecDestroy(sg.exec);
+    if (sg.graph) (void)hipGraphDestroy(sg.graph);
+    sg.exec = nullptr; sg.graph = nullptr;
+  }
 }
 
 // The pricer of the tier search (mlt_tier_search.h) on the device: a configuration = launch units in hi+lo weights / in the exact arithmetic +
@@ -2194,10 +2214,11 @@ int mlt_synchronize(mlt_ctx *ctx) {
   return MLT_OK;
 }
 
-int mlt_predict_batch_device(mlt_ctx *ctx, int n, int size, const void *d_org, const void *d_pred, const void *d_poc, const void *d_qp,
-                             void *d_split_mode, void *d_logits) {
+// mlt_predict_batch_device / mlt_predict_batch_device_decisions: one of d_split_mode / d_dec may be NULL
+static int predict_batch_device_impl(mlt_ctx *ctx, int n, int size, const void *d_org, const void *d_pred, const void *d_poc, const void *d_qp,
+                                     void *d_split_mode, void *d_logits, DecisionRec *d_dec) {
   if (!ctx) return MLT_ERR_ARG;
-  if (n < 0 || !d_split_mode || (n > 0 && (!d_org || !d_pred || !d_poc || !d_qp))) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  if (n < 0 || (!d_split_mode && !d_dec) || (n > 0 && (!d_org || !d_pred || !d_poc || !d_qp))) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
   SizeState *st;
   int rc = check_size(ctx, size, &st);
   if (rc) return rc;
@@ -2208,17 +2229,29 @@ int mlt_predict_batch_device(mlt_ctx *ctx, int n, int size, const void *d_org, c
   for (int i0 = 0; i0 < n; i0 += ctx->chunk) {
     const int c = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
     const Planes pl{(const int16_t *)d_org + (size_t)i0 * cs, (const int16_t *)d_pred + (size_t)i0 * cs, size, cs, size, cs};
-    rc = run_checked(ctx, *st, c, pl, (const int32_t *)d_poc + i0, (const int32_t *)d_qp + i0, (int32_t *)d_split_mode + i0,
-                     d_logits ? (float *)d_logits + (size_t)i0 * nl : nullptr);
+    rc = run_checked(ctx, *st, c, pl, (const int32_t *)d_poc + i0, (const int32_t *)d_qp + i0, d_split_mode ? (int32_t *)d_split_mode + i0 : nullptr,
+                     d_logits ? (float *)d_logits + (size_t)i0 * nl : nullptr, d_dec ? d_dec + i0 : nullptr);
     if (rc) return rc;
   }
   return MLT_OK;
 }
 
+int mlt_predict_batch_device(mlt_ctx *ctx, int n, int size, const void *d_org, const void *d_pred, const void *d_poc, const void *d_qp,
+                             void *d_split_mode, void *d_logits) {
+  if (ctx && !d_split_mode) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  return predict_batch_device_impl(ctx, n, size, d_org, d_pred, d_poc, d_qp, d_split_mode, d_logits, nullptr);
+}
+
+int mlt_predict_batch_device_decisions(mlt_ctx *ctx, int n, int size, const void *d_org, const void *d_pred, const void *d_poc, const void *d_qp,
+                                       void *d_decisions, void *d_logits) {
+  if (ctx && !d_decisions) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  return predict_batch_device_impl(ctx, n, size, d_org, d_pred, d_poc, d_qp, nullptr, d_logits, (DecisionRec *)d_decisions);
+}
+
 static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *org, const int16_t *pred, const int32_t *poc, const int32_t *qp,
-                      int32_t *split_mode, float *logits) {
+                      int32_t *split_mode, float *logits, mlt_decision *dec = nullptr) {   // split_mode or dec may be NULL, not both
   if (!ctx) return MLT_ERR_ARG;
-  if (n < 0 || !split_mode || (n > 0 && (!org || !pred || !poc || !qp))) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  if (n < 0 || (!split_mode && !dec) || (n > 0 && (!org || !pred || !poc || !qp))) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
   SizeState *st;
   int rc = check_size(ctx, size, &st);
   if (rc) return rc;
@@ -2233,7 +2266,8 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
   const size_t plane = (cs * 2 * cap + 255) / 256 * 256;
   const size_t small = ((size_t)cap * 4 + 255) / 256 * 256;
   const size_t lgb = ((size_t)cap * nl * 4 + 255) / 256 * 256;
-  const size_t setbytes = 2 * plane + 3 * small + lgb;
+  const size_t decb = dec ? ((size_t)cap * sizeof(DecisionRec) + 255) / 256 * 256 : 0;   // the records sit beside the split modes and the logits
+  const size_t setbytes = 2 * plane + 3 * small + lgb + decb;
   const int nset = n > cap ? 2 : 1;
   if ((rc = ensure_stage(ctx, nset * setbytes))) return rc;
   if (nset == 2 && !ctx->copy_stream) {
@@ -2243,11 +2277,12 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
       if (!ctx->ev_done[b]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_done[b], hipEventDisableTiming));
     }
   }
-  struct Set { int16_t *d_org, *d_pred; int32_t *d_poc, *d_qp, *d_split; float *d_lg; };
+  struct Set { int16_t *d_org, *d_pred; int32_t *d_poc, *d_qp, *d_split; float *d_lg; DecisionRec *d_dec; };
   auto set_of = [&](int b) {
     char *base = ctx->stage + (size_t)b * setbytes;
     return Set{(int16_t *)base, (int16_t *)(base + plane), (int32_t *)(base + 2 * plane), (int32_t *)(base + 2 * plane + small),
-               (int32_t *)(base + 2 * plane + 2 * small), (float *)(base + 2 * plane + 3 * small)};
+               (int32_t *)(base + 2 * plane + 2 * small), (float *)(base + 2 * plane + 3 * small),
+               dec ? (DecisionRec *)(base + 2 * plane + 3 * small + lgb) : nullptr};
   };
   const bool guards = st->guards();
   GuardSlot gs[2];
@@ -2256,7 +2291,8 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
       if ((rc = guard_slot(ctx, b, cap, nl, &gs[b]))) return rc;
   // Results come back through pinned buffers owned by the context: a D2H into the caller's (usually pageable) arrays
   // would block the host until the kernels are done and serialise the next sub-chunk's H2D behind them.
-  const size_t hres_set = (size_t)cap * 4 + (size_t)cap * nl * 4;
+  const size_t hres_set = (size_t)cap * 4 + (size_t)cap * nl * 4 + (dec ? (size_t)cap * sizeof(DecisionRec) : 0);
+  const size_t hres_dec = (size_t)cap * 4 + (size_t)cap * nl * 4;
   if (ctx->h_res_bytes < 2 * hres_set) {
     if (ctx->h_res) (void)hipHostFree(ctx->h_res);
     ctx->h_res = nullptr; ctx->h_res_bytes = 0;
@@ -2269,6 +2305,7 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
     char *hb = ctx->h_res + (size_t)b * hres_set;
     HIP_TRY(ctx, hipMemcpyAsync(hb, S.d_split, (size_t)c * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (logits) HIP_TRY(ctx, hipMemcpyAsync(hb + (size_t)cap * 4, S.d_lg, (size_t)c * nl * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (dec) HIP_TRY(ctx, hipMemcpyAsync(hb + hres_dec, S.d_dec, (size_t)c * sizeof(DecisionRec), hipMemcpyDeviceToHost, ctx->stream));
     return MLT_OK;
   };
   auto flush = [&](int b) -> int {  // sub-chunk in set b has completed: guard fix-up if needed, then hand its results to the caller
@@ -2280,15 +2317,16 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
       if (k > 0) {  // the set's inputs are still in place (the next H2D into it is issued after this flush)
         const Set S = set_of(b);
         const Planes pl{S.d_org, S.d_pred, size, (long)cs, size, (long)cs};
-        int r = guard_fixup_async(ctx, *st, k, pl, S.d_poc, S.d_qp, S.d_split, logits ? S.d_lg : nullptr, gs[b]);
+        int r = guard_fixup_async(ctx, *st, k, pl, S.d_poc, S.d_qp, S.d_split, logits ? S.d_lg : nullptr, gs[b], S.d_dec);
         if (r) return r;
         if ((r = fetch(b, pend_c[b]))) return r;
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       }
     }
     const char *hb = ctx->h_res + (size_t)b * hres_set;
-    std::memcpy(split_mode + pend_i0[b], hb, (size_t)pend_c[b] * 4);
+    if (split_mode) std::memcpy(split_mode + pend_i0[b], hb, (size_t)pend_c[b] * 4);
     if (logits) std::memcpy(logits + (size_t)pend_i0[b] * nl, hb + (size_t)cap * 4, (size_t)pend_c[b] * nl * 4);
+    if (dec) std::memcpy(dec + pend_i0[b], hb + hres_dec, (size_t)pend_c[b] * sizeof(DecisionRec));
     pend_i0[b] = -1;
     return MLT_OK;
   };
@@ -2310,8 +2348,8 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
       HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_h2d[b], 0));
     }
     const Planes pl{S.d_org, S.d_pred, size, (long)cs, size, (long)cs};
-    if (guards) rc = run_guarded_async(ctx, *st, c, pl, S.d_poc, S.d_qp, S.d_split, logits ? S.d_lg : nullptr, gs[b]);
-    else rc = run_main(ctx, *st, c, S.d_org, size, (long)cs, S.d_pred, size, (long)cs, S.d_poc, S.d_qp, S.d_split, logits ? S.d_lg : nullptr);
+    if (guards) rc = run_guarded_async(ctx, *st, c, pl, S.d_poc, S.d_qp, S.d_split, logits ? S.d_lg : nullptr, gs[b], S.d_dec);
+    else rc = run_main(ctx, *st, c, S.d_org, size, (long)cs, S.d_pred, size, (long)cs, S.d_poc, S.d_qp, S.d_split, logits ? S.d_lg : nullptr, nullptr, nullptr, false, nullptr, S.d_dec);
     if (rc) return rc;
     if ((rc = fetch(b, c))) return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_done[b], ctx->stream));
@@ -2324,10 +2362,11 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
   return MLT_OK;
 }
 
-int mlt_predict_batch(mlt_ctx *ctx, int n, int size, const int16_t *org, const int16_t *pred, const int32_t *poc, const int32_t *qp,
-                      int32_t *split_mode, float *logits) {
+// mlt_predict_batch / mlt_predict_batch_decisions (split_mode or dec may be NULL, not both)
+static int predict_batch_impl(mlt_ctx *ctx, int n, int size, const int16_t *org, const int16_t *pred, const int32_t *poc, const int32_t *qp,
+                              int32_t *split_mode, float *logits, mlt_decision *dec) {
   if (!ctx) return MLT_ERR_ARG;
-  if (n < 0 || !split_mode || (n > 0 && (!org || !pred || !poc || !qp))) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  if (n < 0 || (!split_mode && !dec) || (n > 0 && (!org || !pred || !poc || !qp))) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
   SizeState *st;
   int rc = check_size(ctx, size, &st);
   if (rc) return rc;
@@ -2343,7 +2382,7 @@ int mlt_predict_batch(mlt_ctx *ctx, int n, int size, const int16_t *org, const i
     auto run = [&](int g) {
       const int lo = shard_lo(n, g, G), hi = shard_lo(n, g + 1, G);
       if (hi > lo) rcs[(size_t)g] = predict_batch_single(devs[(size_t)g], hi - lo, size, org + (size_t)lo * csz, pred + (size_t)lo * csz, poc + lo, qp + lo,
-                                                         split_mode + lo, logits ? logits + (size_t)lo * nlg : nullptr);
+                                                         split_mode ? split_mode + lo : nullptr, logits ? logits + (size_t)lo * nlg : nullptr, dec ? dec + lo : nullptr);
     };
     std::vector<std::thread> th;
     for (int g = 1; g < G; ++g) th.emplace_back(run, g);
@@ -2353,20 +2392,33 @@ int mlt_predict_batch(mlt_ctx *ctx, int n, int size, const int16_t *org, const i
       if (rcs[(size_t)g]) { if (g) ctx->err = "device " + std::to_string(devs[(size_t)g]->device) + ": " + devs[(size_t)g]->err; return rcs[(size_t)g]; }
     return MLT_OK;
   }
-  return predict_batch_single(ctx, n, size, org, pred, poc, qp, split_mode, logits);
+  return predict_batch_single(ctx, n, size, org, pred, poc, qp, split_mode, logits, dec);
 }
 
-int mlt_predict(mlt_ctx *ctx, const int16_t *org, int org_stride, const int16_t *pred, int pred_stride, int size, int32_t poc, int32_t qp,
-                int32_t *split_mode, float *logits_opt) {
+int mlt_predict_batch(mlt_ctx *ctx, int n, int size, const int16_t *org, const int16_t *pred, const int32_t *poc, const int32_t *qp,
+                      int32_t *split_mode, float *logits) {
+  if (ctx && !split_mode) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  return predict_batch_impl(ctx, n, size, org, pred, poc, qp, split_mode, logits, nullptr);
+}
+
+int mlt_predict_batch_decisions(mlt_ctx *ctx, int n, int size, const int16_t *org, const int16_t *pred, const int32_t *poc, const int32_t *qp,
+                                mlt_decision *out, float *logits) {
+  if (ctx && !out) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  return predict_batch_impl(ctx, n, size, org, pred, poc, qp, nullptr, logits, out);
+}
+
+// mlt_predict / mlt_predict_decision (split_mode or dec may be NULL, not both)
+static int predict_one(mlt_ctx *ctx, const int16_t *org, int org_stride, const int16_t *pred, int pred_stride, int size, int32_t poc, int32_t qp,
+                       int32_t *split_mode, float *logits_opt, mlt_decision *dec) {
   if (!ctx) return MLT_ERR_ARG;
-  if (!org || !pred || !split_mode || org_stride < size || pred_stride < size) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  if (!org || !pred || (!split_mode && !dec) || org_stride < size || pred_stride < size) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
   SizeState *st;
   int rc = check_size(ctx, size, &st);
   if (rc) return rc;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
   const int nl = st->model.n_logits;
   const size_t cs = (size_t)size * size;
-  SingleCu &sg = ctx->single[size_index(size)];
+  SingleCu &sg = ctx->single[size_index(size) + (dec ? 4 : 0)];   // (a graph of its own for the calls that want the record: plain calls replay the launches they always did)
   if (!sg.h_stage) {
     sg.plane = (cs * 2 + 255) / 256 * 256;
     HIP_TRY(ctx, hipHostMalloc((void **)&sg.h_stage, 2 * sg.plane + 256, hipHostMallocDefault));
@@ -2382,15 +2434,17 @@ int mlt_predict(mlt_ctx *ctx, const int16_t *org, int org_stride, const int16_t 
   h_sc[0] = poc; h_sc[1] = qp;
   HIP_TRY(ctx, hipMemcpyAsync(sg.d_stage, sg.h_stage, 2 * sg.plane + 8, hipMemcpyHostToDevice, ctx->stream));
   int16_t *d_org = (int16_t *)sg.d_stage, *d_pred = (int16_t *)(sg.d_stage + sg.plane);
-  int32_t *d_sc = (int32_t *)(sg.d_stage + 2 * sg.plane);  // [poc, qp, split, flagged count, logits (<= 16) ..., flat, idx]
+  int32_t *d_sc = (int32_t *)(sg.d_stage + 2 * sg.plane);  // [poc, qp, split, flagged count, logits (<= 16) ..., flat, idx, mag, pad, record (12 words at 24)]
+  DecisionRec *d_dec = dec ? (DecisionRec *)(d_sc + 24) : nullptr;
+  const size_t fetch = dec ? (size_t)(22 + 12) * 4 : (size_t)(2 + nl) * 4;   // split, count, logits [.. record]
   const Planes pl{d_org, d_pred, size, (long)cs, size, (long)cs};
   const bool guards = st->guards();
   GuardSlot g;
   g.d_count = d_sc + 3; g.d_flat = d_sc + 20; g.d_idx = d_sc + 21; g.d_lg = (float *)(d_sc + 4); g.d_mag = (float *)(d_sc + 22); g.h_count = h_sc + 3;
   g.single = true;  // (d_flat was zeroed with the staging buffer and is cleared by every call's heads kernel)
   auto chain = [&]() -> int {  // the kernel chain of one CU (captured into a hipGraph below)
-    if (!guards) return run_main(ctx, *st, 1, d_org, size, (long)cs, d_pred, size, (long)cs, d_sc, d_sc + 1, d_sc + 2, (float *)(d_sc + 4));
-    int r = run_guarded_async(ctx, *st, 1, pl, d_sc, d_sc + 1, d_sc + 2, (float *)(d_sc + 4), g);  // its 4-byte count D2H lands in h_sc[3]
+    if (!guards) return run_main(ctx, *st, 1, d_org, size, (long)cs, d_pred, size, (long)cs, d_sc, d_sc + 1, d_sc + 2, (float *)(d_sc + 4), nullptr, nullptr, false, nullptr, d_dec);
+    int r = run_guarded_async(ctx, *st, 1, pl, d_sc, d_sc + 1, d_sc + 2, (float *)(d_sc + 4), g, d_dec);  // its 4-byte count D2H lands in h_sc[3]
     return r;
   };
   const bool no_graph = tuning().no_graph;
@@ -2423,30 +2477,46 @@ int mlt_predict(mlt_ctx *ctx, const int16_t *org, int org_stride, const int16_t 
     }
   }
   if (!replayed && (rc = chain())) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(h_sc + 2, d_sc + 2, (size_t)(2 + nl) * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(h_sc + 2, d_sc + 2, fetch, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (guards && h_sc[3] != 0) {  // flagged (flat content / near-tie on the decision head): re-evaluate with the exact arithmetic
-    if ((rc = guard_fixup_async(ctx, *st, 1, pl, d_sc, d_sc + 1, d_sc + 2, (float *)(d_sc + 4), g))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(h_sc + 2, d_sc + 2, (size_t)(2 + nl) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = guard_fixup_async(ctx, *st, 1, pl, d_sc, d_sc + 1, d_sc + 2, (float *)(d_sc + 4), g, d_dec))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(h_sc + 2, d_sc + 2, fetch, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
-  *split_mode = h_sc[2];
+  if (split_mode) *split_mode = h_sc[2];
   if (logits_opt) std::memcpy(logits_opt, h_sc + 4, (size_t)nl * 4);
+  if (dec) std::memcpy(dec, h_sc + 24, sizeof(DecisionRec));
   return MLT_OK;
+}
+
+int mlt_predict(mlt_ctx *ctx, const int16_t *org, int org_stride, const int16_t *pred, int pred_stride, int size, int32_t poc, int32_t qp,
+                int32_t *split_mode, float *logits_opt) {
+  if (ctx && !split_mode) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  return predict_one(ctx, org, org_stride, pred, pred_stride, size, poc, qp, split_mode, logits_opt, nullptr);
+}
+
+int mlt_predict_decision(mlt_ctx *ctx, const int16_t *org, int org_stride, const int16_t *pred, int pred_stride, int size, int32_t poc, int32_t qp,
+                         mlt_decision *out, float *logits_opt) {
+  if (ctx && !out) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  return predict_one(ctx, org, org_stride, pred, pred_stride, size, poc, qp, nullptr, logits_opt, out);
 }
 
 // ---- deferred single-CU prediction ----
 namespace {
-// device / pinned layout of one output set: split[CAP] | logits[CAP * nl] | flagged count (16 ints) | flat[CAP] | idx[CAP]
-struct DeferredOut { int32_t *split; float *lg; int32_t *count, *flat, *idx; float *mag; };
+// device / pinned layout of one output set: split[CAP] | logits[CAP * nl] | flagged count (16 ints) | records[CAP] | flat[CAP] | idx[CAP] | mag[CAP]
+// (a deferred batch always carries its CUs' decision records -- whether a ticket is read with mlt_wait or mlt_wait_decision is not known when the batch is launched:
+// 3 KiB more in the batch's one result copy)
+struct DeferredOut { int32_t *split; float *lg; int32_t *count, *flat, *idx; float *mag; DecisionRec *dec; };
 DeferredOut deferred_out(char *base, int nl) {
   DeferredOut o;
   o.split = (int32_t *)base; o.lg = (float *)(base + (size_t)MLT_DEFER_CAP * 4);
   o.count = (int32_t *)(base + (size_t)MLT_DEFER_CAP * 4 * (1 + nl));
-  o.flat = o.count + 16; o.idx = o.flat + MLT_DEFER_CAP; o.mag = (float *)(o.idx + MLT_DEFER_CAP);
+  o.dec = (DecisionRec *)(o.count + 16);
+  o.flat = (int32_t *)(o.dec + MLT_DEFER_CAP); o.idx = o.flat + MLT_DEFER_CAP; o.mag = (float *)(o.idx + MLT_DEFER_CAP);
   return o;
 }
-size_t deferred_fetch_bytes(int nl) { return (size_t)MLT_DEFER_CAP * 4 * (1 + nl) + 64; }
+size_t deferred_fetch_bytes(int nl) { return (size_t)MLT_DEFER_CAP * 4 * (1 + nl) + 64 + (size_t)MLT_DEFER_CAP * sizeof(DecisionRec); }
 
 int deferred_launch(mlt_ctx *ctx, SizeState *st, Deferred &df) {  // launch the accumulating generation as one batch
   if (df.n == 0) return MLT_OK;
@@ -2465,10 +2535,10 @@ int deferred_launch(mlt_ctx *ctx, SizeState *st, Deferred &df) {  // launch the 
   if (st->guards()) {
     GuardSlot g;
     g.d_flat = od.flat; g.d_idx = od.idx; g.d_count = od.count; g.d_lg = od.lg; g.d_mag = od.mag; g.phase = &df.phase[b]; g.h_count = oh.count;
-    rc = run_guarded_async(ctx, *st, n, pl, d_poc, d_qp, od.split, od.lg, g);
+    rc = run_guarded_async(ctx, *st, n, pl, d_poc, d_qp, od.split, od.lg, g, od.dec);
     df.guard_pending[b] = true;
   } else {
-    rc = run_main(ctx, *st, n, pl.org, pl.org_rs, pl.org_cs, pl.pred, pl.pred_rs, pl.pred_cs, d_poc, d_qp, od.split, od.lg);
+    rc = run_main(ctx, *st, n, pl.org, pl.org_rs, pl.org_cs, pl.pred, pl.pred_rs, pl.pred_cs, d_poc, d_qp, od.split, od.lg, nullptr, nullptr, false, nullptr, od.dec);
     df.guard_pending[b] = false;
   }
   if (rc) return rc;
@@ -2498,7 +2568,7 @@ int deferred_guard_fixup(mlt_ctx *ctx, SizeState *st, Deferred &df, int b) {
   const Planes pl{(const int16_t *)di, (const int16_t *)(di + planes), size, (long)(df.plane / 2), size, (long)(df.plane / 2)};
   GuardSlot g;
   g.d_flat = od.flat; g.d_idx = od.idx; g.d_count = od.count; g.d_lg = od.lg; g.d_mag = od.mag; g.h_count = oh.count;
-  int rc = guard_fixup_async(ctx, *st, k, pl, d_poc, d_qp, od.split, od.lg, g);
+  int rc = guard_fixup_async(ctx, *st, k, pl, d_poc, d_qp, od.split, od.lg, g, od.dec);
   if (rc) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(ho, dout, deferred_fetch_bytes(nl), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2569,19 +2639,20 @@ int mlt_flush(mlt_ctx *ctx, int size) {
   return df.h_in ? deferred_launch(ctx, st, df) : MLT_OK;
 }
 
-int mlt_wait(mlt_ctx *ctx, int size, mlt_ticket ticket, int32_t *split_mode, float *logits_opt) {
+// mlt_wait / mlt_wait_decision (split_mode or dec may be NULL, not both)
+static int wait_impl(mlt_ctx *ctx, int size, mlt_ticket ticket, int32_t *split_mode, float *logits_opt, mlt_decision *dec) {
   if (!ctx) return MLT_ERR_ARG;
   if (!ctx->peers.empty()) {
     const int g = (int)(ticket >> 56);
     if (g > (int)ctx->peers.size()) { ctx->err = "unknown ticket"; return MLT_ERR_ARG; }
     if (g > 0) {
       mlt_ctx *p = device_of(ctx, g);
-      const int rc = mlt_wait(p, size, ticket & (((mlt_ticket)1 << 56) - 1), split_mode, logits_opt);
+      const int rc = wait_impl(p, size, ticket & (((mlt_ticket)1 << 56) - 1), split_mode, logits_opt, dec);
       if (rc) ctx->err = p->err;
       return rc;
     }
   }
-  if (!split_mode) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  if (!split_mode && !dec) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
   SizeState *st;
   int rc = check_size(ctx, size, &st);
   if (rc) return rc;
@@ -2595,8 +2666,49 @@ int mlt_wait(mlt_ctx *ctx, int size, mlt_ticket ticket, int32_t *split_mode, flo
   HIP_TRY(ctx, hipEventSynchronize(df.done[b]));
   if ((rc = deferred_guard_fixup(ctx, st, df, b))) return rc;
   const char *ho = df.h_out + (size_t)b * df.out_set;
-  *split_mode = ((const int32_t *)ho)[slot];
+  if (split_mode) *split_mode = ((const int32_t *)ho)[slot];
   if (logits_opt) std::memcpy(logits_opt, ho + (size_t)MLT_DEFER_CAP * 4 + (size_t)slot * nl * 4, (size_t)nl * 4);
+  if (dec) std::memcpy(dec, deferred_out(const_cast<char *>(ho), nl).dec + slot, sizeof(DecisionRec));
+  return MLT_OK;
+}
+
+int mlt_wait(mlt_ctx *ctx, int size, mlt_ticket ticket, int32_t *split_mode, float *logits_opt) {
+  if (ctx && !split_mode) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  return wait_impl(ctx, size, ticket, split_mode, logits_opt, nullptr);
+}
+
+int mlt_wait_decision(mlt_ctx *ctx, int size, mlt_ticket ticket, mlt_decision *out, float *logits_opt) {
+  if (ctx && !out) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  return wait_impl(ctx, size, ticket, nullptr, logits_opt, out);
+}
+
+int mlt_set_confidence_gate(mlt_ctx *ctx, int size, float min_confidence) {
+  if (!ctx) return MLT_ERR_ARG;
+  if (!(min_confidence >= 0.f && min_confidence < 1.f)) { ctx->err = "mlt_set_confidence_gate: threshold must be in [0, 1)"; return MLT_ERR_ARG; }   // (NaN fails the test)
+  SizeState *st;
+  int rc = check_size(ctx, size, &st);
+  if (rc) return rc;
+  for (mlt_ctx *p : ctx->peers)
+    if ((rc = mlt_set_confidence_gate(p, size, min_confidence))) { ctx->err = p->err; return rc; }
+  // mlt_predict's captured graphs bake the heads kernel's arguments in -- the threshold among them: dropped like after a reload, re-captured by the next call
+  if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  drop_graphs(ctx, size_index(size));
+  // deferred batches already launched keep the threshold they were launched with: their pending exact re-runs happen now, not at their first mlt_wait
+  Deferred &df = ctx->deferred[size_index(size)];
+  for (int b = 0; b < 2; ++b)
+    if (df.guard_pending[b] && (rc = deferred_guard_fixup(ctx, st, df, b))) return rc;
+  st->min_conf = min_confidence;
+  return MLT_OK;
+}
+
+int mlt_get_confidence_gate(mlt_ctx *ctx, int size, float *min_confidence) {
+  if (!ctx) return MLT_ERR_ARG;
+  if (!min_confidence) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  SizeState *st;
+  const int rc = check_size(ctx, size, &st);
+  if (rc) return rc;
+  *min_confidence = st->min_conf;
   return MLT_OK;
 }
 

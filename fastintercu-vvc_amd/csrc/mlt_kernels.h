@@ -179,6 +179,20 @@ bool mlt_chain_supported(int c, int h);
 hipError_t mlt_probe_lds_oob(int *d_ok, hipStream_t st);  // *d_ok = 1 iff DS reads beyond the LDS allocation return zeros on this device
 bool mlt_stage_supported(int c, int h);  // ... including the stage's stride-2 conv + shortcut (S2 variant)
 
+// Decision record of one CU (include/mltcnn.h: mlt_decision -- same 48 bytes; mlt_api.cpp asserts the layout).
+struct DecisionRec {
+  int32_t split_mode, raw_mode;
+  float confidence, margin;
+  int32_t level_mode[MLT_MAX_HEADS_K];
+  float level_conf[MLT_MAX_HEADS_K];
+};
+// Confidence gate guard: with the decision guard and a gate both on, a CU whose decision-head confidence lies within this fraction of the
+// tolerance of the gate's threshold is re-evaluated exactly, so that fp16 rounding never decides which side of the gate it falls on.  Two logits
+// within tol of the reference move a softmax probability by at most tol / 2: d p_top = p_top sum_j p_j (d l_top - d l_j), the differences move
+// by at most 2 tol, and sum_{j != top} p_top p_j = p_top (1 - p_top) <= 1/4.  The decision guard uses 3 x tol where 2 x is the bound (the
+// admission of the fast arithmetic is statistical); the same factor 1.5 on tol / 2 gives 0.75 tol.
+#define MLT_CONF_BAND_FRAC 0.75f
+
 struct HeadArgs {
   const float *gap[MLT_MAX_HEADS_K];  // GAP partial sums [n][slots][C] fp32 (written by the stage's last conv)
   int slots[MLT_MAX_HEADS_K];
@@ -188,7 +202,13 @@ struct HeadArgs {
   int n_heads, decision_head;
   const int32_t *poc, *qp;
   float *logits;   // [n][sum classes] or NULL
-  int32_t *split;  // [n]
+  int32_t *split;  // [n] (NULL: not wanted -- the record carries it)
+  // Decision records and the confidence gate (NULL / 0: not wanted, and then no softmax is computed).  dec[n] <- the record of CU n (every head's
+  // first-max argmax and its fp32 softmax probability; the decision head's margin).  min_conf > 0: split[n] (and dec[n].split_mode) = -1 unless the
+  // decision head's confidence >= min_conf (a NaN confidence gates).  g_conf_band > 0 (with the guard selection, g_margin > 0): the CU is also
+  // flagged when |confidence - min_conf| < g_conf_band (MLT_CONF_BAND_FRAC).
+  DecisionRec *dec;
+  float min_conf, g_conf_band;
   // Single-CU launches (n == 1, mlt_predict's captured graph): the guard selection rides on this kernel instead of a launch of its own
   // (guard_select_kernel: 5 us of a 160 us call).  g_count != NULL: g_count[0] = 1 and g_idx[0] = 0 when CU 0 is flagged by the
   // flat-content statistic (g_flat, thresholds as GuardSelectArgs) or by the decision-head margin (g_margin > 0), else g_count[0] = 0;
@@ -227,6 +247,7 @@ struct GuardSelectArgs {
   float margin;                // select when top1 - top2 of the decision head < margin (logits != NULL, margin > 0)
   const float *mag;            // [n] (HeadArgs.mag) or NULL: select when mag > mag_thr (round 6: the magnitude guard)
   float mag_thr;
+  float min_conf, conf_band;   // conf_band > 0 (with the margin test): select when |confidence - min_conf| < conf_band (HeadArgs.g_conf_band)
 };
 struct GuardGatherArgs {
   const int16_t *org, *pred;
@@ -239,9 +260,11 @@ struct GuardGatherArgs {
 struct GuardScatterArgs {
   const int32_t *idx, *g_split;
   const float *g_logits;
-  int32_t *split;              // [n]
+  int32_t *split;              // [n] or NULL
   float *logits;               // [n][n_logits] or NULL
   int k, n_logits;
+  const DecisionRec *g_dec;    // [k] records of the re-run, or NULL
+  DecisionRec *dec;            // [n] or NULL
 };
 hipError_t mlt_launch_flat_stat(const FlatStatArgs &a, bool aligned8, hipStream_t st);
 hipError_t mlt_launch_guard_select(const GuardSelectArgs &a, hipStream_t st);

@@ -5,9 +5,32 @@
 // logits_k = W_k . [feat (C floats), poc, qp] + b_k ; split = first maximal index (torch.argmax).
 // Every class of a head runs the identical operation sequence, so identical rows tie exactly.
 // ---------------------------------------------------------------------------------------------
+// Decision of one head from its K logits: first-max argmax (torch.argmax), top-1 minus top-2 logit (the decision guard's statistic, same comparisons), and the
+// softmax probability of the argmax -- fp32, max-subtracted, the full-precision expf, every class through the same operations and summed in class order, so tied
+// rows give tied probabilities (the argmax's own term is expf(0) = 1).  A NaN logit gives a NaN confidence.  Shared by heads_kernel and guard_select_kernel.
+__device__ __forceinline__ void head_decision(const float *l, int K, int &best, float &conf, float &margin) {
+  best = 0;
+  for (int k = 1; k < K; ++k)
+    if (l[k] > l[best]) best = k;
+  float t1 = -3.4e38f, t2 = -3.4e38f;
+  for (int c = 0; c < K; ++c) {
+    if (l[c] > t1) { t2 = t1; t1 = l[c]; } else if (l[c] > t2) t2 = l[c];
+  }
+  margin = t1 - t2;
+  const float mx = l[best];
+  float sum = 0.f;
+  for (int k = 0; k < K; ++k) sum += expf(l[k] - mx);
+  conf = 1.f / sum;
+}
+
+// DEC: the instantiation that also computes the decision records / applies the confidence gate (HeadArgs.dec != NULL or min_conf > 0: mlt_launch_heads picks it);
+// <false> is the kernel as it was before records existed -- launches that want neither run exactly that code.
+template <bool DEC>
 __global__ __launch_bounds__(256) void heads_kernel(const HeadArgs a) {
   __shared__ float feat[MLT_MAX_HEADS_K][256 + 2];
   __shared__ float lg[MLT_MAX_LOGITS_K];
+  __shared__ int hmode[MLT_MAX_HEADS_K];      // per head: argmax, its softmax probability, top-2 margin (only when records or the gate are wanted)
+  __shared__ float hconf[MLT_MAX_HEADS_K], hmarg[MLT_MAX_HEADS_K];
   __shared__ float lgm[MLT_MAX_LOGITS_K];   // sum_k |w_ck feat_k| per logit (the magnitude guard's statistic)
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float fpoc = (float)a.poc[n], fqp = (float)a.qp[n];  // EncCu.cpp:881-882 (int -> float, exact)
@@ -50,13 +73,39 @@ __global__ __launch_bounds__(256) void heads_kernel(const HeadArgs a) {
   }
   __syncthreads();
   if (tid < lo && a.logits) a.logits[(size_t)n * lo + tid] = lg[tid];
+  if constexpr (DEC) {   // one thread per head
+    if (tid < a.n_heads) {
+      int o = 0;
+      for (int hd = 0; hd < tid; ++hd) o += a.classes[hd];
+      int bm; float cf, mg;
+      head_decision(lg + o, a.classes[tid], bm, cf, mg);
+      hmode[tid] = bm; hconf[tid] = cf; hmarg[tid] = mg;
+    }
+    __syncthreads();
+  }
   if (tid == 0) {
     int off = 0;
     for (int hd = 0; hd < a.decision_head; ++hd) off += a.classes[hd];
     int best = 0;
     for (int k = 1; k < a.classes[a.decision_head]; ++k)
       if (lg[off + k] > lg[off + best]) best = k;
-    a.split[n] = best;
+    int out = best;
+    float conf = 0.f;
+    if constexpr (DEC) {
+      conf = hconf[a.decision_head];
+      if (a.min_conf > 0.f) out = conf >= a.min_conf ? best : -1;   // (a NaN confidence gates)
+      if (a.dec) {
+        DecisionRec r;
+        r.split_mode = out; r.raw_mode = best; r.confidence = conf; r.margin = hmarg[a.decision_head];
+#pragma unroll
+        for (int hd = 0; hd < MLT_MAX_HEADS_K; ++hd) {
+          r.level_mode[hd] = hd < a.n_heads ? hmode[hd] : -1;
+          r.level_conf[hd] = hd < a.n_heads ? hconf[hd] : 0.f;
+        }
+        a.dec[n] = r;
+      }
+    }
+    if (!DEC || a.split) a.split[n] = out;   // (only a launch that writes records may come without a split buffer)
     float mag = 0.f;
     if (a.mag || a.g_mag_thr > 0.f) {
       for (int k = 0; k < lo; ++k) mag = !(lgm[k] <= mag) ? lgm[k] : mag;   // (a NaN sticks)
@@ -75,6 +124,7 @@ __global__ __launch_bounds__(256) void heads_kernel(const HeadArgs a) {
           if (lg[off + c] > t1) { t2 = t1; t1 = lg[off + c]; } else if (lg[off + c] > t2) t2 = lg[off + c];
         }
         s = s || !(t1 - t2 >= a.g_margin);
+        if (DEC && a.g_conf_band > 0.f) s = s || !(fabsf(conf - a.min_conf) >= a.g_conf_band);   // the gate guard (mlt_kernels.h: MLT_CONF_BAND_FRAC); also catches NaN
       }
       if (a.g_mag_thr > 0.f) s = s || !(mag <= a.g_mag_thr);
       if (a.g_next) {   // unordered append to a count that was zero on entry; workgroup 0 re-arms the slot's other counter for the next launch
@@ -141,6 +191,11 @@ __global__ __launch_bounds__(1024) void guard_select_kernel(const GuardSelectArg
         if (l[c] > t1) { t2 = t1; t1 = l[c]; } else if (l[c] > t2) t2 = l[c];
       }
       s = s || !(t1 - t2 >= a.margin);  // also catches NaN
+      if (a.conf_band > 0.f) {   // the gate guard, on the confidence heads_kernel computed from these logits (same function, same operations)
+        int bm; float cf, mg;
+        head_decision(l, a.head_classes, bm, cf, mg);
+        s = s || !(fabsf(cf - a.min_conf) >= a.conf_band);
+      }
     }
     if (a.mag && a.mag_thr > 0.f) s = s || !(a.mag[i] <= a.mag_thr);
     return s;
@@ -176,7 +231,9 @@ __global__ __launch_bounds__(256) void guard_scatter_kernel(const GuardScatterAr
   const int t = blockIdx.x * 256 + threadIdx.x, j = t / (a.n_logits + 1), e = t - j * (a.n_logits + 1);
   if (j >= a.k) return;
   const int dst = a.idx[j];
-  if (e == a.n_logits) a.split[dst] = a.g_split[j];
-  else if (a.logits) a.logits[(size_t)dst * a.n_logits + e] = a.g_logits[(size_t)j * a.n_logits + e];
+  if (e == a.n_logits) {
+    if (a.split) a.split[dst] = a.g_split[j];
+    if (a.dec) a.dec[dst] = a.g_dec[j];
+  } else if (a.logits) a.logits[(size_t)dst * a.n_logits + e] = a.g_logits[(size_t)j * a.n_logits + e];
 }
 

@@ -19,6 +19,12 @@
 // flush / wait, calls per CU size, seconds inside mlt_init (weights + calibration) -- the "share of an encode spent inside the predictor" figure
 // tools/eval_harness.py reads (N4).
 //
+// MLTCNN_MIN_CONF (any build, read next to MLTCNN_STATS): the library's CONFIDENCE GATE (mlt_set_confidence_gate) -- either one number for every enabled
+// size ("0.9") or per size ("128:0.9,64:0.8").  A CU whose decision-head softmax probability stays below the threshold comes back as -1 from
+// predictSplitMode() / waitSplitMode(): "no prediction", EncModeCtrl::setNewModeList is a no-op and the encoder runs its exhaustive RDO for that CU.
+// A gated call is NOT a failure: no "error" line, not counted in failed=; under MLTCNN_STATS=1 the stats line ends with gated=<count> when a gate
+// is set.  Malformed value: a message on stderr, the gate stays off.  predictDecision() / waitDecision() return the whole decision record.
+//
 // Test hooks, compiled in only with -DMLTCNN_TEST_HOOKS (tools/build_vtm.sh does; a production build carries none of them):
 //   MLTCNN_FAULT_INJECT=1      the predictor reports ok() without touching a device and every predictSplitMode() fails (-1):
 //                              exercises the reference's swallow-and-continue contract from the real call site on a box without a GPU
@@ -82,12 +88,18 @@ class SplitPredictor {
       std::fprintf(stderr, "  mltcnn: %s\n", mlt_last_error(nullptr));
       m_ctx = nullptr;
     }
+    if (m_ctx)
+      if (const char *g = std::getenv("MLTCNN_MIN_CONF")) applyMinConf(g);
   }
   ~SplitPredictor() {
-    if (m_stats)
-      std::fprintf(stderr, "mltcnn-stats predict_calls=%llu predict_s=%.6f submit_calls=%llu submit_s=%.6f wait_calls=%llu wait_s=%.6f flush_calls=%llu flush_s=%.6f "
-                           "calls_128=%llu calls_64=%llu calls_32=%llu calls_16=%llu failed=%llu init_s=%.6f\n",
-                   m_n[0], m_t[0], m_n[1], m_t[1], m_n[2], m_t[2], m_n[3], m_t[3], m_bySize[0], m_bySize[1], m_bySize[2], m_bySize[3], m_failed, m_initSeconds);
+    if (m_stats) {   // (one fprintf for the whole line: predictors of several EncCu threads share stderr)
+      char line[768];
+      int k = std::snprintf(line, sizeof line, "mltcnn-stats predict_calls=%llu predict_s=%.6f submit_calls=%llu submit_s=%.6f wait_calls=%llu wait_s=%.6f flush_calls=%llu flush_s=%.6f "
+                            "calls_128=%llu calls_64=%llu calls_32=%llu calls_16=%llu failed=%llu init_s=%.6f",
+                            m_n[0], m_t[0], m_n[1], m_t[1], m_n[2], m_t[2], m_n[3], m_t[3], m_bySize[0], m_bySize[1], m_bySize[2], m_bySize[3], m_failed, m_initSeconds);
+      if (m_gateSet && k > 0 && k < (int)sizeof line) std::snprintf(line + k, sizeof line - (size_t)k, " gated=%llu", m_gated);
+      std::fprintf(stderr, "%s\n", line);
+    }
     mlt_shutdown(m_ctx);
   }
   SplitPredictor(const SplitPredictor &) = delete;
@@ -116,7 +128,7 @@ class SplitPredictor {
       std::fprintf(stderr, "error\n");  // EncCu.cpp:925
       split = -1;
       ++m_failed;
-    }
+    } else if (split < 0) ++m_gated;   // withheld by the confidence gate: not a failure
     if (logitsOpt) for (int i = 0; i < mlt_num_logits(cuw); ++i) logitsOpt[i] = lg[i];
     if (!m_dumpPath.empty()) dumpCall(org, orgStride, pred, predStride, cuw, poc, cuQP, split, lg);
     return split;
@@ -138,10 +150,82 @@ class SplitPredictor {
     Timer tm(this, 2, 0);
     if (m_faultInject && m_forceSplit >= 0) return m_forceSplit;
     if (!m_ctx || mlt_wait(m_ctx, cuw, ticket, &split, logitsOpt) != MLT_OK) return -1;
+    if (split < 0) ++m_gated;
     return split;
   }
 
+  // The whole decision record (include/mltcnn.h: mlt_decision -- every level's argmax and confidence, the gated and the raw split mode) for callers that want
+  // more than the one integer.  false on failure (out->split_mode = -1: treat like predictedSplitMode = -1).
+  bool predictDecision(const Pel *org, int orgStride, const Pel *pred, int predStride, int cuw, int poc, int cuQP, mlt_decision *out, float *logitsOpt = nullptr) {
+    Timer tm(this, 0, cuw);
+    *out = mlt_decision{};
+    out->split_mode = out->raw_mode = -1;
+    if (!m_ctx || mlt_predict_decision(m_ctx, org, orgStride, pred, predStride, cuw, poc, cuQP, out, logitsOpt) != MLT_OK) {
+      std::fprintf(stderr, "error\n");  // EncCu.cpp:925
+      out->split_mode = -1;
+      ++m_failed;
+      return false;
+    }
+    if (out->split_mode < 0) ++m_gated;
+    return true;
+  }
+  bool waitDecision(int cuw, mlt_ticket ticket, mlt_decision *out, float *logitsOpt = nullptr) {
+    Timer tm(this, 2, 0);
+    *out = mlt_decision{};
+    out->split_mode = out->raw_mode = -1;
+    if (!m_ctx || mlt_wait_decision(m_ctx, cuw, ticket, out, logitsOpt) != MLT_OK) { out->split_mode = -1; return false; }
+    if (out->split_mode < 0) ++m_gated;
+    return true;
+  }
+
+  // MLTCNN_MIN_CONF's value -> thresholds for {128, 64, 32, 16}: "v" (every size) or "S:v,S:v,..." (sizes not named: 0 = off), each 0 <= v < 1.
+  // Pure host logic; false (thr all zero) for anything malformed -- the gate then stays off.
+  static bool parseMinConf(const char *spec, float thr[4]) {
+    static const int sizes[4] = {128, 64, 32, 16};
+    for (int i = 0; i < 4; ++i) thr[i] = 0.f;
+    bool ok = spec && *spec != 0;
+    if (ok && !std::strchr(spec, ':')) {
+      char *end = nullptr;
+      const float v = std::strtof(spec, &end);
+      ok = end != spec && *end == 0 && v >= 0.f && v < 1.f;
+      for (int i = 0; i < 4 && ok; ++i) thr[i] = v;
+    } else if (ok) {
+      const char *p = spec;
+      while (ok && *p) {
+        char *end = nullptr;
+        const long sz = std::strtol(p, &end, 10);
+        int si = -1;
+        for (int i = 0; i < 4; ++i) if (sz == sizes[i]) si = i;
+        ok = end != p && *end == ':' && si >= 0;
+        if (!ok) break;
+        p = end + 1;
+        const float v = std::strtof(p, &end);
+        ok = end != p && (*end == ',' || *end == 0) && v >= 0.f && v < 1.f;
+        if (!ok) break;
+        thr[si] = v;
+        p = *end ? end + 1 : end;
+        if (*end == ',' && !*p) ok = false;   // trailing comma
+      }
+    }
+    if (!ok) for (int i = 0; i < 4; ++i) thr[i] = 0.f;
+    return ok;
+  }
+
  private:
+  void applyMinConf(const char *spec) {
+    static const int sizes[4] = {128, 64, 32, 16};
+    float thr[4];
+    if (!parseMinConf(spec, thr)) {
+      std::fprintf(stderr, "mltcnn: MLTCNN_MIN_CONF=\"%s\" is malformed (want 0 <= v < 1, \"v\" or \"128:v,64:v,...\"): confidence gate off\n", spec);
+      return;
+    }
+    for (int i = 0; i < 4; ++i) {
+      if (!(m_mask & (1u << i)) || thr[i] <= 0.f) continue;
+      if (mlt_set_confidence_gate(m_ctx, sizes[i], thr[i]) == MLT_OK) m_gateSet = true;
+      else std::fprintf(stderr, "mltcnn: confidence gate for size %d not set: %s\n", sizes[i], mlt_last_error(m_ctx));
+    }
+  }
+
   // one record per call: int32 {magic 0x4D4C5443, cuw, poc, qp, split, nLogits}, float logits[MLT_MAX_LOGITS], int16 org[cuw*cuw], int16 pred[cuw*cuw]
   // -- built in a buffer and written with ONE write(2) on an O_APPEND descriptor (atomic with respect to other appenders: predictors
   // of several EncCu threads share one dump file); a failed write is reported once.
@@ -179,6 +263,8 @@ class SplitPredictor {
   bool m_stats = false;
   unsigned long long m_n[4] = {0, 0, 0, 0}, m_bySize[4] = {0, 0, 0, 0}, m_failed = 0;
   double m_t[4] = {0, 0, 0, 0};
+  unsigned long long m_gated = 0;   // calls the confidence gate withheld (split -1 from a call that succeeded)
+  bool m_gateSet = false;           // MLTCNN_MIN_CONF set a gate on at least one size
   double m_initSeconds = 0.0;   // wall-clock of mlt_init (weights + load-time calibration): what an encoder process pays once
 
   mlt_ctx *m_ctx = nullptr;

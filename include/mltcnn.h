@@ -234,6 +234,43 @@ int mlt_submit(mlt_ctx *ctx, const int16_t *org, int org_stride, const int16_t *
 int mlt_flush(mlt_ctx *ctx, int size);
 int mlt_wait(mlt_ctx *ctx, int size, mlt_ticket ticket, int32_t *split_mode, float *logits_opt);
 
+/* ---- Per-level decisions with confidence, and a confidence gate on the split (new exports; MLT_ABI_VERSION stays 4) ----
+ * The network is a multi-level tree (three heads for the 128 model: 2 / 3 / 4 classes; four for the CU models: 2 / 3 / 4 / 6).  The decision record
+ * carries, per CU, every head's argmax and how sure the network is of it, computed on the device from the logits the call returns: softmax in fp32 on
+ * the max-subtracted logits with the full-precision expf, every class through the same operations (tied rows give tied probabilities).
+ * mlt_config.head_index[] keeps its meaning: it selects the DECISION head, whose fields fill split_mode / raw_mode / confidence / margin. */
+typedef struct mlt_decision {   /* 48 bytes, little-endian, no padding */
+  int32_t split_mode;     /* what the encoder consumes: raw_mode, or -1 when the gate withholds it */
+  int32_t raw_mode;       /* argmax of the decision head (first maximal index), gate ignored */
+  float   confidence;     /* softmax probability of raw_mode within the decision head */
+  float   margin;         /* top-1 minus top-2 logit of the decision head */
+  int32_t level_mode[4];  /* argmax of every head, lvl1..lvl4 (first-max rule); -1 for a head the model lacks */
+  float   level_conf[4];  /* its softmax probability; 0 for a head the model lacks */
+} mlt_decision;
+
+/* Confidence gate of one CU size: split_mode = confidence >= min_confidence ? raw_mode : -1 (a NaN confidence gates), applied ON THE DEVICE to the
+ * split output of EVERY entry point, old and new -- -1 is what EncModeCtrl::setNewModeList treats as "no prediction" (exhaustive RDO), so an
+ * integrator trades encode-time saving against BD-rate with this one number.  0 <= min_confidence < 1; 0 = off (the default: every call returns what
+ * it returned without the gate, from the same launches).  NaN, negative or >= 1 -> MLT_ERR_ARG; size not loaded -> MLT_ERR_SIZE_DISABLED.  Addresses
+ * every device of a multi-device context, takes effect for batches launched after it returns, and invalidates captured graphs the way a weight reload
+ * does.  Not a property of the weights: mlt_load_weights of that size and mlt_calibrate keep it.
+ * Gate guard: on sizes that run a non-exact tier with the decision guard on, a CU whose confidence lies within 0.75 x tolerance of the threshold is
+ * re-evaluated with the exact arithmetic like a near-tie (two logits within `tolerance` of the reference move a softmax probability by at most
+ * tolerance / 2; the factor 1.5 on top is the decision guard's), so fp16 rounding does not decide which side of the gate a CU falls on. */
+int mlt_set_confidence_gate(mlt_ctx *ctx, int size, float min_confidence);
+int mlt_get_confidence_gate(mlt_ctx *ctx, int size, float *min_confidence);
+
+/* The decision-record twins of mlt_predict / mlt_predict_batch / mlt_predict_batch_device / mlt_wait: same arguments, same implementation (chunking,
+ * staging pipeline, guards, sharding over devices[], deferred slots), a record per CU in place of the split mode; the logits they return are
+ * bit-identical to their twins', and with the gate off raw_mode == split_mode == the twin's split.  d_decisions: n x 48 bytes of DEVICE memory. */
+int mlt_predict_decision(mlt_ctx *ctx, const int16_t *org, int org_stride, const int16_t *pred, int pred_stride,
+                         int size, int32_t poc, int32_t qp, mlt_decision *out, float *logits_opt);
+int mlt_predict_batch_decisions(mlt_ctx *ctx, int n, int size, const int16_t *org, const int16_t *pred,
+                                const int32_t *poc, const int32_t *qp, mlt_decision *out, float *logits);
+int mlt_predict_batch_device_decisions(mlt_ctx *ctx, int n, int size, const void *d_org, const void *d_pred,
+                                       const void *d_poc, const void *d_qp, void *d_decisions, void *d_logits);
+int mlt_wait_decision(mlt_ctx *ctx, int size, mlt_ticket ticket, mlt_decision *out, float *logits_opt);
+
 int mlt_synchronize(mlt_ctx *ctx);
 
 /* Use an existing hipStream_t (e.g. the caller's) instead of the context's own stream; NULL switches back to a
