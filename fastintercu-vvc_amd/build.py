@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmltcnn_hip.so")
 ABI_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "mltcnn.h"))
-SOURCES = ["mlt_kernels.hip", "mlt_model.cpp", "mlt_api.cpp"]
+SOURCES = ["mlt_kernels.hip", "mlt_model.cpp", "mlt_dispatch.cpp", "mlt_guards.cpp", "mlt_calibrate.cpp", "mlt_api.cpp"]
 SOURCE_EXTS = (".hip", ".inc", ".cpp", ".h")
 SIG_MARKER = b"MLTCNN_SOURCE_SIG="
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden",
@@ -87,7 +87,7 @@ def _unit_key(src: str, defines) -> str:
 def build_lib(force: bool = False, verbose: bool = False, defines=(), out: str | None = None) -> str:
     """Cross-compiles without a GPU (hipcc only needs the gfx950 target).  One object per translation unit, cached under _build/ by the hash of
     everything the unit includes (an edit to the host runtime does not recompile the kernels: 85 s -> 12 s); the source signature is a
-    define of mlt_api.cpp alone.
+    define of mlt_api.cpp alone (the unit that holds the marker string).
     `defines` / `out`: tuning variants (scripts/sweep_cfg.py); the product is always LIB with no defines."""
     target = out or LIB
     if force or out or stale():

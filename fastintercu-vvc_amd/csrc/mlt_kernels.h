@@ -1,4 +1,4 @@
-// mlt_kernels.h -- launch interface between the host runtime (mlt_api.cpp) and mlt_kernels.hip.
+// mlt_kernels.h -- launch interface between the host runtime (mlt_runtime.h and its translation units) and mlt_kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -179,7 +179,7 @@ bool mlt_chain_supported(int c, int h);
 hipError_t mlt_probe_lds_oob(int *d_ok, hipStream_t st);  // *d_ok = 1 iff DS reads beyond the LDS allocation return zeros on this device
 bool mlt_stage_supported(int c, int h);  // ... including the stage's stride-2 conv + shortcut (S2 variant)
 
-// Decision record of one CU (include/mltcnn.h: mlt_decision -- same 48 bytes; mlt_api.cpp asserts the layout).
+// Decision record of one CU (include/mltcnn.h: mlt_decision -- same 48 bytes; mlt_runtime.h asserts the layout).
 struct DecisionRec {
   int32_t split_mode, raw_mode;
   float confidence, margin;
@@ -216,7 +216,7 @@ struct HeadArgs {
   int32_t *g_count, *g_idx, *g_flat;
   int g_flat_thr, g_near_thr;
   float g_margin;
-  // Round 6, the MAGNITUDE guard (mlt_api.cpp: SizeState.mag_thr): mag[n] <- max over all logits of sum_k |w_ck feat_k| -- the size of the
+  // Round 6, the MAGNITUDE guard (mlt_runtime.h: SizeState.mag_thr): mag[n] <- max over all logits of sum_k |w_ck feat_k| -- the size of the
   // feature-driven part of the logits, which is what the fp16 pipeline's RELATIVE error acts on (poc, qp and the bias enter exactly).  NULL: not
   // wanted.  g_mag_thr > 0 (single-CU launches): CU 0 is also flagged when its magnitude exceeds the threshold (NaN included).
   float *mag;

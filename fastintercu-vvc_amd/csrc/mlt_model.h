@@ -73,7 +73,7 @@ enum { MLT_MODEL_FAST = 0, MLT_MODEL_EXACT = 1, MLT_MODEL_W2 = 2, MLT_MODEL_XLIT
 // reset per (cout, cin) pair (rounds 1-3); 1: raster, error carried across cin; 2: reversed taps; 3: column-major taps; 4: spiral from the
 // centre; 5: serpentine, carried across cin.  Every one keeps each weight within one ulp and cancels the rounding error along spatially
 // adjacent taps; they differ by which weights take which error, i.e. they are different draws of the same error distribution, and the
-// load-time calibration may pick the draw that suits a weight set (mlt_api.cpp).
+// load-time calibration may pick the draw that suits a weight set (mlt_calibrate.cpp).
 enum { MLT_N_ROUNDINGS = 6 };
 bool build_model(const void *blob, size_t bytes, int mode, int size, Model &m, std::string &err, int rounding = 0);  // size: CU size the model will serve
 uint16_t f32_to_f16(float f);

@@ -19,7 +19,7 @@ struct TierPrice {
   float rms = 0.f;   // worst rms pooled per content class / per head
   float max = 0.f;   // largest |dlogit| over the calibration logits
   float tail = 0.f;  // max / (rms pooled over everything)
-  // Round 6 -- the same configuration behind the MAGNITUDE guard (mlt_api.cpp, "magnitude guard"): the pricer fills these when the plain
+  // Round 6 -- the same configuration behind the MAGNITUDE guard (mlt_calibrate.cpp, "magnitude guard"): the pricer fills these when the plain
   // figures above miss the contract and it has such a guard.  g_thr = the largest logit magnitude (quarter-octave grid) up to which the
   // calibration CUs meet the REFINED rule; CUs above it are re-evaluated exactly at run time, so g_rms / g_max / g_tail are the figures over
   // the CUs at or below it -- the synthetic set's, the caller's, and a further in-distribution set (texture + 1/f scenes) that restores the
@@ -56,7 +56,7 @@ struct TierRules {
   float score(const TierPrice &p) const { return std::max(k(p) * p.rms / tolerance, p.max / (max_frac * tolerance)); }
 };
 
-// tuning switches (MLT_TUNING=1 environment, mlt_api.cpp): -1 / false = not forced
+// tuning switches (MLT_TUNING=1 environment, mlt_calibrate.cpp: load_one): -1 / false = not forced
 struct TierForce {
   int rounding = -1;       // MLT_ROUNDING: price exactly this realisation and keep it
   int w2_mask = -1;        // MLT_W2_MASK: exactly this STAGE mask in hi+lo weights, kept whatever it measures
@@ -235,7 +235,7 @@ inline int search_tier_128(TierPricer &pr, const TierRules &R, const TierForce &
 }
 
 // The 64 / 32 / 16 models: configured exact; the calibration may keep a PREFIX of stages -- or one launch unit of layer0 -- off the exact
-// arithmetic (their time is in the first stages, their error in the last ones).  R.max_frac = 0.5 here (mlt_api.cpp).
+// arithmetic (their time is in the first stages, their error in the last ones).  R.max_frac = 0.5 here (mlt_calibrate.cpp).
 inline int search_tier_small(TierPricer &pr, const TierRules &R, const TierForce &F, int n_stages, TierChoice &out) {
   out = TierChoice();
   int rc;

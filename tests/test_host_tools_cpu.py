@@ -92,9 +92,10 @@ int main(int argc, char **argv) {
 def test_traffic_json_names_are_the_profile_names_of_the_runtime():
     """scripts/make_traffic_json.py keys the PMC traffic by the launch names the runtime profiles under (bench.py looks `name@batch` up); a name the
     runtime truncates (mlt_profile_entry.name holds 47 characters) or renames silently turns `roofline.traffic` into null.  Every fused-launch name
-    the script emits must be what mlt_api.cpp passes to prof_begin, cut to 47 characters."""
+    the script emits must be what the runtime (the translation units of csrc/) passes to prof_begin, cut to 47 characters."""
     import re
-    src = open(os.path.join(ROOT, "fastintercu-vvc_amd", "csrc", "mlt_api.cpp")).read()
+    import glob
+    src = "".join(open(p).read() for p in sorted(glob.glob(os.path.join(ROOT, "fastintercu-vvc_amd", "csrc", "*.cpp"))))
     runtime = {m[:47] for m in re.findall(r'prof_begin\("([^"]+)"', src)}
     script = open(os.path.join(ROOT, "scripts", "make_traffic_json.py")).read()
     emitted = set(re.findall(r'(?:name = |else )"([^"]+)"(\[:47\])?', script))

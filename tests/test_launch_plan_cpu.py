@@ -1,4 +1,4 @@
-"""CPU: the dispatcher's LAUNCH PLANS.  run_network (csrc/mlt_api.cpp) decides, per batch, which kernels serve which launch units --
+"""CPU: the dispatcher's LAUNCH PLANS.  run_network (csrc/mlt_dispatch.cpp) decides, per batch, which kernels serve which launch units --
 tier x batch class x alignment x which neighbour is a whole-stage kernel (layouts between them) -- and round 5 left that decision observable only on a
 GPU.  The library's plan mode (mlt_ctx::plan) runs the same code with every launch RECORDED instead of enqueued; mlt_plan_describe (host-only hook, no
 device) returns the list.  Pinned here: the launches of the shipped tiers at the batch classes the encoder and the bench use, and the layout hand-offs

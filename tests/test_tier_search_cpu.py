@@ -1,7 +1,7 @@
 """CPU: the tier search of the load-time calibration (fastintercu-vvc_amd/csrc/mlt_tier_search.h) over a STUB pricer, through the
 mlt_tier_search_run hook of libmltcnn_hip.so (ctypes callback; no HIP call on that path): order of the candidates, the refinement
 rule, the one illegal launch-unit pair, forced masks, the small models' prefixes, error propagation.  The device-side pricer
-(mlt_api.cpp: DevicePricer) only measures; everything decided at load time is decided by the code under test here."""
+(mlt_calibrate.cpp: DevicePricer) only measures; everything decided at load time is decided by the code under test here."""
 import ctypes as C
 
 import pytest
