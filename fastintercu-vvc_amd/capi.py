@@ -29,7 +29,9 @@ EXPORTS = ["mlt_abi_version", "mlt_build_signature", "mlt_init", "mlt_num_device
            "mlt_predict_batch_device", "mlt_submit", "mlt_flush", "mlt_wait", "mlt_synchronize", "mlt_set_stream", "mlt_alloc_pinned", "mlt_free_pinned",
            "mlt_num_logits", "mlt_profile_enable", "mlt_profile_read", "mlt_last_error", "mlt_shutdown",
            "mlt_set_confidence_gate", "mlt_get_confidence_gate", "mlt_predict_decision", "mlt_predict_batch_decisions", "mlt_predict_batch_device_decisions",
-           "mlt_wait_decision"]
+           "mlt_wait_decision",
+           "mlt_set_candidate_policy", "mlt_get_candidate_policy", "mlt_predict_candidates", "mlt_predict_batch_candidates",
+           "mlt_predict_batch_device_candidates", "mlt_wait_candidates"]
 
 
 class MltConfig(C.Structure):
@@ -56,6 +58,14 @@ class MltDecision(C.Structure):
 # the same layout as a numpy structured dtype (what the batch calls return and decisions.from_logits builds)
 DECISION_DTYPE = np.dtype([("split_mode", "<i4"), ("raw_mode", "<i4"), ("confidence", "<f4"), ("margin", "<f4"),
                            ("level_mode", "<i4", (4,)), ("level_conf", "<f4", (4,))])
+
+
+class MltCandidates(C.Structure):
+    """`struct mlt_candidates` (include/mltcnn.h): 40 bytes, no padding."""
+    _fields_ = [("mask", C.c_uint32), ("count", C.c_int32), ("order", C.c_int8 * 8), ("prob", C.c_float * 6)]
+
+
+CANDIDATES_DTYPE = np.dtype([("mask", "<u4"), ("count", "<i4"), ("order", "i1", (8,)), ("prob", "<f4", (6,))])
 
 
 class MltKernelTime(C.Structure):
@@ -116,6 +126,12 @@ def load_library():
     lib.mlt_predict_batch_decisions.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.mlt_predict_batch_device_decisions.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.mlt_wait_decision.argtypes = [vp, i32, C.c_uint64, C.POINTER(MltDecision), vp]
+    lib.mlt_set_candidate_policy.argtypes = [vp, i32, C.c_float, i32]
+    lib.mlt_get_candidate_policy.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(i32)]
+    lib.mlt_predict_candidates.argtypes = [vp, vp, i32, vp, i32, i32, C.c_int32, C.c_int32, C.POINTER(MltCandidates), C.POINTER(MltDecision), vp]
+    lib.mlt_predict_batch_candidates.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.mlt_predict_batch_device_candidates.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.mlt_wait_candidates.argtypes = [vp, i32, C.c_uint64, C.POINTER(MltCandidates), C.POINTER(MltDecision), vp]
     lib.mlt_synchronize.argtypes = [vp]
     lib.mlt_set_stream.argtypes = [vp, vp]
     lib.mlt_alloc_pinned.restype = vp
@@ -260,9 +276,15 @@ class MltCnn:
         return int(split.value), logits
 
     def predict_batch_device(self, n: int, size: int, d_org: int, d_pred: int, d_poc: int, d_qp: int, d_split: int | None,
-                             d_logits: int | None, d_decisions: int | None = None):
+                             d_logits: int | None, d_decisions: int | None = None, d_candidates: int | None = None):
         """Raw device pointers (e.g. torch tensor .data_ptr()); asynchronous on the context's stream.
-        d_decisions: n x 48 bytes of device memory -> the decision records instead of the split modes (mlt_predict_batch_device_decisions)."""
+        d_decisions: n x 48 bytes of device memory -> the decision records instead of the split modes (mlt_predict_batch_device_decisions).
+        d_candidates: n x 40 bytes of device memory -> the candidate records, with the decision records beside them when d_decisions is given too
+        (mlt_predict_batch_device_candidates)."""
+        if d_candidates is not None:
+            assert d_split is None, "one call fills either the split modes or the records"
+            self._check(self._lib.mlt_predict_batch_device_candidates(self._h, n, size, d_org, d_pred, d_poc, d_qp, d_candidates, d_decisions, d_logits))
+            return
         if d_decisions is not None:
             assert d_split is None, "one call fills either the split modes or the decision records"
             self._check(self._lib.mlt_predict_batch_device_decisions(self._h, n, size, d_org, d_pred, d_poc, d_qp, d_decisions, d_logits))
@@ -317,6 +339,57 @@ class MltCnn:
         logits = np.zeros(self.num_logits(size) or 1, np.float32)
         self._check(self._lib.mlt_wait_decision(self._h, size, C.c_uint64(ticket), C.byref(d), logits.ctypes.data))
         return self._record(d), logits
+
+    # -- candidate split sets ----------------------------------------------------------------------
+    def set_candidate_policy(self, size: int, coverage: float, max_modes: int = 0):
+        """The candidate record keeps the shortest rank prefix of the decision head that carries `coverage` of the softmax probability, every class when
+        that takes more than max_modes > 0 classes ((0, 0) = the argmax alone, the default); every entry point, every device."""
+        self._check(self._lib.mlt_set_candidate_policy(self._h, size, float(coverage), int(max_modes)))
+
+    def candidate_policy(self, size: int, device_index: int = 0):
+        h = self._lib.mlt_device_ctx(self._h, device_index)
+        if not h:
+            raise MltError(1, "no such device index")
+        cov, mx = C.c_float(-1.0), C.c_int(-1)
+        rc = self._lib.mlt_get_candidate_policy(h, size, C.byref(cov), C.byref(mx))
+        if rc != MLT_OK:
+            raise MltError(rc, self._lib.mlt_last_error(h).decode())
+        return float(cov.value), int(mx.value)
+
+    @staticmethod
+    def _candidates(c: MltCandidates) -> np.ndarray:
+        return np.frombuffer(bytes(c), CANDIDATES_DTYPE)[0].copy()
+
+    def predict_candidates(self, org: np.ndarray, pred: np.ndarray, poc: int, qp: int):
+        """`predict` returning the CU's candidate record (a CANDIDATES_DTYPE scalar), its decision record and the logits."""
+        assert org.dtype == np.int16 and pred.dtype == np.int16 and org.ndim == 2 and org.shape == pred.shape
+        S = org.shape[0]
+        assert org.shape[1] == S and org.strides[1] == 2 and pred.strides[1] == 2
+        c, d = MltCandidates(), MltDecision(-1, -1)
+        logits = np.zeros(self.num_logits(S) or 1, np.float32)
+        self._check(self._lib.mlt_predict_candidates(self._h, org.ctypes.data, org.strides[0] // 2, pred.ctypes.data,
+                                                     pred.strides[0] // 2, S, int(poc), int(qp), C.byref(c), C.byref(d), logits.ctypes.data))
+        return self._candidates(c), self._record(d), logits
+
+    def predict_batch_candidates(self, org: np.ndarray, pred: np.ndarray, poc, qp, want_logits: bool = True, want_decisions: bool = True):
+        org = np.ascontiguousarray(org, np.int16)
+        pred = np.ascontiguousarray(pred, np.int16)
+        n, S, _ = org.shape
+        poc = np.ascontiguousarray(poc, np.int32)
+        qp = np.ascontiguousarray(qp, np.int32)
+        cand = np.zeros((n,), CANDIDATES_DTYPE)
+        dec = np.zeros((n,), DECISION_DTYPE) if want_decisions else None
+        logits = np.zeros((n, self.num_logits(S) or 1), np.float32) if want_logits else None
+        self._check(self._lib.mlt_predict_batch_candidates(self._h, n, S, org.ctypes.data, pred.ctypes.data, poc.ctypes.data, qp.ctypes.data,
+                                                           cand.ctypes.data, dec.ctypes.data if want_decisions else None,
+                                                           logits.ctypes.data if want_logits else None))
+        return cand, dec, logits
+
+    def wait_candidates(self, size: int, ticket: int):
+        c, d = MltCandidates(), MltDecision(-1, -1)
+        logits = np.zeros(self.num_logits(size) or 1, np.float32)
+        self._check(self._lib.mlt_wait_candidates(self._h, size, C.c_uint64(ticket), C.byref(c), C.byref(d), logits.ctypes.data))
+        return self._candidates(c), self._record(d), logits
 
     def synchronize(self):
         self._check(self._lib.mlt_synchronize(self._h))

@@ -235,14 +235,15 @@ int mlt_synchronize(mlt_ctx *ctx) {
   return MLT_OK;
 }
 
-// mlt_predict_batch_device / mlt_predict_batch_device_decisions: one of d_split_mode / d_dec may be NULL
+// mlt_predict_batch_device / _decisions / _candidates: at least one of d_split_mode / d_dec / d_cand
 static int predict_batch_device_impl(mlt_ctx *ctx, int n, int size, const void *d_org, const void *d_pred, const void *d_poc, const void *d_qp,
-                                     void *d_split_mode, void *d_logits, DecisionRec *d_dec) {
+                                     void *d_split_mode, void *d_logits, DecisionRec *d_dec, CandRec *d_cand = nullptr) {
   if (!ctx) return MLT_ERR_ARG;
-  if (n < 0 || (!d_split_mode && !d_dec) || (n > 0 && (!d_org || !d_pred || !d_poc || !d_qp))) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  if (n < 0 || (!d_split_mode && !d_dec && !d_cand) || (n > 0 && (!d_org || !d_pred || !d_poc || !d_qp))) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
   SizeState *st;
   int rc = check_size(ctx, size, &st);
   if (rc) return rc;
+  if (d_cand) st->cand_used = true;
   if (n == 0) return MLT_OK;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
   const int nl = st->model.n_logits;
@@ -250,7 +251,7 @@ static int predict_batch_device_impl(mlt_ctx *ctx, int n, int size, const void *
   for (int i0 = 0; i0 < n; i0 += ctx->chunk) {
     const int c = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
     const PassIO io{Planes::dense((const int16_t *)d_org + i0 * cs, (const int16_t *)d_pred + i0 * cs, size), (const int32_t *)d_poc + i0, (const int32_t *)d_qp + i0,
-                    d_split_mode ? (int32_t *)d_split_mode + i0 : nullptr, d_logits ? (float *)d_logits + (size_t)i0 * nl : nullptr, d_dec ? d_dec + i0 : nullptr};
+                    d_split_mode ? (int32_t *)d_split_mode + i0 : nullptr, d_logits ? (float *)d_logits + (size_t)i0 * nl : nullptr, d_dec ? d_dec + i0 : nullptr, d_cand ? d_cand + i0 : nullptr};
     rc = run_checked(ctx, *st, c, io);
     if (rc) return rc;
   }
@@ -269,13 +270,20 @@ int mlt_predict_batch_device_decisions(mlt_ctx *ctx, int n, int size, const void
   return predict_batch_device_impl(ctx, n, size, d_org, d_pred, d_poc, d_qp, nullptr, d_logits, (DecisionRec *)d_decisions);
 }
 
+int mlt_predict_batch_device_candidates(mlt_ctx *ctx, int n, int size, const void *d_org, const void *d_pred, const void *d_poc, const void *d_qp,
+                                        void *d_candidates, void *d_decisions_opt, void *d_logits) {
+  if (ctx && !d_candidates) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  return predict_batch_device_impl(ctx, n, size, d_org, d_pred, d_poc, d_qp, nullptr, d_logits, (DecisionRec *)d_decisions_opt, (CandRec *)d_candidates);
+}
+
 static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *org, const int16_t *pred, const int32_t *poc, const int32_t *qp,
-                      int32_t *split_mode, float *logits, mlt_decision *dec) {   // split_mode or dec may be NULL, not both
+                      int32_t *split_mode, float *logits, mlt_decision *dec, mlt_candidates *cand) {   // at least one of split_mode / dec / cand
   if (!ctx) return MLT_ERR_ARG;
-  if (n < 0 || (!split_mode && !dec) || (n > 0 && (!org || !pred || !poc || !qp))) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  if (n < 0 || (!split_mode && !dec && !cand) || (n > 0 && (!org || !pred || !poc || !qp))) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
   SizeState *st;
   int rc = check_size(ctx, size, &st);
   if (rc) return rc;
+  if (cand) st->cand_used = true;
   if (n == 0) return MLT_OK;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
   const int nl = st->model.n_logits;
@@ -284,7 +292,7 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
   // under the kernels of sub-chunk k (compute stream).  256 MiB of planes per 4096 CUs take about as long over PCIe as the
   // network does, so the overlap is worth ~1.5x end to end when the caller's buffers are pinned (mlt_alloc_pinned).
   const int cap = n < ctx->stage_chunk ? n : ctx->stage_chunk;
-  const StageSet lay(size, cap, nl, dec != nullptr);   // (the records sit beside the split modes and the logits)
+  const StageSet lay(size, cap, nl, dec != nullptr, cand != nullptr);   // (the records sit beside the split modes and the logits)
   const size_t setbytes = lay.bytes();
   const int nset = n > cap ? 2 : 1;
   if ((rc = ensure_stage(ctx, nset * setbytes))) return rc;
@@ -298,7 +306,7 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
   using Set = StageSet::Ptrs;
   auto set_of = [&](int b) { return lay.at(ctx->stage + (size_t)b * setbytes); };
   // (the fast results of a sub-chunk, and what the exact re-run of its flagged CUs overwrites)
-  auto io_of = [&](const Set &S) { return PassIO{Planes::dense(S.d_org, S.d_pred, size), S.d_poc, S.d_qp, S.d_split, logits ? S.d_lg : nullptr, S.d_dec}; };
+  auto io_of = [&](const Set &S) { return PassIO{Planes::dense(S.d_org, S.d_pred, size), S.d_poc, S.d_qp, S.d_split, logits ? S.d_lg : nullptr, S.d_dec, S.d_cand}; };
   const bool guards = st->guards();
   GuardSlot gs[2];
   if (guards)
@@ -306,8 +314,9 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
       if ((rc = guard_slot(ctx, b, cap, nl, &gs[b]))) return rc;
   // Results come back through pinned buffers owned by the context: a D2H into the caller's (usually pageable) arrays
   // would block the host until the kernels are done and serialise the next sub-chunk's H2D behind them.
-  const size_t hres_set = (size_t)cap * 4 + (size_t)cap * nl * 4 + (dec ? (size_t)cap * sizeof(DecisionRec) : 0);
   const size_t hres_dec = (size_t)cap * 4 + (size_t)cap * nl * 4;
+  const size_t hres_cand = hres_dec + (dec ? (size_t)cap * sizeof(DecisionRec) : 0);
+  const size_t hres_set = hres_cand + (cand ? (size_t)cap * sizeof(CandRec) : 0);
   if (ctx->h_res_bytes < 2 * hres_set) {
     if (ctx->h_res) (void)hipHostFree(ctx->h_res);
     ctx->h_res = nullptr; ctx->h_res_bytes = 0;
@@ -321,6 +330,7 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
     HIP_TRY(ctx, hipMemcpyAsync(hb, S.d_split, (size_t)c * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (logits) HIP_TRY(ctx, hipMemcpyAsync(hb + (size_t)cap * 4, S.d_lg, (size_t)c * nl * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (dec) HIP_TRY(ctx, hipMemcpyAsync(hb + hres_dec, S.d_dec, (size_t)c * sizeof(DecisionRec), hipMemcpyDeviceToHost, ctx->stream));
+    if (cand) HIP_TRY(ctx, hipMemcpyAsync(hb + hres_cand, S.d_cand, (size_t)c * sizeof(CandRec), hipMemcpyDeviceToHost, ctx->stream));
     return MLT_OK;
   };
   auto flush = [&](int b) -> int {  // sub-chunk in set b has completed: guard fix-up if needed, then hand its results to the caller
@@ -340,6 +350,7 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
     if (split_mode) std::memcpy(split_mode + pend_i0[b], hb, (size_t)pend_c[b] * 4);
     if (logits) std::memcpy(logits + (size_t)pend_i0[b] * nl, hb + (size_t)cap * 4, (size_t)pend_c[b] * nl * 4);
     if (dec) std::memcpy(dec + pend_i0[b], hb + hres_dec, (size_t)pend_c[b] * sizeof(DecisionRec));
+    if (cand) std::memcpy(cand + pend_i0[b], hb + hres_cand, (size_t)pend_c[b] * sizeof(CandRec));
     pend_i0[b] = -1;
     return MLT_OK;
   };
@@ -372,11 +383,11 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
   return MLT_OK;
 }
 
-// mlt_predict_batch / mlt_predict_batch_decisions (split_mode or dec may be NULL, not both)
+// mlt_predict_batch / _decisions / _candidates (at least one of split_mode / dec / cand)
 static int predict_batch_impl(mlt_ctx *ctx, int n, int size, const int16_t *org, const int16_t *pred, const int32_t *poc, const int32_t *qp,
-                              int32_t *split_mode, float *logits, mlt_decision *dec) {
+                              int32_t *split_mode, float *logits, mlt_decision *dec, mlt_candidates *cand = nullptr) {
   if (!ctx) return MLT_ERR_ARG;
-  if (n < 0 || (!split_mode && !dec) || (n > 0 && (!org || !pred || !poc || !qp))) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  if (n < 0 || (!split_mode && !dec && !cand) || (n > 0 && (!org || !pred || !poc || !qp))) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
   SizeState *st;
   int rc = check_size(ctx, size, &st);
   if (rc) return rc;
@@ -392,7 +403,7 @@ static int predict_batch_impl(mlt_ctx *ctx, int n, int size, const int16_t *org,
     auto run = [&](int g) {
       const int lo = shard_lo(n, g, G), hi = shard_lo(n, g + 1, G);
       if (hi > lo) rcs[(size_t)g] = predict_batch_single(devs[(size_t)g], hi - lo, size, org + (size_t)lo * csz, pred + (size_t)lo * csz, poc + lo, qp + lo,
-                                                         split_mode ? split_mode + lo : nullptr, logits ? logits + (size_t)lo * nlg : nullptr, dec ? dec + lo : nullptr);
+                                                         split_mode ? split_mode + lo : nullptr, logits ? logits + (size_t)lo * nlg : nullptr, dec ? dec + lo : nullptr, cand ? cand + lo : nullptr);
     };
     std::vector<std::thread> th;
     for (int g = 1; g < G; ++g) th.emplace_back(run, g);
@@ -402,7 +413,7 @@ static int predict_batch_impl(mlt_ctx *ctx, int n, int size, const int16_t *org,
       if (rcs[(size_t)g]) { if (g) ctx->err = "device " + std::to_string(devs[(size_t)g]->device) + ": " + devs[(size_t)g]->err; return rcs[(size_t)g]; }
     return MLT_OK;
   }
-  return predict_batch_single(ctx, n, size, org, pred, poc, qp, split_mode, logits, dec);
+  return predict_batch_single(ctx, n, size, org, pred, poc, qp, split_mode, logits, dec, cand);
 }
 
 int mlt_predict_batch(mlt_ctx *ctx, int n, int size, const int16_t *org, const int16_t *pred, const int32_t *poc, const int32_t *qp,
@@ -417,18 +428,27 @@ int mlt_predict_batch_decisions(mlt_ctx *ctx, int n, int size, const int16_t *or
   return predict_batch_impl(ctx, n, size, org, pred, poc, qp, nullptr, logits, out);
 }
 
-// mlt_predict / mlt_predict_decision (split_mode or dec may be NULL, not both)
+int mlt_predict_batch_candidates(mlt_ctx *ctx, int n, int size, const int16_t *org, const int16_t *pred, const int32_t *poc, const int32_t *qp,
+                                 mlt_candidates *out, mlt_decision *dec_opt, float *logits) {
+  if (ctx && !out) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  return predict_batch_impl(ctx, n, size, org, pred, poc, qp, nullptr, logits, dec_opt, out);
+}
+
+// mlt_predict / mlt_predict_decision / mlt_predict_candidates (at least one of split_mode / dec / cand)
 static int predict_one(mlt_ctx *ctx, const int16_t *org, int org_stride, const int16_t *pred, int pred_stride, int size, int32_t poc, int32_t qp,
-                       int32_t *split_mode, float *logits_opt, mlt_decision *dec) {
+                       int32_t *split_mode, float *logits_opt, mlt_decision *dec, mlt_candidates *cand = nullptr) {
   if (!ctx) return MLT_ERR_ARG;
-  if (!org || !pred || (!split_mode && !dec) || org_stride < size || pred_stride < size) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  if (!org || !pred || (!split_mode && !dec && !cand) || org_stride < size || pred_stride < size) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
   SizeState *st;
   int rc = check_size(ctx, size, &st);
   if (rc) return rc;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
   const int nl = st->model.n_logits;
   const size_t cs = (size_t)size * size;
-  SingleCu &sg = ctx->single[size_index(size) + (dec ? 4 : 0)];   // (a graph of its own for the calls that want the record: plain calls replay the launches they always did)
+  if (cand) st->cand_used = true;
+  // (a graph of its own for the calls that want the record, and one for those that want the candidate record -- which always carries the decision record along:
+  // plain calls replay the launches they always did)
+  SingleCu &sg = ctx->single[size_index(size) + (cand ? 8 : dec ? 4 : 0)];
   if (!sg.h_stage) {
     sg.plane = (cs * 2 + 255) / 256 * 256;
     HIP_TRY(ctx, hipHostMalloc((void **)&sg.h_stage, 2 * sg.plane + 256, hipHostMallocDefault));
@@ -444,10 +464,11 @@ static int predict_one(mlt_ctx *ctx, const int16_t *org, int org_stride, const i
   h_sc[0] = poc; h_sc[1] = qp;
   HIP_TRY(ctx, hipMemcpyAsync(sg.d_stage, sg.h_stage, 2 * sg.plane + 8, hipMemcpyHostToDevice, ctx->stream));
   int16_t *d_org = (int16_t *)sg.d_stage, *d_pred = (int16_t *)(sg.d_stage + sg.plane);
-  int32_t *d_sc = (int32_t *)(sg.d_stage + 2 * sg.plane);  // [poc, qp, split, flagged count, logits (<= 16) ..., flat, idx, mag, pad, record (12 words at 24)]
-  DecisionRec *d_dec = dec ? (DecisionRec *)(d_sc + 24) : nullptr;
-  const size_t fetch = dec ? (size_t)(22 + 12) * 4 : (size_t)(2 + nl) * 4;   // split, count, logits [.. record]
-  const PassIO io{Planes::dense(d_org, d_pred, size), d_sc, d_sc + 1, d_sc + 2, (float *)(d_sc + 4), d_dec};
+  int32_t *d_sc = (int32_t *)(sg.d_stage + 2 * sg.plane);  // [poc, qp, split, flagged count, logits (<= 16) ..., flat, idx, mag, pad, record (12 words at 24), candidate record (10 words at 36)]
+  DecisionRec *d_dec = (dec || cand) ? (DecisionRec *)(d_sc + 24) : nullptr;
+  CandRec *d_cand = cand ? (CandRec *)(d_sc + 36) : nullptr;
+  const size_t fetch = cand ? (size_t)(22 + 12 + 10) * 4 : dec ? (size_t)(22 + 12) * 4 : (size_t)(2 + nl) * 4;   // split, count, logits [.. record [, candidate record]]
+  const PassIO io{Planes::dense(d_org, d_pred, size), d_sc, d_sc + 1, d_sc + 2, (float *)(d_sc + 4), d_dec, d_cand};
   const bool guards = st->guards();
   GuardSlot g;
   g.d_count = d_sc + 3; g.d_flat = d_sc + 20; g.d_idx = d_sc + 21; g.d_lg = (float *)(d_sc + 4); g.d_mag = (float *)(d_sc + 22); g.h_count = h_sc + 3;
@@ -494,6 +515,7 @@ static int predict_one(mlt_ctx *ctx, const int16_t *org, int org_stride, const i
   if (split_mode) *split_mode = h_sc[2];
   if (logits_opt) std::memcpy(logits_opt, h_sc + 4, (size_t)nl * 4);
   if (dec) std::memcpy(dec, h_sc + 24, sizeof(DecisionRec));
+  if (cand) std::memcpy(cand, h_sc + 36, sizeof(CandRec));
   return MLT_OK;
 }
 
@@ -509,21 +531,29 @@ int mlt_predict_decision(mlt_ctx *ctx, const int16_t *org, int org_stride, const
   return predict_one(ctx, org, org_stride, pred, pred_stride, size, poc, qp, nullptr, logits_opt, out);
 }
 
+int mlt_predict_candidates(mlt_ctx *ctx, const int16_t *org, int org_stride, const int16_t *pred, int pred_stride, int size, int32_t poc, int32_t qp,
+                           mlt_candidates *out, mlt_decision *dec_opt, float *logits_opt) {
+  if (ctx && !out) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  return predict_one(ctx, org, org_stride, pred, pred_stride, size, poc, qp, nullptr, logits_opt, dec_opt, out);
+}
+
 // ---- deferred single-CU prediction ----
 namespace {
-// device / pinned layout of one output set: split[CAP] | logits[CAP * nl] | flagged count (16 ints) | records[CAP] | flat[CAP] | idx[CAP] | mag[CAP]
+// device / pinned layout of one output set: split[CAP] | logits[CAP * nl] | flagged count (16 ints) | records[CAP] | candidate records[CAP] | flat[CAP] | idx[CAP] | mag[CAP]
 // (a deferred batch always carries its CUs' decision records -- whether a ticket is read with mlt_wait or mlt_wait_decision is not known when the batch is launched:
-// 3 KiB more in the batch's one result copy)
-struct DeferredOut { int32_t *split; float *lg; int32_t *count, *flat, *idx; float *mag; DecisionRec *dec; };
+// 3 KiB more in the batch's one result copy; the candidate records are filled and fetched only by batches launched once the size has a policy or has seen a
+// candidate call -- SizeState.cand_used -- so that every other batch launches and copies what it always did)
+struct DeferredOut { int32_t *split; float *lg; int32_t *count, *flat, *idx; float *mag; DecisionRec *dec; CandRec *cand; };
 DeferredOut deferred_out(char *base, int nl) {
   DeferredOut o;
   o.split = (int32_t *)base; o.lg = (float *)(base + (size_t)MLT_DEFER_CAP * 4);
   o.count = (int32_t *)(base + (size_t)MLT_DEFER_CAP * 4 * (1 + nl));
   o.dec = (DecisionRec *)(o.count + 16);
-  o.flat = (int32_t *)(o.dec + MLT_DEFER_CAP); o.idx = o.flat + MLT_DEFER_CAP; o.mag = (float *)(o.idx + MLT_DEFER_CAP);
+  o.cand = (CandRec *)(o.dec + MLT_DEFER_CAP);
+  o.flat = (int32_t *)(o.cand + MLT_DEFER_CAP); o.idx = o.flat + MLT_DEFER_CAP; o.mag = (float *)(o.idx + MLT_DEFER_CAP);
   return o;
 }
-size_t deferred_fetch_bytes(int nl) { return (size_t)MLT_DEFER_CAP * 4 * (1 + nl) + 64 + (size_t)MLT_DEFER_CAP * sizeof(DecisionRec); }
+size_t deferred_fetch_bytes(int nl, bool cand) { return (size_t)MLT_DEFER_CAP * 4 * (1 + nl) + 64 + (size_t)MLT_DEFER_CAP * (sizeof(DecisionRec) + (cand ? sizeof(CandRec) : 0)); }
 
 int deferred_launch(mlt_ctx *ctx, SizeState *st, Deferred &df) {  // launch the accumulating generation as one batch
   if (df.n == 0) return MLT_OK;
@@ -537,13 +567,15 @@ int deferred_launch(mlt_ctx *ctx, SizeState *st, Deferred &df) {  // launch the 
   HIP_TRY(ctx, hipMemcpyAsync(di + 2 * planes, hi + 2 * planes, (size_t)MLT_DEFER_CAP * 8, hipMemcpyHostToDevice, ctx->stream));
   int32_t *d_poc = (int32_t *)(di + 2 * planes), *d_qp = d_poc + MLT_DEFER_CAP;
   const DeferredOut od = deferred_out(dout, nl), oh = deferred_out(ho, nl);
-  const PassIO io{Planes{(const int16_t *)di, (const int16_t *)(di + planes), size, (long)(df.plane / 2), size, (long)(df.plane / 2)}, d_poc, d_qp, od.split, od.lg, od.dec};
+  df.has_cand[b] = st->cand_used;
+  const PassIO io{Planes{(const int16_t *)di, (const int16_t *)(di + planes), size, (long)(df.plane / 2), size, (long)(df.plane / 2)}, d_poc, d_qp, od.split, od.lg, od.dec,
+                  df.has_cand[b] ? od.cand : nullptr};
   GuardSlot g;
   g.d_flat = od.flat; g.d_idx = od.idx; g.d_count = od.count; g.d_lg = od.lg; g.d_mag = od.mag; g.phase = &df.phase[b]; g.h_count = oh.count;
   const int rc = run_fast_async(ctx, *st, n, io, g);
   df.guard_pending[b] = st->guards();
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ho, dout, deferred_fetch_bytes(nl), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ho, dout, deferred_fetch_bytes(nl, df.has_cand[b]), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipEventRecord(df.done[b], ctx->stream));
   df.n_launched[b] = n;
   df.gen_of_set[b] = df.gen;
@@ -566,12 +598,13 @@ int deferred_guard_fixup(mlt_ctx *ctx, SizeState *st, Deferred &df, int b) {
   if (k == 0) return MLT_OK;
   if (k < 0 || k > df.n_launched[b] || !st->guards()) { ctx->err = "guard: bad flagged-CU count"; return MLT_ERR_HIP; }
   int32_t *d_poc = (int32_t *)(di + 2 * planes), *d_qp = d_poc + MLT_DEFER_CAP;
-  const PassIO io{Planes{(const int16_t *)di, (const int16_t *)(di + planes), size, (long)(df.plane / 2), size, (long)(df.plane / 2)}, d_poc, d_qp, od.split, od.lg, od.dec};
+  const PassIO io{Planes{(const int16_t *)di, (const int16_t *)(di + planes), size, (long)(df.plane / 2), size, (long)(df.plane / 2)}, d_poc, d_qp, od.split, od.lg, od.dec,
+                  df.has_cand[b] ? od.cand : nullptr};
   GuardSlot g;
   g.d_flat = od.flat; g.d_idx = od.idx; g.d_count = od.count; g.d_lg = od.lg; g.d_mag = od.mag; g.h_count = oh.count;
   int rc = guard_fixup_async(ctx, *st, k, io, g);
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ho, dout, deferred_fetch_bytes(nl), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ho, dout, deferred_fetch_bytes(nl, df.has_cand[b]), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return MLT_OK;
 }
@@ -600,7 +633,7 @@ int mlt_submit(mlt_ctx *ctx, const int16_t *org, int org_stride, const int16_t *
   if (!df.h_in) {
     df.plane = ((size_t)size * size * 2 + 255) / 256 * 256;
     df.in_set = 2 * (size_t)MLT_DEFER_CAP * df.plane + (size_t)MLT_DEFER_CAP * 8;
-    df.out_set = (deferred_fetch_bytes(nl) + (size_t)MLT_DEFER_CAP * 12 + 255) / 256 * 256;
+    df.out_set = (deferred_fetch_bytes(nl, true) + (size_t)MLT_DEFER_CAP * 12 + 255) / 256 * 256;
     HIP_TRY(ctx, hipHostMalloc((void **)&df.h_in, 2 * df.in_set, hipHostMallocDefault));
     HIP_TRY(ctx, hipHostMalloc((void **)&df.h_out, 2 * df.out_set, hipHostMallocDefault));
     HIP_TRY(ctx, hipMalloc((void **)&df.d_in, 2 * df.in_set));
@@ -640,23 +673,24 @@ int mlt_flush(mlt_ctx *ctx, int size) {
   return df.h_in ? deferred_launch(ctx, st, df) : MLT_OK;
 }
 
-// mlt_wait / mlt_wait_decision (split_mode or dec may be NULL, not both)
-static int wait_impl(mlt_ctx *ctx, int size, mlt_ticket ticket, int32_t *split_mode, float *logits_opt, mlt_decision *dec) {
+// mlt_wait / mlt_wait_decision / mlt_wait_candidates (at least one of split_mode / dec / cand)
+static int wait_impl(mlt_ctx *ctx, int size, mlt_ticket ticket, int32_t *split_mode, float *logits_opt, mlt_decision *dec, mlt_candidates *cand = nullptr) {
   if (!ctx) return MLT_ERR_ARG;
   if (!ctx->peers.empty()) {
     const int g = (int)(ticket >> 56);
     if (g > (int)ctx->peers.size()) { ctx->err = "unknown ticket"; return MLT_ERR_ARG; }
     if (g > 0) {
       mlt_ctx *p = device_of(ctx, g);
-      const int rc = wait_impl(p, size, ticket & (((mlt_ticket)1 << 56) - 1), split_mode, logits_opt, dec);
+      const int rc = wait_impl(p, size, ticket & (((mlt_ticket)1 << 56) - 1), split_mode, logits_opt, dec, cand);
       if (rc) ctx->err = p->err;
       return rc;
     }
   }
-  if (!split_mode && !dec) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  if (!split_mode && !dec && !cand) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
   SizeState *st;
   int rc = check_size(ctx, size, &st);
   if (rc) return rc;
+  if (cand) st->cand_used = true;   // (before a still accumulating batch is launched below: it then carries the candidate records)
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
   Deferred &df = ctx->deferred[size_index(size)];
   const uint64_t gen = ticket / MLT_DEFER_CAP;
@@ -664,12 +698,14 @@ static int wait_impl(mlt_ctx *ctx, int size, mlt_ticket ticket, int32_t *split_m
   if (!df.h_in || gen > df.gen || (gen == df.gen && slot >= df.n)) { ctx->err = "unknown ticket"; return MLT_ERR_ARG; }
   if (gen == df.gen && (rc = deferred_launch(ctx, st, df))) return rc;  // still accumulating: launch it now
   if (df.gen_of_set[b] != gen || slot >= df.n_launched[b]) { ctx->err = "ticket expired (two newer batches were started)"; return MLT_ERR_ARG; }
+  if (cand && !df.has_cand[b]) { ctx->err = "the ticket's batch was flushed before the size had a candidate policy or a candidate call: it carries no candidate records"; return MLT_ERR_ARG; }
   HIP_TRY(ctx, hipEventSynchronize(df.done[b]));
   if ((rc = deferred_guard_fixup(ctx, st, df, b))) return rc;
   const char *ho = df.h_out + (size_t)b * df.out_set;
   if (split_mode) *split_mode = ((const int32_t *)ho)[slot];
   if (logits_opt) std::memcpy(logits_opt, ho + (size_t)MLT_DEFER_CAP * 4 + (size_t)slot * nl * 4, (size_t)nl * 4);
   if (dec) std::memcpy(dec, deferred_out(const_cast<char *>(ho), nl).dec + slot, sizeof(DecisionRec));
+  if (cand) std::memcpy(cand, deferred_out(const_cast<char *>(ho), nl).cand + slot, sizeof(CandRec));
   return MLT_OK;
 }
 
@@ -681,6 +717,11 @@ int mlt_wait(mlt_ctx *ctx, int size, mlt_ticket ticket, int32_t *split_mode, flo
 int mlt_wait_decision(mlt_ctx *ctx, int size, mlt_ticket ticket, mlt_decision *out, float *logits_opt) {
   if (ctx && !out) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
   return wait_impl(ctx, size, ticket, nullptr, logits_opt, out);
+}
+
+int mlt_wait_candidates(mlt_ctx *ctx, int size, mlt_ticket ticket, mlt_candidates *out, mlt_decision *dec_opt, float *logits_opt) {
+  if (ctx && !out) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  return wait_impl(ctx, size, ticket, nullptr, logits_opt, dec_opt, out);
 }
 
 int mlt_set_confidence_gate(mlt_ctx *ctx, int size, float min_confidence) {
@@ -710,6 +751,38 @@ int mlt_get_confidence_gate(mlt_ctx *ctx, int size, float *min_confidence) {
   const int rc = check_size(ctx, size, &st);
   if (rc) return rc;
   *min_confidence = st->min_conf;
+  return MLT_OK;
+}
+
+int mlt_set_candidate_policy(mlt_ctx *ctx, int size, float coverage, int max_modes) {
+  if (!ctx) return MLT_ERR_ARG;
+  if (!(coverage >= 0.f && coverage < 1.f)) { ctx->err = "mlt_set_candidate_policy: coverage must be in [0, 1)"; return MLT_ERR_ARG; }   // (NaN fails the test)
+  SizeState *st;
+  int rc = check_size(ctx, size, &st);
+  if (rc) return rc;
+  if (max_modes < 0 || max_modes > st->model.heads[st->head_index].classes) { ctx->err = "mlt_set_candidate_policy: max_modes must be in [0, classes of the decision head]"; return MLT_ERR_ARG; }
+  for (mlt_ctx *p : ctx->peers)
+    if ((rc = mlt_set_candidate_policy(p, size, coverage, max_modes))) { ctx->err = p->err; return rc; }
+  // as for the gate: the one-CU graphs bake the policy into the heads kernel's arguments, and deferred batches already launched keep the policy they were
+  // launched with -- their pending exact re-runs happen now
+  if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  drop_graphs(ctx, size_index(size));
+  Deferred &df = ctx->deferred[size_index(size)];
+  for (int b = 0; b < 2; ++b)
+    if (df.guard_pending[b] && (rc = deferred_guard_fixup(ctx, st, df, b))) return rc;
+  st->cand_cov = coverage; st->cand_max = max_modes;
+  st->cand_used = true;
+  return MLT_OK;
+}
+
+int mlt_get_candidate_policy(mlt_ctx *ctx, int size, float *coverage, int *max_modes) {
+  if (!ctx) return MLT_ERR_ARG;
+  if (!coverage || !max_modes) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
+  SizeState *st;
+  const int rc = check_size(ctx, size, &st);
+  if (rc) return rc;
+  *coverage = st->cand_cov; *max_modes = st->cand_max;
   return MLT_OK;
 }
 

@@ -508,7 +508,7 @@ struct CalibSession {
 
 }  // namespace
 void drop_graphs(mlt_ctx *ctx, int si) {  // a captured kernel chain bakes in weight / workspace pointers
-  for (int v = 0; v < 2; ++v) {
+  for (int v = 0; v < 3; ++v) {
     SingleCu &sg = ctx->single[si + 4 * v];
     if (sg.exec) (void)hipGraphExecDestroy(sg.exec);
     if (sg.graph) (void)hipGraphDestroy(sg.graph);

@@ -645,9 +645,10 @@ int run_network(mlt_ctx *ctx, SizeState &st, const NetCfg &c, int n, const PassI
       ha.n_heads = m.n_heads; ha.decision_head = st.head_index; ha.poc = io.poc; ha.qp = io.qp; ha.logits = io.logits; ha.split = io.split;
       ha.mag = go.d_mag;
       ha.dec = io.dec; ha.min_conf = st.min_conf;
+      ha.cand = io.cand; ha.cand_cov = st.cand_cov; ha.cand_max = st.cand_max;
       const GuardTail *tail = go.tail;
       if (tail && (n == 1 || tail->next)) {
-        ha.g_conf_band = tail->conf_band;
+        ha.g_conf_band = tail->conf_band; ha.g_cand_band = tail->cand_band;
         ha.g_next = tail->next;   // (NULL: mlt_predict's slot -- one CU, the count is set outright)
         ha.g_count = tail->count; ha.g_idx = tail->idx; ha.g_flat = tail->flat; ha.g_flat_thr = tail->flat_thr; ha.g_near_thr = tail->near_thr; ha.g_margin = tail->margin;
         ha.g_mag_thr = tail->mag_thr;

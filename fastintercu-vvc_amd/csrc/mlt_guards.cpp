@@ -32,7 +32,7 @@ int guard_slot(mlt_ctx *ctx, int which, int n, int nl, GuardSlot *g) {
 namespace {
 
 // the thresholds of the size's guards: what the selection -- as a tail of the heads kernel or as guard_select_kernel -- compares against
-struct GuardThr { int flat_thr, near_thr; float margin, mag_thr, band; };
+struct GuardThr { int flat_thr, near_thr; float margin, mag_thr, band, cand_band; };
 GuardThr guard_thresholds(const mlt_ctx *ctx, const SizeState &st) {
   const int quads = st.size * st.size / 4;
   GuardThr t;
@@ -41,6 +41,7 @@ GuardThr guard_thresholds(const mlt_ctx *ctx, const SizeState &st) {
   t.margin = st.margin_guard ? st.guard_margin : 0.f;
   t.mag_thr = st.mag_thr;
   t.band = st.conf_band(ctx->tolerance);
+  t.cand_band = st.cand_band(ctx->tolerance);
   return t;
 }
 
@@ -57,7 +58,7 @@ int run_fast_async(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io, const G
   if (!fast.logits && st.margin_guard) fast.logits = g.d_lg;
   GuardOut go;
   go.d_flat = st.flat_guard ? g.d_flat : nullptr;
-  GuardTail tail{nullptr, g.d_idx, go.d_flat, thr.flat_thr, thr.near_thr, thr.margin, thr.mag_thr, nullptr, thr.band};
+  GuardTail tail{nullptr, g.d_idx, go.d_flat, thr.flat_thr, thr.near_thr, thr.margin, thr.mag_thr, nullptr, thr.band, thr.cand_band};
   if (g.single && n == 1) {
     // one CU (mlt_predict's captured graph): the selection is a tail of the heads kernel -- no guard_select launch, no memset of the
     // statistic (the tail clears it for the next call; it is only consumed when the first kernel is the one that produces it: aligned planes,
@@ -95,6 +96,7 @@ int run_fast_async(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io, const G
   sa.head_off = off; sa.head_classes = st.model.heads[st.head_index].classes;
   sa.flat_thr = thr.flat_thr; sa.near_thr = thr.near_thr; sa.margin = thr.margin;
   sa.min_conf = st.min_conf; sa.conf_band = thr.band;
+  sa.cand_cov = st.cand_cov; sa.cand_max = st.cand_max; sa.cand_band = thr.cand_band;
   Launch L{ctx};
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if ((rc = L.prof_begin("guard_select", 0.0, 0.0, e0, e1))) return rc;
@@ -104,10 +106,10 @@ int run_fast_async(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io, const G
   return MLT_OK;
 }
 
-// k > 0 flagged CUs (g.d_idx) of a batch whose fast results are in io.split / io.logits / io.dec: exact re-evaluation, asynchronous.
+// k > 0 flagged CUs (g.d_idx) of a batch whose fast results are in io.split / io.logits / io.dec / io.cand: exact re-evaluation, asynchronous.
 int guard_fixup_async(mlt_ctx *ctx, SizeState &st, int k, const PassIO &io, const GuardSlot &g) {
   const int S = st.size, nl = st.model.n_logits;
-  const StageSet lay(S, k, nl, io.dec != nullptr);
+  const StageSet lay(S, k, nl, io.dec != nullptr, io.cand != nullptr);
   if (lay.bytes() > ctx->gstage_bytes) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->gstage) (void)hipFree(ctx->gstage);
@@ -121,11 +123,12 @@ int guard_fixup_async(mlt_ctx *ctx, SizeState &st, int k, const PassIO &io, cons
   ga.poc = io.poc; ga.qp = io.qp; ga.idx = g.d_idx; ga.k = k; ga.s_l = ilog2(S);
   ga.g_org = gs.d_org; ga.g_pred = gs.d_pred; ga.g_poc = gs.d_poc; ga.g_qp = gs.d_qp;
   HIP_TRY(ctx, mlt_launch_guard_gather(ga, ctx->stream));
-  // (the re-run's heads kernel applies the size's confidence gate to the gathered split modes and fills the flagged CUs' records from the exact logits)
-  int rc = run_network(ctx, st, st.exact_cfg(), k, PassIO{Planes::dense(gs.d_org, gs.d_pred, S), gs.d_poc, gs.d_qp, gs.d_split, gs.d_lg, gs.d_dec});
+  // (the re-run's heads kernel applies the size's confidence gate to the gathered split modes and fills the flagged CUs' records -- decision and candidate -- from the exact logits)
+  int rc = run_network(ctx, st, st.exact_cfg(), k, PassIO{Planes::dense(gs.d_org, gs.d_pred, S), gs.d_poc, gs.d_qp, gs.d_split, gs.d_lg, gs.d_dec, gs.d_cand});
   if (rc) return rc;
   GuardScatterArgs sc{};
   sc.g_dec = gs.d_dec; sc.dec = io.dec;
+  sc.g_cand = gs.d_cand; sc.cand = io.cand;
   sc.idx = g.d_idx; sc.g_split = gs.d_split; sc.g_logits = gs.d_lg; sc.split = io.split; sc.logits = io.logits; sc.k = k; sc.n_logits = nl;
   HIP_TRY(ctx, mlt_launch_guard_scatter(sc, ctx->stream));
   st.reruns += (uint64_t)k;

@@ -193,6 +193,16 @@ struct DecisionRec {
 // admission of the fast arithmetic is statistical); the same factor 1.5 on tol / 2 gives 0.75 tol.
 #define MLT_CONF_BAND_FRAC 0.75f
 
+// Candidate record of one CU (include/mltcnn.h: mlt_candidates -- same 40 bytes; mlt_runtime.h asserts the layout): the smallest set of classes of the decision
+// head that carries `coverage` of the softmax probability (head_candidates, mlt_tail_kernels.inc).
+#define MLT_MAX_CAND_K 6   // classes of the widest head (lvl4 of the CU models)
+struct CandRec {
+  uint32_t mask;
+  int32_t count;
+  int8_t order[8];
+  float prob[MLT_MAX_CAND_K];
+};
+
 struct HeadArgs {
   const float *gap[MLT_MAX_HEADS_K];  // GAP partial sums [n][slots][C] fp32 (written by the stage's last conv)
   int slots[MLT_MAX_HEADS_K];
@@ -209,6 +219,12 @@ struct HeadArgs {
   // flagged when |confidence - min_conf| < g_conf_band (MLT_CONF_BAND_FRAC).
   DecisionRec *dec;
   float min_conf, g_conf_band;
+  // Candidate sets (heads_cand_kernel: mlt_launch_heads picks it when cand != NULL or the policy is not the default (0, 0); every other launch runs heads_kernel).
+  // cand[n] <- the candidate record of CU n under (cand_cov, cand_max).  g_cand_band > 0 (with the guard selection, g_margin > 0): the CU is also flagged when a
+  // proper prefix sum lies within g_cand_band of cand_cov, or when classes are dropped over a logit gap below g_margin (the candidate guard).
+  CandRec *cand;
+  float cand_cov, g_cand_band;
+  int cand_max;
   // Single-CU launches (n == 1, mlt_predict's captured graph): the guard selection rides on this kernel instead of a launch of its own
   // (guard_select_kernel: 5 us of a 160 us call).  g_count != NULL: g_count[0] = 1 and g_idx[0] = 0 when CU 0 is flagged by the
   // flat-content statistic (g_flat, thresholds as GuardSelectArgs) or by the decision-head margin (g_margin > 0), else g_count[0] = 0;
@@ -248,6 +264,8 @@ struct GuardSelectArgs {
   const float *mag;            // [n] (HeadArgs.mag) or NULL: select when mag > mag_thr (round 6: the magnitude guard)
   float mag_thr;
   float min_conf, conf_band;   // conf_band > 0 (with the margin test): select when |confidence - min_conf| < conf_band (HeadArgs.g_conf_band)
+  float cand_cov, cand_band;   // cand_band > 0 (with the margin test): the candidate guard under the policy (cand_cov, cand_max) (HeadArgs.g_cand_band)
+  int cand_max;
 };
 struct GuardGatherArgs {
   const int16_t *org, *pred;
@@ -265,6 +283,8 @@ struct GuardScatterArgs {
   int k, n_logits;
   const DecisionRec *g_dec;    // [k] records of the re-run, or NULL
   DecisionRec *dec;            // [n] or NULL
+  const CandRec *g_cand;       // [k] candidate records of the re-run, or NULL
+  CandRec *cand;               // [n] or NULL
 };
 hipError_t mlt_launch_flat_stat(const FlatStatArgs &a, bool aligned8, hipStream_t st);
 hipError_t mlt_launch_guard_select(const GuardSelectArgs &a, hipStream_t st);

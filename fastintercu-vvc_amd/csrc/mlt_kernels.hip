@@ -818,7 +818,8 @@ hipError_t mlt_launch_layer1_stream(const Layer1Args &a, bool mfma32, int grid_x
 }
 
 hipError_t mlt_launch_heads(const HeadArgs &a, int n, hipStream_t st) {
-  if (a.dec || a.min_conf > 0.f) hipLaunchKernelGGL(heads_kernel<true>, dim3(n), dim3(256), 0, st, a);
+  if (a.cand || a.cand_cov > 0.f || a.cand_max > 0) hipLaunchKernelGGL(heads_cand_kernel, dim3(n), dim3(256), 0, st, a);
+  else if (a.dec || a.min_conf > 0.f) hipLaunchKernelGGL(heads_kernel<true>, dim3(n), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(heads_kernel<false>, dim3(n), dim3(256), 0, st, a);
   return hipGetLastError();
 }

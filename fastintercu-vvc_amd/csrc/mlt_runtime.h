@@ -155,6 +155,14 @@ struct SizeState {
                                // property of the weights: (re)loads and calibrations keep it
   // the gate guard's band (mlt_kernels.h: MLT_CONF_BAND_FRAC x the tolerance the tier was calibrated against); 0 unless gate and decision guard are both on
   float conf_band(float tolerance) const { return (min_conf > 0.f && margin_guard) ? MLT_CONF_BAND_FRAC * tolerance : 0.f; }
+  // candidate policy (mlt_set_candidate_policy): the candidate record keeps the shortest rank prefix of the decision head that carries cand_cov of the softmax
+  // probability, every class when that takes more than cand_max > 0.  (0, 0): the default -- the argmax alone.  Like min_conf it survives (re)loads and calibrations.
+  float cand_cov = 0.f;
+  int cand_max = 0;
+  bool cand_used = false;      // a policy was set or a candidate call made on this size: deferred batches carry candidate records from then on
+  bool cand_policy() const { return cand_cov > 0.f || cand_max > 0; }
+  // the candidate guard's band (same width as the gate guard's); 0 unless a policy is set and the decision guard is on
+  float cand_band(float tolerance) const { return (cand_policy() && margin_guard) ? MLT_CONF_BAND_FRAC * tolerance : 0.f; }
   mlt::Model model;
   mlt::Model model_exact;      // fast sizes: exact-arithmetic copy the guards re-evaluate flagged CUs with
   mlt::Model model_w2;         // hi+lo-weights copy on the fast tiling (MLT_MODEL_W2); built only when the single-pass calibration fails
@@ -185,7 +193,7 @@ struct GuardSlot {
                                // selection rides on the heads kernel, and the caller's own result copy brings the count back
 };
 // guard selection fused into the heads kernel of a single-CU launch (HeadArgs.g_*)
-struct GuardTail { int32_t *count, *idx, *flat; int flat_thr, near_thr; float margin, mag_thr; int32_t *next; float conf_band; };  // next != NULL: batches (HeadArgs.g_next)
+struct GuardTail { int32_t *count, *idx, *flat; int flat_thr, near_thr; float margin, mag_thr; int32_t *next; float conf_band, cand_band; };  // next != NULL: batches (HeadArgs.g_next)
 
 // mlt_predict (one CU per call, the encoder's use): pinned host staging, one H2D, the kernel chain replayed from a
 // hipGraph captured once per CU size, one D2H.
@@ -209,6 +217,7 @@ struct Deferred {
   int n_launched[2] = {0, 0};               // CUs of the generation occupying each set (0: never launched)
   uint64_t gen_of_set[2] = {~0ull, ~0ull};
   hipEvent_t done[2] = {nullptr, nullptr};
+  bool has_cand[2] = {false, false};        // the set's batch was launched with a candidate area (SizeState.cand_used at that time)
   bool guard_pending[2] = {false, false};   // set's batch ran with guards and its flagged CUs have not been re-evaluated yet
   int phase[2] = {0, 0};                    // which of the set's two selection counters (count[0 .. 1]) its next launch counts on (GuardSlot.phase)
 };
@@ -240,7 +249,8 @@ struct mlt_ctx {
   int stage_chunk = 512;  // measured on 4096 x 128x128 from pinned memory: 512 -> 526 k, 1024 -> 498 k, 2048 -> 426 k CU/s
   char *h_res = nullptr;  // pinned result staging (split + logits) for the two sets
   size_t h_res_bytes = 0;
-  SingleCu single[8];   // [4 + si]: the calls that want the decision record (their graph bakes the record pointer into the heads kernel's arguments)
+  SingleCu single[12];  // [4 + si]: the calls that want the decision record (their graph bakes the record pointer into the heads kernel's arguments); [8 + si]: the
+                        // calls that want the candidate record (and the decision record with it)
   Deferred deferred[4];
   // staging for the host-pointer entry points
   char *stage = nullptr;
@@ -274,6 +284,9 @@ struct mlt_ctx {
 static_assert(sizeof(mlt_decision) == 48 && sizeof(DecisionRec) == sizeof(mlt_decision), "mlt_decision is 48 bytes");
 static_assert(offsetof(mlt_decision, confidence) == offsetof(DecisionRec, confidence) && offsetof(mlt_decision, level_mode) == offsetof(DecisionRec, level_mode) &&
               offsetof(mlt_decision, level_conf) == offsetof(DecisionRec, level_conf) && offsetof(mlt_decision, level_conf) == 32, "mlt_decision layout");
+
+static_assert(sizeof(mlt_candidates) == 40 && sizeof(CandRec) == sizeof(mlt_candidates) && offsetof(mlt_candidates, order) == offsetof(CandRec, order) &&
+              offsetof(mlt_candidates, prob) == offsetof(CandRec, prob) && offsetof(mlt_candidates, prob) == 16, "mlt_candidates layout");
 
 #define HIP_TRY(ctx, expr)                                                                             \
   do {                                                                                                 \
@@ -316,6 +329,7 @@ struct PassIO {
   int32_t *split;
   float *logits;
   DecisionRec *dec;
+  CandRec *cand = nullptr;
 };
 
 // what a pass produces for the guards besides (all unset: a plain pass)
@@ -327,18 +341,20 @@ struct GuardOut {
   float *d_mag = nullptr;           // per-CU logit magnitude (HeadArgs.mag)
 };
 
-// One staging set for `cap` dense CUs in device memory: org | pred | poc | qp | split | logits [| records], every part rounded up to 256 bytes
+// One staging set for `cap` dense CUs in device memory: org | pred | poc | qp | split | logits [| records] [| candidate records], every part rounded up to 256 bytes
 // (so every pointer keeps the alignment the quad-fetching kernels want).
 struct StageSet {
-  struct Ptrs { int16_t *d_org, *d_pred; int32_t *d_poc, *d_qp, *d_split; float *d_lg; DecisionRec *d_dec; };
-  size_t plane, small, lgb, decb;
+  struct Ptrs { int16_t *d_org, *d_pred; int32_t *d_poc, *d_qp, *d_split; float *d_lg; DecisionRec *d_dec; CandRec *d_cand; };
+  size_t plane, small, lgb, decb, candb;
   static size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-  StageSet(int S, int cap, int nl, bool records)
-      : plane(up256((size_t)S * S * 2 * cap)), small(up256((size_t)cap * 4)), lgb(up256((size_t)cap * nl * 4)), decb(records ? up256((size_t)cap * sizeof(DecisionRec)) : 0) {}
-  size_t bytes() const { return 2 * plane + 3 * small + lgb + decb; }
+  StageSet(int S, int cap, int nl, bool records, bool cands = false)
+      : plane(up256((size_t)S * S * 2 * cap)), small(up256((size_t)cap * 4)), lgb(up256((size_t)cap * nl * 4)), decb(records ? up256((size_t)cap * sizeof(DecisionRec)) : 0),
+        candb(cands ? up256((size_t)cap * sizeof(CandRec)) : 0) {}
+  size_t bytes() const { return 2 * plane + 3 * small + lgb + decb + candb; }
   Ptrs at(char *base) const {
     return Ptrs{(int16_t *)base, (int16_t *)(base + plane), (int32_t *)(base + 2 * plane), (int32_t *)(base + 2 * plane + small), (int32_t *)(base + 2 * plane + 2 * small),
-                (float *)(base + 2 * plane + 3 * small), decb ? (DecisionRec *)(base + 2 * plane + 3 * small + lgb) : nullptr};
+                (float *)(base + 2 * plane + 3 * small), decb ? (DecisionRec *)(base + 2 * plane + 3 * small + lgb) : nullptr,
+                candb ? (CandRec *)(base + 2 * plane + 3 * small + lgb + decb) : nullptr};
   }
 };
 

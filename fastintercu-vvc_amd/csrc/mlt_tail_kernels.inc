@@ -23,10 +23,75 @@ __device__ __forceinline__ void head_decision(const float *l, int K, int &best, 
   conf = 1.f / sum;
 }
 
+// Candidate set of one head from its K <= MLT_MAX_CAND_K logits, the counterpart of head_decision (include/mltcnn.h: mlt_candidates states the semantics):
+// classes ranked by logit, descending, equal logits in class order (an insertion sort by adjacent exchanges on registers: every index is a compile-time constant
+// after unrolling, nothing lives in scratch); the fp32 softmax of every class -- the operations of head_decision, so prob[argmax] is its confidence bit for bit --
+// prefix sums in rank order; the shortest prefix that reaches `coverage` is kept, every class when that needs more than max_modes > 0 of them or a logit is NaN.
+// flag (band > 0: the candidate guard): a proper prefix sum lies within `band` of the coverage, or classes are dropped over a logit gap below gap_thr -- in the
+// !(x >= y) form, so a NaN flags.  Shared by heads_cand_kernel and guard_select_kernel.
+__device__ __forceinline__ void head_candidates(const float *l, int K, float coverage, int max_modes, float band, float gap_thr, CandRec &r, bool &flag) {
+  int best = 0;
+  for (int k = 1; k < K; ++k)
+    if (l[k] > l[best]) best = k;
+  const float mx = l[best];
+  float sum = 0.f;
+  for (int k = 0; k < K; ++k) sum += expf(l[k] - mx);
+  float key[MLT_MAX_CAND_K], pr[MLT_MAX_CAND_K];
+  int id[MLT_MAX_CAND_K];
+  bool nan = false;
+#pragma unroll
+  for (int k = 0; k < MLT_MAX_CAND_K; ++k) {
+    const bool in = k < K;
+    const float v = l[in ? k : 0];
+    nan = nan || (in && v != v);
+    key[k] = in ? v : -__builtin_inff();   // (padding never moves up: nothing is below it, and equal keys keep their order)
+    id[k] = in ? k : -1;
+    pr[k] = in ? expf(v - mx) / sum : 0.f;
+    r.prob[k] = pr[k];
+  }
+#pragma unroll
+  for (int i = 1; i < MLT_MAX_CAND_K; ++i) {
+#pragma unroll
+    for (int j = i; j > 0; --j) {
+      const bool up = key[j] > key[j - 1];
+      const float tk = key[j], tp = pr[j];
+      const int ti = id[j];
+      key[j] = up ? key[j - 1] : tk; pr[j] = up ? pr[j - 1] : tp; id[j] = up ? id[j - 1] : ti;
+      key[j - 1] = up ? tk : key[j - 1]; pr[j - 1] = up ? tp : pr[j - 1]; id[j - 1] = up ? ti : id[j - 1];
+    }
+  }
+  float cum = 0.f;
+  int n = K;
+  bool found = false, near = false;
+#pragma unroll
+  for (int rk = 0; rk < MLT_MAX_CAND_K; ++rk) {
+    if (rk < K) {
+      cum += pr[rk];
+      if (!found && cum >= coverage) { n = rk + 1; found = true; }
+      if (rk < K - 1) near = near || !(fabsf(cum - coverage) >= band);
+    }
+  }
+  const int kept = (nan || (max_modes > 0 && n > max_modes)) ? K : n;
+  uint32_t mask = 0;
+  float gap = 3.4e38f;   // (nothing dropped: no boundary)
+#pragma unroll
+  for (int rk = 0; rk < MLT_MAX_CAND_K; ++rk) {
+    if (rk < kept) mask |= 1u << (nan ? rk : id[rk]);
+    if (rk + 1 < MLT_MAX_CAND_K && rk + 1 == kept && kept < K) gap = key[rk] - key[rk + 1];
+  }
+  r.mask = mask;
+  r.count = kept;
+#pragma unroll
+  for (int rk = 0; rk < MLT_MAX_CAND_K; ++rk) r.order[rk] = (int8_t)(rk < K ? (nan ? rk : id[rk]) : -1);   // (a NaN row is listed in class order)
+  r.order[6] = r.order[7] = -1;
+  flag = band > 0.f && (near || !(gap >= gap_thr));
+}
+
 // DEC: the instantiation that also computes the decision records / applies the confidence gate (HeadArgs.dec != NULL or min_conf > 0: mlt_launch_heads picks it);
-// <false> is the kernel as it was before records existed -- launches that want neither run exactly that code.
-template <bool DEC>
-__global__ __launch_bounds__(256) void heads_kernel(const HeadArgs a) {
+// <false> is the kernel as it was before records existed -- launches that want neither run exactly that code.  CAND: the body of heads_cand_kernel, which also
+// computes the candidate records and the candidate guard (HeadArgs.cand != NULL or a policy other than (0, 0)); heads_kernel<DEC> is the body without them.
+template <bool DEC, bool CAND>
+__device__ __forceinline__ void heads_body(const HeadArgs &a) {
   __shared__ float feat[MLT_MAX_HEADS_K][256 + 2];
   __shared__ float lg[MLT_MAX_LOGITS_K];
   __shared__ int hmode[MLT_MAX_HEADS_K];      // per head: argmax, its softmax probability, top-2 margin (only when records or the gate are wanted)
@@ -105,6 +170,12 @@ __global__ __launch_bounds__(256) void heads_kernel(const HeadArgs a) {
         a.dec[n] = r;
       }
     }
+    bool cflag = false;
+    if constexpr (CAND) {
+      CandRec cr;
+      head_candidates(lg + off, a.classes[a.decision_head], a.cand_cov, a.cand_max, a.g_cand_band, a.g_margin, cr, cflag);
+      if (a.cand) a.cand[n] = cr;
+    }
     if (!DEC || a.split) a.split[n] = out;   // (only a launch that writes records may come without a split buffer)
     float mag = 0.f;
     if (a.mag || a.g_mag_thr > 0.f) {
@@ -125,6 +196,7 @@ __global__ __launch_bounds__(256) void heads_kernel(const HeadArgs a) {
         }
         s = s || !(t1 - t2 >= a.g_margin);
         if (DEC && a.g_conf_band > 0.f) s = s || !(fabsf(conf - a.min_conf) >= a.g_conf_band);   // the gate guard (mlt_kernels.h: MLT_CONF_BAND_FRAC); also catches NaN
+        if (CAND) s = s || cflag;   // the candidate guard (head_candidates; off unless g_cand_band > 0)
       }
       if (a.g_mag_thr > 0.f) s = s || !(mag <= a.g_mag_thr);
       if (a.g_next) {   // unordered append to a count that was zero on entry; workgroup 0 re-arms the slot's other counter for the next launch
@@ -137,6 +209,12 @@ __global__ __launch_bounds__(256) void heads_kernel(const HeadArgs a) {
     }
   }
 }
+
+template <bool DEC>
+__global__ __launch_bounds__(256) void heads_kernel(const HeadArgs a) { heads_body<DEC, false>(a); }
+
+// Records, gate and candidate sets: launched only when a candidate buffer or a candidate policy is present (mlt_launch_heads).
+__global__ __launch_bounds__(256) void heads_cand_kernel(const HeadArgs a) { heads_body<true, true>(a); }
 
 
 // ---------------------------------------------------------------------------------------------
@@ -196,6 +274,11 @@ __global__ __launch_bounds__(1024) void guard_select_kernel(const GuardSelectArg
         head_decision(l, a.head_classes, bm, cf, mg);
         s = s || !(fabsf(cf - a.min_conf) >= a.conf_band);
       }
+      if (a.cand_band > 0.f) {   // the candidate guard, on the set heads_cand_kernel computed from these logits (same function)
+        CandRec cr; bool cf;
+        head_candidates(l, a.head_classes, a.cand_cov, a.cand_max, a.cand_band, a.margin, cr, cf);
+        s = s || cf;
+      }
     }
     if (a.mag && a.mag_thr > 0.f) s = s || !(a.mag[i] <= a.mag_thr);
     return s;
@@ -234,6 +317,7 @@ __global__ __launch_bounds__(256) void guard_scatter_kernel(const GuardScatterAr
   if (e == a.n_logits) {
     if (a.split) a.split[dst] = a.g_split[j];
     if (a.dec) a.dec[dst] = a.g_dec[j];
+    if (a.cand) a.cand[dst] = a.g_cand[j];
   } else if (a.logits) a.logits[(size_t)dst * a.n_logits + e] = a.g_logits[(size_t)j * a.n_logits + e];
 }
 

@@ -25,6 +25,12 @@
 // A gated call is NOT a failure: no "error" line, not counted in failed=; under MLTCNN_STATS=1 the stats line ends with gated=<count> when a gate
 // is set.  Malformed value: a message on stderr, the gate stays off.  predictDecision() / waitDecision() return the whole decision record.
 //
+// MLTCNN_CANDIDATES (any build, read next to MLTCNN_MIN_CONF): the library's CANDIDATE POLICY (mlt_set_candidate_policy) -- "coverage[/max]" for every enabled
+// size ("0.9", "0.9/2") or per size ("128:0.9/2,64:0.8").  predictCandidates() / waitCandidates() then return, per CU, the smallest set of classes of the
+// decision head that carries `coverage` of the softmax probability -- every class when that takes more than `max` of them (full RDO) -- as a bit mask over
+// CLASS INDICES; keptClasses() lists them in rank order.  Malformed value: a message on stderr, every policy stays at its default (the argmax alone).  Under
+// MLTCNN_STATS=1 the stats line ends with kept_modes=<sum of the counts returned> when a policy is set.
+//
 // Test hooks, compiled in only with -DMLTCNN_TEST_HOOKS (tools/build_vtm.sh does; a production build carries none of them):
 //   MLTCNN_FAULT_INJECT=1      the predictor reports ok() without touching a device and every predictSplitMode() fails (-1):
 //                              exercises the reference's swallow-and-continue contract from the real call site on a box without a GPU
@@ -90,6 +96,8 @@ class SplitPredictor {
     }
     if (m_ctx)
       if (const char *g = std::getenv("MLTCNN_MIN_CONF")) applyMinConf(g);
+    if (m_ctx)
+      if (const char *g = std::getenv("MLTCNN_CANDIDATES")) applyCandidates(g);
   }
   ~SplitPredictor() {
     if (m_stats) {   // (one fprintf for the whole line: predictors of several EncCu threads share stderr)
@@ -97,7 +105,8 @@ class SplitPredictor {
       int k = std::snprintf(line, sizeof line, "mltcnn-stats predict_calls=%llu predict_s=%.6f submit_calls=%llu submit_s=%.6f wait_calls=%llu wait_s=%.6f flush_calls=%llu flush_s=%.6f "
                             "calls_128=%llu calls_64=%llu calls_32=%llu calls_16=%llu failed=%llu init_s=%.6f",
                             m_n[0], m_t[0], m_n[1], m_t[1], m_n[2], m_t[2], m_n[3], m_t[3], m_bySize[0], m_bySize[1], m_bySize[2], m_bySize[3], m_failed, m_initSeconds);
-      if (m_gateSet && k > 0 && k < (int)sizeof line) std::snprintf(line + k, sizeof line - (size_t)k, " gated=%llu", m_gated);
+      if (m_gateSet && k > 0 && k < (int)sizeof line) k += std::snprintf(line + k, sizeof line - (size_t)k, " gated=%llu", m_gated);
+      if (m_policySet && k > 0 && k < (int)sizeof line) std::snprintf(line + k, sizeof line - (size_t)k, " kept_modes=%llu", m_keptModes);
       std::fprintf(stderr, "%s\n", line);
     }
     mlt_shutdown(m_ctx);
@@ -178,6 +187,84 @@ class SplitPredictor {
     return true;
   }
 
+  // The candidate record (include/mltcnn.h: mlt_candidates -- which classes of the decision head stay in the RDO under the size's candidate policy), with the
+  // decision record beside it when decOpt != nullptr.  false on failure: every class kept (full RDO) and decOpt->split_mode = raw_mode = -1.
+  bool predictCandidates(const Pel *org, int orgStride, const Pel *pred, int predStride, int cuw, int poc, int cuQP, mlt_candidates *out, mlt_decision *decOpt = nullptr,
+                         float *logitsOpt = nullptr) {
+    Timer tm(this, 0, cuw);
+    if (!m_ctx || mlt_predict_candidates(m_ctx, org, orgStride, pred, predStride, cuw, poc, cuQP, out, decOpt, logitsOpt) != MLT_OK) {
+      std::fprintf(stderr, "error\n");  // EncCu.cpp:925
+      failCandidates(cuw, out, decOpt);
+      ++m_failed;
+      return false;
+    }
+    m_keptModes += (unsigned long long)out->count;
+    if (decOpt && decOpt->split_mode < 0) ++m_gated;
+    return true;
+  }
+  bool waitCandidates(int cuw, mlt_ticket ticket, mlt_candidates *out, mlt_decision *decOpt = nullptr, float *logitsOpt = nullptr) {
+    Timer tm(this, 2, 0);
+    if (!m_ctx || mlt_wait_candidates(m_ctx, cuw, ticket, out, decOpt, logitsOpt) != MLT_OK) { failCandidates(cuw, out, decOpt); return false; }
+    m_keptModes += (unsigned long long)out->count;
+    if (decOpt && decOpt->split_mode < 0) ++m_gated;
+    return true;
+  }
+
+  // The class indices a candidate record keeps, most probable first (classes[] holds up to 8); returns how many.
+  static int keptClasses(const mlt_candidates &c, int classes[8]) {
+    int n = 0;
+    for (int r = 0; r < 8; ++r)
+      if (c.order[r] >= 0 && ((c.mask >> c.order[r]) & 1u)) classes[n++] = c.order[r];
+    return n;
+  }
+
+  // MLTCNN_CANDIDATES' value -> policies for {128, 64, 32, 16}: "c[/m]" (every size) or "S:c[/m],S:c[/m],..." (sizes not named: the default (0, 0)), each
+  // 0 <= c < 1 and 0 <= m <= 6 (the library checks m against the size's decision head).  Pure host logic; false (every policy at its default) for anything malformed.
+  static bool parseCandidates(const char *spec, float cov[4], int maxModes[4]) {
+    static const int sizes[4] = {128, 64, 32, 16};
+    for (int i = 0; i < 4; ++i) { cov[i] = 0.f; maxModes[i] = 0; }
+    // one "c[/m]" item ending at ',' or the end of the string
+    auto item = [](const char *p, const char **next, float *c, int *m) -> bool {
+      char *end = nullptr;
+      const float v = std::strtof(p, &end);
+      if (end == p || !(v >= 0.f && v < 1.f)) return false;
+      long mm = 0;
+      if (*end == '/') {
+        const char *q = end + 1;
+        if (*q < '0' || *q > '9') return false;
+        mm = std::strtol(q, &end, 10);
+        if (mm < 0 || mm > 6) return false;
+      }
+      if (*end != ',' && *end != 0) return false;
+      *c = v; *m = (int)mm; *next = end;
+      return true;
+    };
+    bool ok = spec && *spec != 0;
+    if (ok && !std::strchr(spec, ':')) {
+      const char *end = nullptr;
+      float c = 0.f; int m = 0;
+      ok = item(spec, &end, &c, &m) && *end == 0;
+      for (int i = 0; i < 4 && ok; ++i) { cov[i] = c; maxModes[i] = m; }
+    } else if (ok) {
+      const char *p = spec;
+      while (ok && *p) {
+        char *end = nullptr;
+        const long sz = std::strtol(p, &end, 10);
+        int si = -1;
+        for (int i = 0; i < 4; ++i) if (sz == sizes[i]) si = i;
+        ok = end != p && *end == ':' && si >= 0;
+        if (!ok) break;
+        const char *after = nullptr;
+        ok = item(end + 1, &after, &cov[si], &maxModes[si]);
+        if (!ok) break;
+        p = *after ? after + 1 : after;
+        if (*after == ',' && !*p) ok = false;   // trailing comma
+      }
+    }
+    if (!ok) for (int i = 0; i < 4; ++i) { cov[i] = 0.f; maxModes[i] = 0; }
+    return ok;
+  }
+
   // MLTCNN_MIN_CONF's value -> thresholds for {128, 64, 32, 16}: "v" (every size) or "S:v,S:v,..." (sizes not named: 0 = off), each 0 <= v < 1.
   // Pure host logic; false (thr all zero) for anything malformed -- the gate then stays off.
   static bool parseMinConf(const char *spec, float thr[4]) {
@@ -226,6 +313,31 @@ class SplitPredictor {
     }
   }
 
+  void applyCandidates(const char *spec) {
+    static const int sizes[4] = {128, 64, 32, 16};
+    float cov[4];
+    int mx[4];
+    if (!parseCandidates(spec, cov, mx)) {
+      std::fprintf(stderr, "mltcnn: MLTCNN_CANDIDATES=\"%s\" is malformed (want \"c[/m]\" or \"128:c[/m],64:c[/m],...\", 0 <= c < 1, 0 <= m <= 6): default candidate policy\n", spec);
+      return;
+    }
+    for (int i = 0; i < 4; ++i) {
+      if (!(m_mask & (1u << i)) || (cov[i] <= 0.f && mx[i] == 0)) continue;
+      if (mlt_set_candidate_policy(m_ctx, sizes[i], cov[i], mx[i]) == MLT_OK) m_policySet = true;
+      else std::fprintf(stderr, "mltcnn: candidate policy for size %d not set: %s\n", sizes[i], mlt_last_error(m_ctx));
+    }
+  }
+  // a failed candidate call: every class of the decision head kept (the encoder tests everything; this class configures the reference's heads: element [2] of the
+  // 128 model, four classes, element [0] otherwise, two), no prediction in the decision record
+  static void failCandidates(int cuw, mlt_candidates *out, mlt_decision *decOpt) {
+    *out = mlt_candidates{};
+    const int k = cuw == 128 ? 4 : 2;
+    out->mask = (1u << k) - 1u;
+    out->count = k;
+    for (int r = 0; r < 8; ++r) out->order[r] = (int8_t)(r < k ? r : -1);
+    if (decOpt) { *decOpt = mlt_decision{}; decOpt->split_mode = decOpt->raw_mode = -1; }
+  }
+
   // one record per call: int32 {magic 0x4D4C5443, cuw, poc, qp, split, nLogits}, float logits[MLT_MAX_LOGITS], int16 org[cuw*cuw], int16 pred[cuw*cuw]
   // -- built in a buffer and written with ONE write(2) on an O_APPEND descriptor (atomic with respect to other appenders: predictors
   // of several EncCu threads share one dump file); a failed write is reported once.
@@ -265,6 +377,8 @@ class SplitPredictor {
   double m_t[4] = {0, 0, 0, 0};
   unsigned long long m_gated = 0;   // calls the confidence gate withheld (split -1 from a call that succeeded)
   bool m_gateSet = false;           // MLTCNN_MIN_CONF set a gate on at least one size
+  unsigned long long m_keptModes = 0;   // sum of the counts predictCandidates / waitCandidates returned
+  bool m_policySet = false;         // MLTCNN_CANDIDATES set a policy on at least one size
   double m_initSeconds = 0.0;   // wall-clock of mlt_init (weights + load-time calibration): what an encoder process pays once
 
   mlt_ctx *m_ctx = nullptr;

@@ -271,6 +271,50 @@ int mlt_predict_batch_device_decisions(mlt_ctx *ctx, int n, int size, const void
                                        const void *d_poc, const void *d_qp, void *d_decisions, void *d_logits);
 int mlt_wait_decision(mlt_ctx *ctx, int size, mlt_ticket ticket, mlt_decision *out, float *logits_opt);
 
+/* ---- Candidate split sets: top-p mode masks on every entry point (new exports; MLT_ABI_VERSION stays 4) ----
+ * Between "test exactly one split" (the integer) and "test everything" (-1): per CU, the smallest set of classes of the DECISION head that carries a chosen share
+ * of the softmax probability, with a cap above which the CU falls back to full RDO.  Computed on the device from the logits the call returns (K classes, l[0..K-1]):
+ *   1. rank     stable sort of the classes by logit, descending; equal logits put the lower class first (the first-max rule, extended); order[r] = class at rank r
+ *   2. prob     e[k] = expf(l[k] - l[order[0]]), sum added in class order, prob[k] = e[k] / sum, fp32 -- the operations behind mlt_decision.confidence, so
+ *               prob[raw_mode] is bit-equal to it
+ *   3. cum      cum[r] = prob[order[0]] + ... + prob[order[r]], fp32, added in rank order
+ *   4. n        the smallest r + 1 with cum[r] >= coverage; K if rounding lets no prefix reach it
+ *   5. cap      max_modes > 0 and n > max_modes: the network is unsure, all K classes are kept (full RDO, the meaning of the gate's -1); else the first n ranks
+ *   6. mask     bit k set for every kept class k; count = popcount(mask)
+ *   7. NaN      any NaN logit in the head keeps all K classes (order then lists them in class order)
+ * The default policy (0, 0) gives mask = 1 << raw_mode, count = 1; (t, 1) is the confidence gate restated as a mask (one class iff confidence >= t, else all).
+ * The bits are CLASS INDICES of the decision head; mapping classes to PartSplit stays the integrator's job, as for the integer (identity for head [2] of the 128
+ * model).  Policy and confidence gate are independent: the gate changes split_mode only, the policy the candidate record only. */
+typedef struct mlt_candidates {   /* 40 bytes, little-endian, no padding */
+  uint32_t mask;      /* bit k = class k of the decision head stays in the RDO */
+  int32_t  count;     /* popcount(mask) */
+  int8_t   order[8];  /* classes, most probable first; -1 beyond K */
+  float    prob[6];   /* softmax probability of class k (class order); 0 beyond K */
+} mlt_candidates;
+
+/* Candidate policy of one CU size.  0 <= coverage < 1 (NaN, negative or >= 1 -> MLT_ERR_ARG); 0 <= max_modes <= K of the size's decision head (else MLT_ERR_ARG);
+ * size not loaded -> MLT_ERR_SIZE_DISABLED.  Like the gate: per-size state, addresses every device of a multi-device context, takes effect for batches launched
+ * after it returns, invalidates captured graphs, survives mlt_load_weights and mlt_calibrate.
+ * Candidate guard: on sizes that run a non-exact tier with the decision guard on, once a policy other than (0, 0) is set, a CU is re-evaluated with the exact
+ * arithmetic (counted in guard_reruns) when (a) a proper prefix sum lies within 0.75 x tolerance of the coverage, or (b) classes are dropped and the logit gap
+ * between the last kept and the first dropped class is below the size's guard margin -- so fp16 rounding decides neither how many classes are kept nor which
+ * one is the last.  Like the gate guard it acts on EVERY entry point of that size, old ones included (the twins' logits stay bit-identical). */
+int mlt_set_candidate_policy(mlt_ctx *ctx, int size, float coverage, int max_modes);
+int mlt_get_candidate_policy(mlt_ctx *ctx, int size, float *coverage, int *max_modes);
+
+/* The candidate twins of mlt_predict / mlt_predict_batch / mlt_predict_batch_device / mlt_wait: same arguments, same implementation (chunking, staging
+ * pipeline, guards, sharding over devices[], deferred slots), a candidate record per CU, and -- dec_opt / d_decisions_opt != NULL -- the decision record beside
+ * it.  Logits and decision records are bit-identical to what the existing twins return under the same policy and gate.  d_candidates: n x 40 bytes of DEVICE
+ * memory.  A deferred batch carries candidate records once a policy is set or a candidate call has been made for the size on this context;
+ * mlt_wait_candidates on a batch that was FLUSHED before either returns MLT_ERR_ARG (a ticket still accumulating is launched with them). */
+int mlt_predict_candidates(mlt_ctx *ctx, const int16_t *org, int org_stride, const int16_t *pred, int pred_stride,
+                           int size, int32_t poc, int32_t qp, mlt_candidates *out, mlt_decision *dec_opt, float *logits_opt);
+int mlt_predict_batch_candidates(mlt_ctx *ctx, int n, int size, const int16_t *org, const int16_t *pred,
+                                 const int32_t *poc, const int32_t *qp, mlt_candidates *out, mlt_decision *dec_opt, float *logits);
+int mlt_predict_batch_device_candidates(mlt_ctx *ctx, int n, int size, const void *d_org, const void *d_pred,
+                                        const void *d_poc, const void *d_qp, void *d_candidates, void *d_decisions_opt, void *d_logits);
+int mlt_wait_candidates(mlt_ctx *ctx, int size, mlt_ticket ticket, mlt_candidates *out, mlt_decision *dec_opt, float *logits_opt);
+
 int mlt_synchronize(mlt_ctx *ctx);
 
 /* Use an existing hipStream_t (e.g. the caller's) instead of the context's own stream; NULL switches back to a
