@@ -31,7 +31,8 @@ EXPORTS = ["mlt_abi_version", "mlt_build_signature", "mlt_init", "mlt_num_device
            "mlt_set_confidence_gate", "mlt_get_confidence_gate", "mlt_predict_decision", "mlt_predict_batch_decisions", "mlt_predict_batch_device_decisions",
            "mlt_wait_decision",
            "mlt_set_candidate_policy", "mlt_get_candidate_policy", "mlt_predict_candidates", "mlt_predict_batch_candidates",
-           "mlt_predict_batch_device_candidates", "mlt_wait_candidates"]
+           "mlt_predict_batch_device_candidates", "mlt_wait_candidates",
+           "mlt_picture_create", "mlt_picture_upload", "mlt_picture_wrap_device", "mlt_picture_destroy", "mlt_predict_at", "mlt_grid_positions"]
 
 
 class MltConfig(C.Structure):
@@ -132,6 +133,12 @@ def load_library():
     lib.mlt_predict_batch_candidates.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.mlt_predict_batch_device_candidates.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.mlt_wait_candidates.argtypes = [vp, i32, C.c_uint64, C.POINTER(MltCandidates), C.POINTER(MltDecision), vp]
+    lib.mlt_picture_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
+    lib.mlt_picture_upload.argtypes = [vp, vp, vp, i32]
+    lib.mlt_picture_wrap_device.argtypes = [vp, vp, i32, i32, i32, C.POINTER(vp)]
+    lib.mlt_picture_destroy.argtypes = [vp, vp]
+    lib.mlt_predict_at.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.mlt_grid_positions.argtypes = [i32, i32, i32, vp, i32]
     lib.mlt_synchronize.argtypes = [vp]
     lib.mlt_set_stream.argtypes = [vp, vp]
     lib.mlt_alloc_pinned.restype = vp
@@ -146,6 +153,35 @@ def load_library():
     lib.mlt_shutdown.restype = None
     _LIB = lib
     return lib
+
+
+def grid_positions(width: int, height: int, size: int) -> np.ndarray:
+    """[count, 2] int32 {x, y} of the complete CUs on the size-aligned grid of a width x height picture, raster order (mlt_grid_positions; pure host)."""
+    lib = load_library()
+    count = lib.mlt_grid_positions(int(width), int(height), int(size), None, 0)
+    xy = np.zeros((count, 2), np.int32)
+    if count:
+        assert lib.mlt_grid_positions(int(width), int(height), int(size), xy.ctypes.data, count) == count
+    return xy
+
+
+class Picture:
+    """`mlt_picture`: one int16 luma plane in device memory, owned by the context it was made on (MltCnn.picture / MltCnn.wrap_picture)."""
+
+    def __init__(self, ctx: "MltCnn", handle, width: int, height: int, keep=None):
+        self._ctx, self._h, self.width, self.height = ctx, handle, width, height
+        self._keep = keep   # a wrapped plane's owner (e.g. the torch tensor), so that it outlives the handle
+
+    def upload(self, plane: np.ndarray):
+        """plane: int16 [height, width] with unit column stride and any row stride (taken from the array): host -> every device of the context."""
+        assert plane.dtype == np.int16 and plane.shape == (self.height, self.width) and plane.strides[1] == 2 and plane.strides[0] % 2 == 0
+        self._ctx._check(self._ctx._lib.mlt_picture_upload(self._ctx._h, self._h, plane.ctypes.data, plane.strides[0] // 2))
+        return self
+
+    def close(self):
+        if self._h and self._ctx._h:
+            self._ctx._check(self._ctx._lib.mlt_picture_destroy(self._ctx._h, self._h))
+        self._h = None
 
 
 class MltCnn:
@@ -390,6 +426,41 @@ class MltCnn:
         logits = np.zeros(self.num_logits(size) or 1, np.float32)
         self._check(self._lib.mlt_wait_candidates(self._h, size, C.c_uint64(ticket), C.byref(c), C.byref(d), logits.ctypes.data))
         return self._candidates(c), self._record(d), logits
+
+    # -- device-resident pictures ------------------------------------------------------------------
+    def picture(self, width: int, height: int) -> Picture:
+        """A library-owned plane on every device of the context (mlt_picture_create); fill it with Picture.upload."""
+        h = C.c_void_p()
+        self._check(self._lib.mlt_picture_create(self._h, int(width), int(height), C.byref(h)))
+        return Picture(self, h, int(width), int(height))
+
+    def wrap_picture(self, ptr: int, stride: int, width: int, height: int, keep=None) -> Picture:
+        """A plane the caller holds in device memory (e.g. torch tensor .data_ptr()), stride in elements; no copy (mlt_picture_wrap_device)."""
+        h = C.c_void_p()
+        self._check(self._lib.mlt_picture_wrap_device(self._h, ptr, int(stride), int(width), int(height), C.byref(h)))
+        return Picture(self, h, int(width), int(height), keep)
+
+    def predict_at(self, size: int, org_pic: Picture, pred_pic: Picture, xy, poc, qp, want=("split", "logits", "decisions", "candidates")) -> dict:
+        """CUs of size x size at xy[i] = (x, y) of the picture pair (mlt_predict_at) -> {name: array} for the names in `want`."""
+        xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        n = xy.shape[0]
+        poc = np.ascontiguousarray(poc, np.int32)
+        qp = np.ascontiguousarray(qp, np.int32)
+        assert poc.shape == (n,) and qp.shape == (n,) and set(want) <= {"split", "logits", "decisions", "candidates"}
+        out = {}
+        if "split" in want:
+            out["split"] = np.full((n,), -1, np.int32)
+        if "logits" in want:
+            out["logits"] = np.zeros((n, self.num_logits(size) or 1), np.float32)
+        if "decisions" in want:
+            out["decisions"] = np.zeros((n,), DECISION_DTYPE)
+            out["decisions"]["split_mode"] = -1
+        if "candidates" in want:
+            out["candidates"] = np.zeros((n,), CANDIDATES_DTYPE)
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        self._check(self._lib.mlt_predict_at(self._h, int(size), org_pic._h, pred_pic._h, n, xy.ctypes.data, poc.ctypes.data, qp.ctypes.data,
+                                             ptr("split"), ptr("logits"), ptr("decisions"), ptr("candidates")))
+        return out
 
     def synchronize(self):
         self._check(self._lib.mlt_synchronize(self._h))

@@ -14,6 +14,8 @@ namespace {
 std::string g_init_error;
 std::mutex g_mutex;
 
+}  // namespace
+
 int ensure_stage(mlt_ctx *ctx, size_t bytes) {
   if (bytes <= ctx->stage_bytes) return MLT_OK;
   if (ctx->stage) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->stage); ctx->stage = nullptr; ctx->stage_bytes = 0; }
@@ -21,8 +23,6 @@ int ensure_stage(mlt_ctx *ctx, size_t bytes) {
   ctx->stage_bytes = bytes;
   return MLT_OK;
 }
-
-}  // namespace
 
 extern "C" {
 #pragma GCC visibility push(default)
@@ -136,9 +136,6 @@ int init_one(const mlt_config *cfg, int device, mlt_ctx **out) {
   return MLT_OK;
 }
 
-// contiguous shard of n items for device g of G (fastintercu-vvc_amd/shard.py: shard_bounds)
-inline int shard_lo(int n, int g, int G) { return (int)(((long long)n * g) / G); }
-inline mlt_ctx *device_of(mlt_ctx *ctx, int i) { return i == 0 ? ctx : ctx->peers[(size_t)i - 1]; }
 }  // namespace
 
 extern "C" {
@@ -173,6 +170,7 @@ mlt_ctx *mlt_device_ctx(mlt_ctx *ctx, int index) {
 
 void mlt_shutdown(mlt_ctx *ctx) {
   if (!ctx) return;
+  free_pictures(ctx);   // (a picture of a multi-device context holds a plane on every peer's device)
   for (mlt_ctx *p : ctx->peers) mlt_shutdown(p);
   ctx->peers.clear();
   (void)hipSetDevice(ctx->device);

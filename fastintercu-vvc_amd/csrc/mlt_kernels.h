@@ -286,6 +286,16 @@ struct GuardScatterArgs {
   const CandRec *g_cand;       // [k] candidate records of the re-run, or NULL
   CandRec *cand;               // [n] or NULL
 };
+// ---- device-resident pictures (mlt_predict_at): CUs named by position, gathered out of two pitched planes into dense staging (mlt_picture_kernels.inc) ----
+struct PictureGatherArgs {
+  const int16_t *org, *pred;   // sample (0, 0) of the two pictures; they are independent sources (base, pitch, alignment class each)
+  long org_pitch, pred_pitch;  // in elements
+  const int32_t *xy;           // [c][2]: x, y of every CU's top-left sample, validated by the host against the pictures' width and height
+  int16_t *g_org, *g_pred;     // dense [c][S][S], 16-byte aligned
+  int c, s_l;                  // CU size S = 1 << s_l (16 .. 128)
+  int vec_org, vec_pred;       // the plane's extent starts and ends on 16-byte boundaries: aligned 16-byte loads may be used (else 2-byte loads only)
+};
+hipError_t mlt_launch_picture_gather(const PictureGatherArgs &a, hipStream_t st);
 hipError_t mlt_launch_flat_stat(const FlatStatArgs &a, bool aligned8, hipStream_t st);
 hipError_t mlt_launch_guard_select(const GuardSelectArgs &a, hipStream_t st);
 hipError_t mlt_launch_guard_gather(const GuardGatherArgs &a, hipStream_t st);

@@ -280,6 +280,7 @@ template <int Q, class ACC = float16v> __device__ __forceinline__ half4 act_quad
 #include "mlt_layer0_kernel.inc"  // layer0_stream_kernel
 #include "mlt_layer1_kernel.inc"  // layer1_stream_kernel
 #include "mlt_tail_kernels.inc"   // heads_kernel, flat_stat / guard kernels
+#include "mlt_picture_kernels.inc"  // picture_gather_kernel
 
 // ---------------------------------------------------------------------------------------------
 // launchers
@@ -843,5 +844,14 @@ hipError_t mlt_launch_guard_gather(const GuardGatherArgs &a, hipStream_t st) {
 hipError_t mlt_launch_guard_scatter(const GuardScatterArgs &a, hipStream_t st) {
   const int items = a.k * (a.n_logits + 1);
   hipLaunchKernelGGL(guard_scatter_kernel, dim3((items + 255) / 256), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// flat grid-stride launch over 16-byte items (mlt_picture_kernels.inc): enough workgroups to fill the device (256 CUs x 8 waves of 64 = 8 workgroups of 256
+// per CU), never more than there are items
+hipError_t mlt_launch_picture_gather(const PictureGatherArgs &a, hipStream_t st) {
+  const size_t items = (size_t)a.c << (2 * a.s_l - 2);   // two planes x c x S x S / 8
+  const size_t want = (items + 255) / 256;
+  hipLaunchKernelGGL(picture_gather_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
   return hipGetLastError();
 }

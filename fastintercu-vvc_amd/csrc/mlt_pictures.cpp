@@ -1,0 +1,206 @@
+// mlt_pictures.cpp -- device-resident pictures (include/mltcnn.h): mlt_picture_create / _upload / _wrap_device / _destroy, mlt_predict_at, mlt_grid_positions.
+//
+// A picture is a pitched int16 luma plane per device of its context.  mlt_predict_at validates the positions on the host, then per chunk: positions + poc + qp H2D,
+// picture_gather_kernel (mlt_picture_kernels.inc) -> the dense [c][S][S] planes of a staging set, run_checked on those planes -- the launches, guards and exact
+// re-runs of mlt_predict_batch_device, so every result is the dense path's bit for bit -- results D2H.  The network kernels know nothing about pictures.
+#include "mlt_runtime.h"
+
+namespace {
+
+const int kMinDim = 16, kMaxDim = 16384;
+
+bool owns(const mlt_ctx *ctx, const mlt_picture *pic) {
+  for (const mlt_picture *p : ctx->pictures)
+    if (p == pic) return true;
+  return false;
+}
+
+void release(mlt_ctx *ctx, mlt_picture *pic) {
+  if (pic->owned)
+    for (size_t g = 0; g < pic->plane.size(); ++g)
+      if (pic->plane[g]) { (void)hipSetDevice(device_of(ctx, (int)g)->device); (void)hipFree(pic->plane[g]); }
+  delete pic;
+}
+
+struct AtOut { int32_t *split; float *logits; mlt_decision *dec; mlt_candidates *cand; };
+
+// one device: CUs [0, n) of xy / poc / qp from the planes this device holds (dev: the device's own context)
+int predict_at_single(mlt_ctx *dev, SizeState *st, const int16_t *d_org, long org_pitch, bool org_vec, const int16_t *d_pred, long pred_pitch, bool pred_vec, int n,
+                      const int32_t *xy, const int32_t *poc, const int32_t *qp, const AtOut &out) {
+  if (hipSetDevice(dev->device) != hipSuccess) { dev->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
+  const int size = st->size, nl = st->model.n_logits;
+  if (out.cand) st->cand_used = true;
+  const int cap = n < dev->chunk ? n : dev->chunk;
+  const StageSet lay(size, cap, nl, out.dec != nullptr, out.cand != nullptr);
+  int rc;
+  if ((rc = ensure_stage(dev, lay.bytes() + StageSet::up256((size_t)cap * 8)))) return rc;   // the set, then the chunk's positions
+  const StageSet::Ptrs S = lay.at(dev->stage);
+  int32_t *d_xy = (int32_t *)(dev->stage + lay.bytes());
+  for (int i0 = 0; i0 < n; i0 += cap) {
+    const int c = n - i0 < cap ? n - i0 : cap;
+    HIP_TRY(dev, hipMemcpyAsync(d_xy, xy + 2 * (size_t)i0, (size_t)c * 8, hipMemcpyHostToDevice, dev->stream));
+    HIP_TRY(dev, hipMemcpyAsync(S.d_poc, poc + i0, (size_t)c * 4, hipMemcpyHostToDevice, dev->stream));
+    HIP_TRY(dev, hipMemcpyAsync(S.d_qp, qp + i0, (size_t)c * 4, hipMemcpyHostToDevice, dev->stream));
+    PictureGatherArgs ga{};
+    ga.org = d_org; ga.pred = d_pred; ga.org_pitch = org_pitch; ga.pred_pitch = pred_pitch; ga.vec_org = org_vec; ga.vec_pred = pred_vec;
+    ga.xy = d_xy; ga.g_org = S.d_org; ga.g_pred = S.d_pred; ga.c = c; ga.s_l = ilog2(size);
+    Launch L{dev};
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    // algorithmic bytes: both planes of every CU read once and written once
+    if ((rc = L.prof_begin("picture_gather", 0.0, (double)c * size * size * 2 * 2 * 2, e0, e1))) return rc;
+    LAUNCH_TRY(dev, mlt_launch_picture_gather(ga, dev->stream));
+    if ((rc = L.prof_end(e1))) return rc;
+    // (the guards and their exact re-run read the gathered planes; the staging pointers are 256-byte aligned: CLS_QUADS whatever the picture's alignment)
+    const PassIO io{Planes::dense(S.d_org, S.d_pred, size), S.d_poc, S.d_qp, S.d_split, out.logits ? S.d_lg : nullptr, S.d_dec, S.d_cand};
+    if ((rc = run_checked(dev, *st, c, io))) return rc;
+    if (out.split) HIP_TRY(dev, hipMemcpyAsync(out.split + i0, S.d_split, (size_t)c * 4, hipMemcpyDeviceToHost, dev->stream));
+    if (out.logits) HIP_TRY(dev, hipMemcpyAsync(out.logits + (size_t)i0 * nl, S.d_lg, (size_t)c * nl * 4, hipMemcpyDeviceToHost, dev->stream));
+    if (out.dec) HIP_TRY(dev, hipMemcpyAsync(out.dec + i0, S.d_dec, (size_t)c * sizeof(DecisionRec), hipMemcpyDeviceToHost, dev->stream));
+    if (out.cand) HIP_TRY(dev, hipMemcpyAsync(out.cand + i0, S.d_cand, (size_t)c * sizeof(CandRec), hipMemcpyDeviceToHost, dev->stream));
+    HIP_TRY(dev, hipStreamSynchronize(dev->stream));   // the set is reused by the next chunk, the arrays are the caller's
+  }
+  return MLT_OK;
+}
+
+}  // namespace
+
+void free_pictures(mlt_ctx *ctx) {
+  for (mlt_picture *p : ctx->pictures) release(ctx, p);
+  ctx->pictures.clear();
+}
+
+extern "C" {
+#pragma GCC visibility push(default)
+
+int mlt_picture_create(mlt_ctx *ctx, int width, int height, mlt_picture **out) {
+  if (!ctx) return MLT_ERR_ARG;
+  if (!out || width < kMinDim || height < kMinDim || width > kMaxDim || height > kMaxDim) { ctx->err = "mlt_picture_create: bad argument (16 <= width, height <= 16384)"; return MLT_ERR_ARG; }
+  *out = nullptr;
+  mlt_picture *pic = new (std::nothrow) mlt_picture();
+  if (!pic) return MLT_ERR_NOMEM;
+  pic->owner = ctx; pic->width = width; pic->height = height; pic->owned = true; pic->vec = true;
+  pic->pitch = ((long)width + 63) / 64 * 64;
+  const int G = 1 + (int)ctx->peers.size();
+  pic->plane.assign((size_t)G, nullptr);
+  for (int g = 0; g < G; ++g) {
+    mlt_ctx *dev = device_of(ctx, g);
+    hipError_t e = hipSetDevice(dev->device);
+    if (e == hipSuccess) e = hipMalloc((void **)&pic->plane[(size_t)g], (size_t)height * (size_t)pic->pitch * 2);
+    if (e != hipSuccess) {
+      ctx->err = std::string("mlt_picture_create: ") + hipGetErrorString(e);
+      release(ctx, pic);
+      return e == hipErrorOutOfMemory ? MLT_ERR_NOMEM : MLT_ERR_HIP;
+    }
+  }
+  ctx->pictures.push_back(pic);
+  *out = pic;
+  return MLT_OK;
+}
+
+int mlt_picture_wrap_device(mlt_ctx *ctx, const void *d_plane, int stride, int width, int height, mlt_picture **out) {
+  if (!ctx) return MLT_ERR_ARG;
+  if (!out || !d_plane || ((uintptr_t)d_plane & 1) || width < kMinDim || height < kMinDim || width > kMaxDim || height > kMaxDim || stride < width) {
+    ctx->err = "mlt_picture_wrap_device: bad argument (2-byte aligned plane, 16 <= width, height <= 16384, stride >= width)";
+    return MLT_ERR_ARG;
+  }
+  *out = nullptr;
+  if (!ctx->peers.empty()) { ctx->err = "mlt_picture_wrap_device: a device plane lives on ONE device -- wrap it on mlt_device_ctx(ctx, i)"; return MLT_ERR_ARG; }
+  mlt_picture *pic = new (std::nothrow) mlt_picture();
+  if (!pic) return MLT_ERR_NOMEM;
+  pic->owner = ctx; pic->width = width; pic->height = height; pic->pitch = stride; pic->owned = false;
+  const uintptr_t lo = (uintptr_t)d_plane, hi = lo + (((size_t)height - 1) * (size_t)stride + (size_t)width) * 2;
+  pic->vec = ((lo | hi) & 15) == 0;   // aligned 16-byte windows that hold a byte of the extent then lie inside it (mlt_picture_kernels.inc)
+  pic->plane.assign(1, (int16_t *)const_cast<void *>(d_plane));
+  ctx->pictures.push_back(pic);
+  *out = pic;
+  return MLT_OK;
+}
+
+int mlt_picture_upload(mlt_ctx *ctx, mlt_picture *pic, const int16_t *plane, int stride) {
+  if (!ctx) return MLT_ERR_ARG;
+  if (!pic || !plane || !owns(ctx, pic) || stride < pic->width) { ctx->err = "mlt_picture_upload: bad argument (a picture of this context, stride >= width)"; return MLT_ERR_ARG; }
+  if (!pic->owned) { ctx->err = "mlt_picture_upload: a wrapped picture is the caller's memory"; return MLT_ERR_ARG; }
+  const int G = (int)pic->plane.size();
+  for (int g = 0; g < G; ++g) {
+    mlt_ctx *dev = device_of(ctx, g);
+    if (hipSetDevice(dev->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
+    HIP_TRY(ctx, hipMemcpy2DAsync(pic->plane[(size_t)g], (size_t)pic->pitch * 2, plane, (size_t)stride * 2, (size_t)pic->width * 2, (size_t)pic->height, hipMemcpyHostToDevice, dev->stream));
+  }
+  for (int g = 0; g < G; ++g) {   // the host buffer may be reused once every copy has read it
+    mlt_ctx *dev = device_of(ctx, g);
+    if (hipSetDevice(dev->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
+    HIP_TRY(ctx, hipStreamSynchronize(dev->stream));
+  }
+  return MLT_OK;
+}
+
+int mlt_picture_destroy(mlt_ctx *ctx, mlt_picture *pic) {
+  if (!ctx) return MLT_ERR_ARG;
+  if (!pic || !owns(ctx, pic)) { ctx->err = "mlt_picture_destroy: not a picture of this context"; return MLT_ERR_ARG; }
+  for (size_t i = 0; i < ctx->pictures.size(); ++i)
+    if (ctx->pictures[i] == pic) { ctx->pictures.erase(ctx->pictures.begin() + (long)i); break; }
+  release(ctx, pic);   // (every call that reads a picture has synchronised before it returned; hipFree waits for the device besides)
+  return MLT_OK;
+}
+
+int mlt_predict_at(mlt_ctx *ctx, int size, const mlt_picture *org, const mlt_picture *pred, int n, const int32_t *xy, const int32_t *poc, const int32_t *qp,
+                   int32_t *split_mode_opt, float *logits_opt, mlt_decision *dec_opt, mlt_candidates *cand_opt) {
+  if (!ctx) return MLT_ERR_ARG;
+  if (n < 0 || !org || !pred || (!split_mode_opt && !logits_opt && !dec_opt && !cand_opt) || (n > 0 && (!xy || !poc || !qp))) { ctx->err = "mlt_predict_at: bad argument"; return MLT_ERR_ARG; }
+  SizeState *st;
+  int rc = check_size(ctx, size, &st);
+  if (rc) return rc;
+  if (!owns(ctx, org) || !owns(ctx, pred)) { ctx->err = "mlt_predict_at: both pictures must belong to this context"; return MLT_ERR_ARG; }
+  if (org->width != pred->width || org->height != pred->height) { ctx->err = "mlt_predict_at: the two pictures differ in width or height"; return MLT_ERR_ARG; }
+  if (n == 0) return MLT_OK;
+  // every position, before anything is enqueued: the gather kernel trusts them
+  for (int i = 0; i < n; ++i) {
+    const long x = xy[2 * (size_t)i], y = xy[2 * (size_t)i + 1];
+    if (x < 0 || y < 0 || x + size > org->width || y + size > org->height) {
+      char msg[192];
+      std::snprintf(msg, sizeof msg, "mlt_predict_at: position %d (x = %ld, y = %ld) puts a %d x %d CU outside the %d x %d picture", i, x, y, size, size, org->width, org->height);
+      ctx->err = msg;
+      return MLT_ERR_ARG;
+    }
+  }
+  const AtOut out{split_mode_opt, logits_opt, dec_opt, cand_opt};
+  const int G = (int)org->plane.size();   // (both pictures belong to ctx: a plane per device of it)
+  if (G > 1 && n > 1) {
+    // multi-device context: contiguous shards, one host thread per further device, every device gathers from its own copy of the planes (predict_batch_impl)
+    const int nlg = st->model.n_logits, si = size_index(size);
+    std::vector<int> rcs((size_t)G, MLT_OK);
+    auto run = [&](int g) {
+      const int lo = shard_lo(n, g, G), hi = shard_lo(n, g + 1, G);
+      if (hi <= lo) return;
+      mlt_ctx *dev = device_of(ctx, g);
+      SizeState *sg = &dev->sz[si];
+      if (!sg->enabled || !sg->loaded) { dev->err = "CU size not enabled or weights not loaded"; rcs[(size_t)g] = MLT_ERR_SIZE_DISABLED; return; }
+      const AtOut o{out.split ? out.split + lo : nullptr, out.logits ? out.logits + (size_t)lo * nlg : nullptr, out.dec ? out.dec + lo : nullptr, out.cand ? out.cand + lo : nullptr};
+      rcs[(size_t)g] = predict_at_single(dev, sg, org->plane[(size_t)g], org->pitch, org->vec, pred->plane[(size_t)g], pred->pitch, pred->vec, hi - lo,
+                                         xy + 2 * (size_t)lo, poc + lo, qp + lo, o);
+    };
+    std::vector<std::thread> th;
+    for (int g = 1; g < G; ++g) th.emplace_back(run, g);
+    run(0);
+    for (std::thread &t : th) t.join();
+    for (int g = 0; g < G; ++g)
+      if (rcs[(size_t)g]) { if (g) ctx->err = "device " + std::to_string(device_of(ctx, g)->device) + ": " + device_of(ctx, g)->err; return rcs[(size_t)g]; }
+    return MLT_OK;
+  }
+  return predict_at_single(ctx, st, org->plane[0], org->pitch, org->vec, pred->plane[0], pred->pitch, pred->vec, n, xy, poc, qp, out);
+}
+
+int mlt_grid_positions(int width, int height, int size, int32_t *xy, int cap) {
+  if (size_index(size) < 0 || width < size || height < size) return 0;
+  const int cols = width / size, rows = height / size;
+  const long long total = (long long)cols * rows;
+  if (total > 0x7fffffff) return 0;
+  for (long long i = 0; xy && i < total && i < cap; ++i) {
+    xy[2 * i] = (int32_t)(i % cols) * size;
+    xy[2 * i + 1] = (int32_t)(i / cols) * size;
+  }
+  return (int)total;
+}
+
+#pragma GCC visibility pop
+}  // extern "C"

@@ -3,6 +3,7 @@
 //   mlt_guards.cpp     the parity guards: selection slots, the fast pass with the size's guards, the exact re-run of flagged CUs
 //   mlt_calibrate.cpp  model upload, calibration sets and session, the loader, mlt_load_weights / mlt_calibrate / mlt_arithmetic
 //   mlt_api.cpp        init / shutdown / stream, the predict entry points, deferred prediction, confidence gate, profile
+//   mlt_pictures.cpp   device-resident pictures: create / upload / wrap / destroy, mlt_predict_at, mlt_grid_positions
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -222,6 +223,19 @@ struct Deferred {
   int phase[2] = {0, 0};                    // which of the set's two selection counters (count[0 .. 1]) its next launch counts on (GuardSlot.phase)
 };
 
+// A device-resident picture (include/mltcnn.h: mlt_picture): one int16 luma plane per device of the context that owns it.  Library-owned planes are pitched to
+// a multiple of 64 elements (rows start on 128-byte lines; any multiple of 8 would do for the gather's argument) and allocated as height x pitch elements, so the
+// extent starts and ends on 16-byte boundaries and picture_gather_kernel may fetch 16-byte windows (mlt_picture_kernels.inc); a wrapped plane is the caller's
+// memory -- base, stride and the extent (height - 1) x stride + width as declared -- and takes the vector paths only when that extent happens to start and end so.
+struct mlt_picture {
+  mlt_ctx *owner = nullptr;
+  int width = 0, height = 0;
+  long pitch = 0;                  // elements
+  bool owned = false;              // allocated by mlt_picture_create (freed by mlt_picture_destroy / mlt_shutdown); false: mlt_picture_wrap_device
+  bool vec = false;                // extent starts and ends 16-byte aligned
+  std::vector<int16_t *> plane;    // [device index of the owner]: sample (0, 0)
+};
+
 struct ProfAcc { uint32_t launches = 0; double flops = 0, bytes = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; };
 
 struct mlt_ctx {
@@ -266,6 +280,7 @@ struct mlt_ctx {
   hipEvent_t ev_guard = nullptr;  // "count of flagged CUs has landed" (device-pointer entry)
   char *gstage = nullptr;
   size_t gstage_bytes = 0;
+  std::vector<mlt_picture *> pictures;  // every picture created on / wrapped for this context (mlt_pictures.cpp); what is left is released by mlt_shutdown
   std::string err;
   bool profile = false;
   bool guard_select_kernel = false;  // MLT_GUARD_SELECT_KERNEL (read at mlt_init, like MLT_CHUNK): the guards' selection of a BATCH as a launch of its own (round 5's form,
@@ -365,7 +380,15 @@ struct Launch {
   int prof_end(hipEvent_t e1);
 };
 
+// contiguous shard of n items for device g of G (fastintercu-vvc_amd/shard.py: shard_bounds)
+inline int shard_lo(int n, int g, int G) { return (int)(((long long)n * g) / G); }
+inline mlt_ctx *device_of(mlt_ctx *ctx, int i) { return i == 0 ? ctx : ctx->peers[(size_t)i - 1]; }
+
 // ---- functions that cross translation units ----
+// mlt_api.cpp
+int ensure_stage(mlt_ctx *ctx, size_t bytes);   // the context's staging for the host-array entry points holds at least `bytes`
+// mlt_pictures.cpp
+void free_pictures(mlt_ctx *ctx);               // mlt_shutdown: before the peers go
 // mlt_dispatch.cpp
 void release_ws(mlt_ctx *ctx);
 int run_network(mlt_ctx *ctx, SizeState &st, const NetCfg &c, int n, const PassIO &io, const GuardOut &go = GuardOut());

@@ -210,6 +210,38 @@ class SplitPredictor {
     return true;
   }
 
+  // Device-resident pictures (include/mltcnn.h: mlt_picture, mlt_predict_at) for callers that evaluate WHOLE frames -- a lookahead or pre-analysis pass, not the
+  // per-CU call of xCompressCU, which gains nothing measurable from them.  uploadPicture() copies one luma plane (Pel rows of `stride` elements)
+  // to the device; *pic == nullptr: the picture is created first (width x height), else it is reused for the next frame of the same geometry.  The pictures live
+  // until the predictor is destroyed.  false on failure.
+  bool uploadPicture(mlt_picture **pic, const Pel *plane, int stride, int width, int height) {
+    if (!m_ctx || !pic) return false;
+    if (!*pic && mlt_picture_create(m_ctx, width, height, pic) != MLT_OK) { *pic = nullptr; return false; }
+    return mlt_picture_upload(m_ctx, *pic, plane, stride) == MLT_OK;
+  }
+  // n CUs of cuw x cuw at xy[i] = {x, y} of the picture pair, one batch: splitModes[i] as predictSplitMode() returns it, and -- candOpt / decOpt != nullptr -- the
+  // candidate and decision records beside it.  false on failure: every split mode -1, every candidate record keeps all classes (full RDO), no prediction in the
+  // decision records.
+  bool predictAt(const mlt_picture *org, const mlt_picture *pred, int cuw, int n, const int32_t *xy, const int32_t *poc, const int32_t *cuQP, int32_t *splitModes,
+                 mlt_candidates *candOpt = nullptr, mlt_decision *decOpt = nullptr, float *logitsOpt = nullptr) {
+    Timer tm(this, 0, cuw);
+    if (!m_ctx || !splitModes || mlt_predict_at(m_ctx, cuw, org, pred, n, xy, poc, cuQP, splitModes, logitsOpt, decOpt, candOpt) != MLT_OK) {
+      std::fprintf(stderr, "error\n");  // EncCu.cpp:925
+      for (int i = 0; i < n; ++i) {
+        if (splitModes) splitModes[i] = -1;
+        if (candOpt) failCandidates(cuw, candOpt + i, decOpt ? decOpt + i : nullptr);
+        else if (decOpt) { decOpt[i] = mlt_decision{}; decOpt[i].split_mode = decOpt[i].raw_mode = -1; }
+      }
+      ++m_failed;
+      return false;
+    }
+    for (int i = 0; i < n; ++i) {
+      if (splitModes[i] < 0) ++m_gated;
+      if (candOpt) m_keptModes += (unsigned long long)candOpt[i].count;
+    }
+    return true;
+  }
+
   // The class indices a candidate record keeps, most probable first (classes[] holds up to 8); returns how many.
   static int keptClasses(const mlt_candidates &c, int classes[8]) {
     int n = 0;

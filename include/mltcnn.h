@@ -315,6 +315,44 @@ int mlt_predict_batch_device_candidates(mlt_ctx *ctx, int n, int size, const voi
                                         const void *d_poc, const void *d_qp, void *d_candidates, void *d_decisions_opt, void *d_logits);
 int mlt_wait_candidates(mlt_ctx *ctx, int size, mlt_ticket ticket, mlt_candidates *out, mlt_decision *dec_opt, float *logits_opt);
 
+/* ---- Device-resident pictures: predict CUs by position, gathered on the GPU (new exports; MLT_ABI_VERSION stays 4) ----
+ * Every entry point above takes CUT-OUT CUs.  A caller that evaluates whole pictures (lookahead / pre-analysis, a sweep of a gate or candidate policy over real
+ * sequences, frames that already sit in HBM) keeps the two luma planes on the device instead -- the original and the prediction, one mlt_picture each -- and names
+ * CUs by the position of their top-left luma sample: one upload per frame serves every CU size, and a device kernel (picture_gather) cuts the CUs out into the dense
+ * planes the batch path consumes.  The network kernels are the batch path's: every result is bit-identical to mlt_predict_batch* on the same CUs, whatever the
+ * positions' alignment (the gathered planes are always aligned, so they always run the quad-fetching kernels).  The encoder's per-CU call gains nothing measurable from
+ * pictures.
+ * Geometry: 16 <= width, height <= 16384, else MLT_ERR_ARG.  A picture belongs to the context it was made on (for a single device of a multi-device context: the one
+ * mlt_device_ctx returns) and every call below takes that context. */
+typedef struct mlt_picture mlt_picture;   /* opaque; one int16 (Pel) luma plane in device memory, owned by a context */
+
+/* Allocates the plane on EVERY device of a multi-device context (content undefined until the first upload).  Freed by mlt_picture_destroy or mlt_shutdown. */
+int mlt_picture_create(mlt_ctx *ctx, int width, int height, mlt_picture **out);
+/* Host -> device, height rows of width Pels, `stride` >= width in elements; a picture made by mlt_picture_create only.  Copies on each device's context stream (with
+ * mlt_set_stream: the caller's) and returns once the host buffer may be reused.  May be called again on the same picture (the next frame, same geometry) without
+ * reallocation; a later mlt_predict_at on the same context sees the new content (stream order). */
+int mlt_picture_upload(mlt_ctx *ctx, mlt_picture *pic, const int16_t *plane, int stride);
+/* A plane the caller already holds in DEVICE memory: no copy, the caller keeps ownership (mlt_picture_destroy / mlt_shutdown release the handle only) and orders its own
+ * writes before the calls that read it.  Any base address with 2-byte alignment and any stride >= width; the declared extent is (height - 1) * stride + width elements
+ * from d_plane and no byte outside it is ever read.  Single-device contexts only: MLT_ERR_ARG on a context with peers (use mlt_device_ctx(ctx, i)). */
+int mlt_picture_wrap_device(mlt_ctx *ctx, const void *d_plane, int stride, int width, int height, mlt_picture **out);
+int mlt_picture_destroy(mlt_ctx *ctx, mlt_picture *pic);
+
+/* n CUs of size x size at xy[i] = {x, y} (top-left luma sample) of the picture pair; xy / poc / qp and the outputs are HOST arrays, synchronous like mlt_predict_batch.
+ * Outputs as on the batch twins: split modes, logits (n x mlt_num_logits(size)), decision records, candidate records -- at least one of them non-NULL, else MLT_ERR_ARG.
+ * Both pictures must belong to ctx and have equal width and height (else MLT_ERR_ARG); the size must be loaded (else MLT_ERR_SIZE_DISABLED).  Every position must
+ * satisfy 0 <= x, x + size <= width, 0 <= y, y + size <= height: ALL positions are checked on the host BEFORE anything is enqueued; on a violation the call returns
+ * MLT_ERR_ARG, leaves the outputs untouched and names the offending index through mlt_last_error.  Any x / y is accepted, not only multiples of the size, and so are
+ * overlapping and duplicate positions.  n == 0 returns MLT_OK.  Confidence gate, candidate policy and all three guards apply exactly as on mlt_predict_batch* of that
+ * size.  Processed in chunks of the context's pass size (4096 CUs); on a multi-device context in contiguous shards, one host thread per device. */
+int mlt_predict_at(mlt_ctx *ctx, int size, const mlt_picture *org, const mlt_picture *pred, int n, const int32_t *xy, const int32_t *poc, const int32_t *qp,
+                   int32_t *split_mode_opt, float *logits_opt, mlt_decision *dec_opt, mlt_candidates *cand_opt);
+
+/* Pure host, no context: the COMPLETE CUs of the size-aligned grid in raster order -- (width / size) * (height / size) positions; the partial CUs at the right and
+ * bottom border are left out (VTM splits them implicitly).  Returns the total count and writes min(count, cap) entries of {x, y} to xy; xy == NULL with cap == 0 is
+ * the size query.  0 for an unsupported size or a picture smaller than the size. */
+int mlt_grid_positions(int width, int height, int size, int32_t *xy, int cap);
+
 int mlt_synchronize(mlt_ctx *ctx);
 
 /* Use an existing hipStream_t (e.g. the caller's) instead of the context's own stream; NULL switches back to a

@@ -1,0 +1,136 @@
+#!/usr/bin/env python3
+"""Split-prior maps of a whole picture: every complete CU of the size-aligned grid, every loaded CU size, from two device-resident planes.
+
+Reads the original and the prediction luma of one frame -- `.npy` int16 [height, width], or raw 16-bit little-endian luma (e.g. the first plane of a
+10-bit 4:0:0 / 4:2:0 .yuv) with --width / --height -- uploads each ONCE (MltCnn.picture), runs grid_positions + predict_at for every requested size
+and writes per size `<out>_<S>_split.npy` (int32, -1 where the confidence gate withholds), `<out>_<S>_confidence.npy` (float32) and
+`<out>_<S>_mask.npy` (uint32 candidate mask), each shaped [height // S, width // S]; prints the class histogram of the decision head.
+
+  python tools/picture_map.py org.npy pred.npy --weights-dir DIR --sizes 128,64 --poc 8 --qp 32 --out maps/frame8
+  python tools/picture_map.py org.yuv pred.yuv --width 1920 --height 1080 --synthetic 10 --coverage 0.9 --out /tmp/f
+
+File reading and grid logic (read_picture, grid, to_map, histogram) need neither a device nor the library; run_maps needs the MI355X."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SIZES = (128, 64, 32, 16)
+
+
+def read_picture(path: str, width: int | None = None, height: int | None = None) -> np.ndarray:
+    """-> int16 [height, width], C-contiguous.  `.npy`: a 2-D int16 array (width / height, if given, must match).  Anything else: raw 16-bit little-endian
+    samples, the first width x height of the file (the luma plane of its first frame)."""
+    if path.endswith(".npy"):
+        a = np.load(path)
+        if a.ndim != 2 or a.dtype != np.int16:
+            raise ValueError(f"{path}: want a 2-D int16 array, got {a.dtype} {a.shape}")
+        if (width and a.shape[1] != width) or (height and a.shape[0] != height):
+            raise ValueError(f"{path}: {a.shape[1]}x{a.shape[0]}, not the {width}x{height} asked for")
+        return np.ascontiguousarray(a)
+    if not width or not height:
+        raise ValueError(f"{path}: a raw file needs --width and --height")
+    count = width * height
+    a = np.fromfile(path, dtype="<u2", count=count)
+    if a.size != count:
+        raise ValueError(f"{path}: a {width}x{height} plane needs {count} samples of 16 bits, the file holds {a.size}")
+    if a.max(initial=0) > 0x7FFF:
+        raise ValueError(f"{path}: samples above 32767 do not fit a Pel (int16)")
+    return a.astype(np.int16).reshape(height, width)
+
+
+def grid(width: int, height: int, size: int) -> np.ndarray:
+    """[count, 2] int32 {x, y}: the complete CUs of the size-aligned grid, raster order -- what capi.grid_positions returns, in numpy (partial CUs at
+    the right and bottom border are left out: VTM splits them implicitly)."""
+    if size not in SIZES or width < size or height < size:
+        return np.zeros((0, 2), np.int32)
+    ys, xs = np.meshgrid(np.arange(height // size, dtype=np.int32) * size, np.arange(width // size, dtype=np.int32) * size, indexing="ij")
+    return np.stack([xs.ravel(), ys.ravel()], axis=1).astype(np.int32)
+
+
+def to_map(values: np.ndarray, width: int, height: int, size: int) -> np.ndarray:
+    """Per-CU values in grid (raster) order -> [height // size, width // size]."""
+    return np.asarray(values).reshape(height // size, width // size)
+
+
+def histogram(split: np.ndarray, classes: int) -> dict:
+    """{class: count} of the split map, -1 (withheld by the confidence gate) included when present."""
+    h = {k: int((split == k).sum()) for k in range(classes)}
+    if (split < 0).any():
+        h[-1] = int((split < 0).sum())
+    return h
+
+
+def run_maps(m, org: np.ndarray, pred: np.ndarray, sizes, poc: int, qp: int) -> dict:
+    """m: an MltCnn with `sizes` loaded.  -> {size: {"xy", "split", "confidence", "mask"}} with the three maps shaped [height // size, width // size]."""
+    from fastintercu_vvc_amd import capi
+    assert org.shape == pred.shape
+    height, width = org.shape
+    p_org, p_pred = m.picture(width, height).upload(org), m.picture(width, height).upload(pred)
+    out = {}
+    try:
+        for size in sizes:
+            xy = capi.grid_positions(width, height, size)
+            if not len(xy):
+                continue
+            n = len(xy)
+            r = m.predict_at(size, p_org, p_pred, xy, np.full(n, poc, np.int32), np.full(n, qp, np.int32), want=("decisions", "candidates"))
+            out[size] = {"xy": xy, "split": to_map(r["decisions"]["split_mode"], width, height, size),
+                         "confidence": to_map(r["decisions"]["confidence"], width, height, size), "mask": to_map(r["candidates"]["mask"], width, height, size)}
+    finally:
+        p_org.close()
+        p_pred.close()
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("org")
+    ap.add_argument("pred")
+    ap.add_argument("--width", type=int)
+    ap.add_argument("--height", type=int)
+    ap.add_argument("--sizes", default="128", help="comma-separated CU sizes")
+    ap.add_argument("--weights-dir", help="directory with MLTORPQ_splitMode_<S>.mltw (tools/convert_weights.py)")
+    ap.add_argument("--synthetic", type=int, help="seeded synthetic weights instead of --weights-dir")
+    ap.add_argument("--poc", type=int, default=0)
+    ap.add_argument("--qp", type=int, default=32)
+    ap.add_argument("--min-conf", type=float, default=0.0, help="confidence gate")
+    ap.add_argument("--coverage", type=float, default=0.0, help="candidate policy: coverage")
+    ap.add_argument("--max-modes", type=int, default=0, help="candidate policy: cap")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--out", required=True, help="prefix of the .npy maps")
+    args = ap.parse_args(argv)
+    sizes = tuple(int(s) for s in args.sizes.split(",") if s)
+    if not sizes or any(s not in SIZES for s in sizes) or (args.weights_dir is None) == (args.synthetic is None):
+        ap.error("--sizes from 128,64,32,16 and exactly one of --weights-dir / --synthetic")
+    org = read_picture(args.org, args.width, args.height)
+    pred = read_picture(args.pred, org.shape[1], org.shape[0])
+    import mltcnn_pkg
+    pkg = mltcnn_pkg.load()
+    blobs = None
+    if args.synthetic is not None:
+        blobs = {s: pkg.weights.synthetic_blob(pkg.synth.ARCH_CTU if s == 128 else pkg.synth.ARCH_CU, args.synthetic) for s in sizes}
+    m = pkg.MltCnn(device=args.device, sizes=sizes, weights_dir=args.weights_dir, blobs=blobs)
+    for s in sizes:
+        if args.min_conf > 0:
+            m.set_confidence_gate(s, args.min_conf)
+        if args.coverage > 0 or args.max_modes > 0:
+            m.set_candidate_policy(s, args.coverage, args.max_modes)
+    maps = run_maps(m, org, pred, sizes, args.poc, args.qp)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    for s, r in maps.items():
+        for name in ("split", "confidence", "mask"):
+            np.save(f"{args.out}_{s}_{name}.npy", r[name])
+        classes = pkg.decisions.HEAD_CLASSES[s][pkg.decisions.default_head(s)]
+        hist = " ".join(f"{k}:{v}" for k, v in sorted(histogram(r["split"], classes).items()))
+        print(f"size {s}: {r['split'].size} CUs ({r['split'].shape[1]} x {r['split'].shape[0]})  split histogram  {hist}  mean confidence {float(r['confidence'].mean()):.4f}")
+    m.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
