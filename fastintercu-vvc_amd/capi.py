@@ -32,7 +32,9 @@ EXPORTS = ["mlt_abi_version", "mlt_build_signature", "mlt_init", "mlt_num_device
            "mlt_wait_decision",
            "mlt_set_candidate_policy", "mlt_get_candidate_policy", "mlt_predict_candidates", "mlt_predict_batch_candidates",
            "mlt_predict_batch_device_candidates", "mlt_wait_candidates",
-           "mlt_picture_create", "mlt_picture_upload", "mlt_picture_wrap_device", "mlt_picture_destroy", "mlt_predict_at", "mlt_grid_positions"]
+           "mlt_picture_create", "mlt_picture_upload", "mlt_picture_wrap_device", "mlt_picture_destroy", "mlt_predict_at", "mlt_grid_positions",
+           "mlt_tree_max_nodes", "mlt_tree_roots", "mlt_predict_tree"]
+TREE_BY_CANDIDATES = 0x1  # mlt_tree_config.flags: descend on cand_mask & descend_mask instead of on split_mode
 
 
 class MltConfig(C.Structure):
@@ -67,6 +69,18 @@ class MltCandidates(C.Structure):
 
 
 CANDIDATES_DTYPE = np.dtype([("mask", "<u4"), ("count", "<i4"), ("order", "i1", (8,)), ("prob", "<f4", (6,))])
+
+
+class MltTreeConfig(C.Structure):
+    """`struct mlt_tree_config` (include/mltcnn.h): 40 bytes."""
+    _fields_ = [("struct_size", C.c_uint32), ("top_size", C.c_int32), ("min_size", C.c_int32), ("descend_mask", C.c_uint32 * 4), ("flags", C.c_uint32),
+                ("poc", C.c_int32), ("qp", C.c_int32)]
+
+
+# `struct mlt_tree_node` (include/mltcnn.h): 32 bytes, no padding
+TREE_NODE_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("size", "<i2"), ("depth", "i1"), ("flags", "u1"), ("parent", "<i4"), ("first_child", "<i4"),
+                            ("split_mode", "<i4"), ("confidence", "<f4"), ("cand_mask", "<u4")])
+assert TREE_NODE_DTYPE.itemsize == 32
 
 
 class MltKernelTime(C.Structure):
@@ -139,6 +153,9 @@ def load_library():
     lib.mlt_picture_destroy.argtypes = [vp, vp]
     lib.mlt_predict_at.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.mlt_grid_positions.argtypes = [i32, i32, i32, vp, i32]
+    lib.mlt_tree_max_nodes.argtypes = [i32, i32, i32, i32]
+    lib.mlt_tree_roots.argtypes = [i32, i32, i32, i32, vp, i32]
+    lib.mlt_predict_tree.argtypes = [vp, vp, vp, C.POINTER(MltTreeConfig), vp, i32, C.POINTER(i32), vp, vp, i32, vp, vp]
     lib.mlt_synchronize.argtypes = [vp]
     lib.mlt_set_stream.argtypes = [vp, vp]
     lib.mlt_alloc_pinned.restype = vp
@@ -162,6 +179,21 @@ def grid_positions(width: int, height: int, size: int) -> np.ndarray:
     xy = np.zeros((count, 2), np.int32)
     if count:
         assert lib.mlt_grid_positions(int(width), int(height), int(size), xy.ctypes.data, count) == count
+    return xy
+
+
+def tree_max_nodes(width: int, height: int, top: int = 128, min_size: int = 16) -> int:
+    """Node count of a tree that descends everywhere: the capacity mlt_predict_tree asks for (mlt_tree_max_nodes; pure host, 0 on bad arguments)."""
+    return load_library().mlt_tree_max_nodes(int(width), int(height), int(top), int(min_size))
+
+
+def tree_roots(width: int, height: int, top: int, size: int) -> np.ndarray:
+    """[count, 2] int32 {x, y}: the roots of level `size` of a tree whose top level is `top`, raster order (mlt_tree_roots; pure host)."""
+    lib = load_library()
+    count = lib.mlt_tree_roots(int(width), int(height), int(top), int(size), None, 0)
+    xy = np.zeros((count, 2), np.int32)
+    if count:
+        assert lib.mlt_tree_roots(int(width), int(height), int(top), int(size), xy.ctypes.data, count) == count
     return xy
 
 
@@ -460,6 +492,40 @@ class MltCnn:
         ptr = lambda k: out[k].ctypes.data if k in out else None
         self._check(self._lib.mlt_predict_at(self._h, int(size), org_pic._h, pred_pic._h, n, xy.ctypes.data, poc.ctypes.data, qp.ctypes.data,
                                              ptr("split"), ptr("logits"), ptr("decisions"), ptr("candidates")))
+        return out
+
+    def predict_tree(self, org_pic: Picture, pred_pic: Picture, poc: int, qp: int, top: int = 128, min_size: int = 16, descend: dict | None = None,
+                     by_candidates: bool = False, want=("leaf_map",)) -> dict:
+        """The partition tree of the picture pair (mlt_predict_tree): quadtree descent on the device from `top` down to `min_size`.
+        descend: {size: mask of the decision head's classes that mean "quad split"} (default 1 << 1 everywhere).
+        -> {"nodes": TREE_NODE_DTYPE [n] in the contract's order} + for the names in `want`: "leaf_map" uint8 [height // 16, width // 16],
+        "logits" float32 [n, 15] (a 128 node fills the first 9 of its row, the rest stays 0), "decisions", "candidates" (one record per node)."""
+        assert set(want) <= {"leaf_map", "logits", "decisions", "candidates"}
+        cfg = MltTreeConfig()
+        cfg.struct_size = C.sizeof(MltTreeConfig)
+        cfg.top_size, cfg.min_size, cfg.poc, cfg.qp = int(top), int(min_size), int(poc), int(qp)
+        cfg.flags = TREE_BY_CANDIDATES if by_candidates else 0
+        for i, s in enumerate((128, 64, 32, 16)):
+            cfg.descend_mask[i] = int((descend or {}).get(s, 0))
+        cap = tree_max_nodes(org_pic.width, org_pic.height, top, min_size)
+        nodes = np.zeros((max(cap, 1),), TREE_NODE_DTYPE)
+        out = {}
+        if "leaf_map" in want:
+            out["leaf_map"] = np.zeros((org_pic.height // 16, org_pic.width // 16), np.uint8)
+        if "logits" in want:
+            out["logits"] = np.zeros((max(cap, 1), 15), np.float32)
+        if "decisions" in want:
+            out["decisions"] = np.zeros((max(cap, 1),), DECISION_DTYPE)
+        if "candidates" in want:
+            out["candidates"] = np.zeros((max(cap, 1),), CANDIDATES_DTYPE)
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        n = C.c_int(0)
+        self._check(self._lib.mlt_predict_tree(self._h, org_pic._h, pred_pic._h, C.byref(cfg), nodes.ctypes.data, cap, C.byref(n), ptr("leaf_map"),
+                                               ptr("logits"), 15, ptr("decisions"), ptr("candidates")))
+        out["nodes"] = nodes[:n.value].copy()
+        for k in ("logits", "decisions", "candidates"):
+            if k in out:
+                out[k] = out[k][:n.value].copy()
         return out
 
     def synchronize(self):

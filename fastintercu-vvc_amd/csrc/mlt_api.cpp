@@ -199,6 +199,7 @@ void mlt_shutdown(mlt_ctx *ctx) {
   if (ctx->stage) (void)hipFree(ctx->stage);
   if (ctx->guard_dev) (void)hipFree(ctx->guard_dev);
   if (ctx->gstage) (void)hipFree(ctx->gstage);
+  free_tree(ctx);
   if (ctx->guard_host) (void)hipHostFree(ctx->guard_host);
   if (ctx->ev_guard) (void)hipEventDestroy(ctx->ev_guard);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -296,6 +296,42 @@ struct PictureGatherArgs {
   int vec_org, vec_pred;       // the plane's extent starts and ends on 16-byte boundaries: aligned 16-byte loads may be used (else 2-byte loads only)
 };
 hipError_t mlt_launch_picture_gather(const PictureGatherArgs &a, hipStream_t st);
+// ---- partition trees (mlt_predict_tree): the quadtree descent between two network levels (mlt_tree_kernels.inc) ----
+// A node of the tree (include/mltcnn.h: mlt_tree_node -- same 32 bytes; mlt_runtime.h asserts the layout).
+struct TreeNodeRec {
+  int32_t x, y;
+  int16_t size;
+  int8_t depth;
+  uint8_t flags;
+  int32_t parent, first_child, split_mode;
+  float confidence;
+  uint32_t cand_mask;
+};
+struct TreeExpandArgs {
+  TreeNodeRec *nodes;          // every node of the tree, in the contract's order; node_cap entries
+  int32_t *xy;                 // [node_cap][2]: the nodes' positions -- a level's slice is the position list its network pass gathers from
+  int node_cap;
+  int lvl_start, lvl_n;        // the level just evaluated: nodes [lvl_start, lvl_start + lvl_n); lvl_n == 0 with size = 2 x top_size, depth = -1 opens the tree
+  int size, depth;             // its CU size and depth; the next level's are size / 2 and depth + 1
+  const DecisionRec *dec;      // [lvl_n] the level's decision records
+  const CandRec *cand;         // [lvl_n] its candidate records, or NULL: cand_mask = 1 << raw_mode, every class when a logit of the decision head is NaN
+  const float *logits;         // [lvl_n][n_logits] (read only when cand == NULL)
+  int n_logits, head_off, head_classes;   // the decision head inside a row of logits
+  uint32_t descend_mask;       // classes of the decision head that mean "quad split"; 0: the level never descends (min_size)
+  int by_candidates;           // descend on cand_mask & descend_mask instead of on split_mode
+  const int32_t *next_roots;   // [n_next_roots][2] the next level's roots, raster order
+  int n_next_roots, root_flags;   // root_flags: their mlt_tree_node.flags (bit 0 below top_size)
+  int32_t *count;              // [1] out: the next level's node count = n_next_roots + 4 x descending parents (NULL: not wanted)
+};
+struct TreeRasterArgs {
+  const TreeNodeRec *nodes;
+  int lvl_start, lvl_n;
+  int blk_l;                   // log2(size / 16): a node covers (1 << blk_l)^2 map bytes
+  uint8_t *map;                // [map_h][map_w], one byte per 16 x 16 block
+  int map_w, map_h;
+};
+hipError_t mlt_launch_tree_expand(const TreeExpandArgs &a, hipStream_t st);
+hipError_t mlt_launch_tree_raster(const TreeRasterArgs &a, hipStream_t st);
 hipError_t mlt_launch_flat_stat(const FlatStatArgs &a, bool aligned8, hipStream_t st);
 hipError_t mlt_launch_guard_select(const GuardSelectArgs &a, hipStream_t st);
 hipError_t mlt_launch_guard_gather(const GuardGatherArgs &a, hipStream_t st);

@@ -281,6 +281,7 @@ template <int Q, class ACC = float16v> __device__ __forceinline__ half4 act_quad
 #include "mlt_layer1_kernel.inc"  // layer1_stream_kernel
 #include "mlt_tail_kernels.inc"   // heads_kernel, flat_stat / guard kernels
 #include "mlt_picture_kernels.inc"  // picture_gather_kernel
+#include "mlt_tree_kernels.inc"  // tree_expand_kernel, tree_raster_kernel
 
 // ---------------------------------------------------------------------------------------------
 // launchers
@@ -853,5 +854,20 @@ hipError_t mlt_launch_picture_gather(const PictureGatherArgs &a, hipStream_t st)
   const size_t items = (size_t)a.c << (2 * a.s_l - 2);   // two planes x c x S x S / 8
   const size_t want = (items + 255) / 256;
   hipLaunchKernelGGL(picture_gather_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// ONE workgroup: the ordered compaction carries its running base from tile to tile (mlt_tree_kernels.inc)
+hipError_t mlt_launch_tree_expand(const TreeExpandArgs &a, hipStream_t st) {
+  hipLaunchKernelGGL(tree_expand_kernel, dim3(1), dim3(MLT_TREE_TILE), 0, st, a);
+  return hipGetLastError();
+}
+
+// flat grid-stride launch over the 16 x 16 blocks of the level's nodes
+hipError_t mlt_launch_tree_raster(const TreeRasterArgs &a, hipStream_t st) {
+  const size_t items = (size_t)a.lvl_n << (2 * a.blk_l);
+  if (!items) return hipSuccess;
+  const size_t want = (items + 255) / 256;
+  hipLaunchKernelGGL(tree_raster_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
   return hipGetLastError();
 }

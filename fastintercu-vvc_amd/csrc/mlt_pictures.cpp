@@ -3,6 +3,7 @@
 // A picture is a pitched int16 luma plane per device of its context.  mlt_predict_at validates the positions on the host, then per chunk: positions + poc + qp H2D,
 // picture_gather_kernel (mlt_picture_kernels.inc) -> the dense [c][S][S] planes of a staging set, run_checked on those planes -- the launches, guards and exact
 // re-runs of mlt_predict_batch_device, so every result is the dense path's bit for bit -- results D2H.  The network kernels know nothing about pictures.
+// predict_at_chunks is that per-chunk pass; mlt_predict_tree (mlt_tree.cpp) runs it on position lists that already live on the device.
 #include "mlt_runtime.h"
 
 namespace {
@@ -22,28 +23,36 @@ void release(mlt_ctx *ctx, mlt_picture *pic) {
   delete pic;
 }
 
-struct AtOut { int32_t *split; float *logits; mlt_decision *dec; mlt_candidates *cand; };
+}  // namespace
 
-// one device: CUs [0, n) of xy / poc / qp from the planes this device holds (dev: the device's own context)
-int predict_at_single(mlt_ctx *dev, SizeState *st, const int16_t *d_org, long org_pitch, bool org_vec, const int16_t *d_pred, long pred_pitch, bool pred_vec, int n,
-                      const int32_t *xy, const int32_t *poc, const int32_t *qp, const AtOut &out) {
+// One device: CUs [0, n) of a position list from the planes this device holds (dev: the device's own context), in chunks of the pass size.  Host lists
+// (mlt_predict_at): positions, poc and qp go H2D per chunk and the results D2H.  Device lists (mlt_predict_tree: at.device): the gather reads the positions where
+// they are, every CU takes (poc_all, qp_all) and the network writes logits and records straight into the caller's device arrays (every store to them is a
+// 4-byte or a struct store: no alignment beyond the arrays' own is assumed) -- the launches in between are the same, so are the results.
+int predict_at_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &pl, int n, const AtList &at, const AtOut &out) {
   if (hipSetDevice(dev->device) != hipSuccess) { dev->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
   const int size = st->size, nl = st->model.n_logits;
-  if (out.cand) st->cand_used = true;
+  if (out.cand && !at.device) st->cand_used = true;
   const int cap = n < dev->chunk ? n : dev->chunk;
-  const StageSet lay(size, cap, nl, out.dec != nullptr, out.cand != nullptr);
+  const StageSet lay(size, cap, nl, out.dec != nullptr && !at.device, out.cand != nullptr && !at.device);
   int rc;
-  if ((rc = ensure_stage(dev, lay.bytes() + StageSet::up256((size_t)cap * 8)))) return rc;   // the set, then the chunk's positions
+  if ((rc = ensure_stage(dev, lay.bytes() + (at.device ? 0 : StageSet::up256((size_t)cap * 8))))) return rc;   // the set, then the chunk's positions
   const StageSet::Ptrs S = lay.at(dev->stage);
   int32_t *d_xy = (int32_t *)(dev->stage + lay.bytes());
+  if (at.device) {   // one (poc, qp) pair: filled once, every chunk reads its first c entries
+    HIP_TRY(dev, hipMemsetD32Async((hipDeviceptr_t)S.d_poc, at.poc_all, (size_t)cap, dev->stream));
+    HIP_TRY(dev, hipMemsetD32Async((hipDeviceptr_t)S.d_qp, at.qp_all, (size_t)cap, dev->stream));
+  }
   for (int i0 = 0; i0 < n; i0 += cap) {
     const int c = n - i0 < cap ? n - i0 : cap;
-    HIP_TRY(dev, hipMemcpyAsync(d_xy, xy + 2 * (size_t)i0, (size_t)c * 8, hipMemcpyHostToDevice, dev->stream));
-    HIP_TRY(dev, hipMemcpyAsync(S.d_poc, poc + i0, (size_t)c * 4, hipMemcpyHostToDevice, dev->stream));
-    HIP_TRY(dev, hipMemcpyAsync(S.d_qp, qp + i0, (size_t)c * 4, hipMemcpyHostToDevice, dev->stream));
+    if (!at.device) {
+      HIP_TRY(dev, hipMemcpyAsync(d_xy, at.xy + 2 * (size_t)i0, (size_t)c * 8, hipMemcpyHostToDevice, dev->stream));
+      HIP_TRY(dev, hipMemcpyAsync(S.d_poc, at.poc + i0, (size_t)c * 4, hipMemcpyHostToDevice, dev->stream));
+      HIP_TRY(dev, hipMemcpyAsync(S.d_qp, at.qp + i0, (size_t)c * 4, hipMemcpyHostToDevice, dev->stream));
+    }
     PictureGatherArgs ga{};
-    ga.org = d_org; ga.pred = d_pred; ga.org_pitch = org_pitch; ga.pred_pitch = pred_pitch; ga.vec_org = org_vec; ga.vec_pred = pred_vec;
-    ga.xy = d_xy; ga.g_org = S.d_org; ga.g_pred = S.d_pred; ga.c = c; ga.s_l = ilog2(size);
+    ga.org = pl.org; ga.pred = pl.pred; ga.org_pitch = pl.org_pitch; ga.pred_pitch = pl.pred_pitch; ga.vec_org = pl.org_vec; ga.vec_pred = pl.pred_vec;
+    ga.xy = at.device ? at.xy + 2 * (size_t)i0 : d_xy; ga.g_org = S.d_org; ga.g_pred = S.d_pred; ga.c = c; ga.s_l = ilog2(size);
     Launch L{dev};
     hipEvent_t e0 = nullptr, e1 = nullptr;
     // algorithmic bytes: both planes of every CU read once and written once
@@ -51,6 +60,12 @@ int predict_at_single(mlt_ctx *dev, SizeState *st, const int16_t *d_org, long or
     LAUNCH_TRY(dev, mlt_launch_picture_gather(ga, dev->stream));
     if ((rc = L.prof_end(e1))) return rc;
     // (the guards and their exact re-run read the gathered planes; the staging pointers are 256-byte aligned: CLS_QUADS whatever the picture's alignment)
+    if (at.device) {
+      const PassIO io{Planes::dense(S.d_org, S.d_pred, size), S.d_poc, S.d_qp, out.split ? out.split + i0 : S.d_split, out.logits ? out.logits + (size_t)i0 * nl : nullptr,
+                      out.dec ? (DecisionRec *)out.dec + i0 : nullptr, out.cand ? (CandRec *)out.cand + i0 : nullptr};
+      if ((rc = run_checked(dev, *st, c, io))) return rc;
+      continue;   // (the stream orders this chunk's reads of the staged planes before the next chunk's gather)
+    }
     const PassIO io{Planes::dense(S.d_org, S.d_pred, size), S.d_poc, S.d_qp, S.d_split, out.logits ? S.d_lg : nullptr, S.d_dec, S.d_cand};
     if ((rc = run_checked(dev, *st, c, io))) return rc;
     if (out.split) HIP_TRY(dev, hipMemcpyAsync(out.split + i0, S.d_split, (size_t)c * 4, hipMemcpyDeviceToHost, dev->stream));
@@ -62,7 +77,7 @@ int predict_at_single(mlt_ctx *dev, SizeState *st, const int16_t *d_org, long or
   return MLT_OK;
 }
 
-}  // namespace
+bool owns_picture(const mlt_ctx *ctx, const mlt_picture *pic) { return owns(ctx, pic); }
 
 void free_pictures(mlt_ctx *ctx) {
   for (mlt_picture *p : ctx->pictures) release(ctx, p);
@@ -176,8 +191,7 @@ int mlt_predict_at(mlt_ctx *ctx, int size, const mlt_picture *org, const mlt_pic
       SizeState *sg = &dev->sz[si];
       if (!sg->enabled || !sg->loaded) { dev->err = "CU size not enabled or weights not loaded"; rcs[(size_t)g] = MLT_ERR_SIZE_DISABLED; return; }
       const AtOut o{out.split ? out.split + lo : nullptr, out.logits ? out.logits + (size_t)lo * nlg : nullptr, out.dec ? out.dec + lo : nullptr, out.cand ? out.cand + lo : nullptr};
-      rcs[(size_t)g] = predict_at_single(dev, sg, org->plane[(size_t)g], org->pitch, org->vec, pred->plane[(size_t)g], pred->pitch, pred->vec, hi - lo,
-                                         xy + 2 * (size_t)lo, poc + lo, qp + lo, o);
+      rcs[(size_t)g] = predict_at_chunks(dev, sg, AtPlanes::of(org, pred, g), hi - lo, AtList::host(xy + 2 * (size_t)lo, poc + lo, qp + lo), o);
     };
     std::vector<std::thread> th;
     for (int g = 1; g < G; ++g) th.emplace_back(run, g);
@@ -187,7 +201,7 @@ int mlt_predict_at(mlt_ctx *ctx, int size, const mlt_picture *org, const mlt_pic
       if (rcs[(size_t)g]) { if (g) ctx->err = "device " + std::to_string(device_of(ctx, g)->device) + ": " + device_of(ctx, g)->err; return rcs[(size_t)g]; }
     return MLT_OK;
   }
-  return predict_at_single(ctx, st, org->plane[0], org->pitch, org->vec, pred->plane[0], pred->pitch, pred->vec, n, xy, poc, qp, out);
+  return predict_at_chunks(ctx, st, AtPlanes::of(org, pred, 0), n, AtList::host(xy, poc, qp), out);
 }
 
 int mlt_grid_positions(int width, int height, int size, int32_t *xy, int cap) {

@@ -4,6 +4,7 @@
 //   mlt_calibrate.cpp  model upload, calibration sets and session, the loader, mlt_load_weights / mlt_calibrate / mlt_arithmetic
 //   mlt_api.cpp        init / shutdown / stream, the predict entry points, deferred prediction, confidence gate, profile
 //   mlt_pictures.cpp   device-resident pictures: create / upload / wrap / destroy, mlt_predict_at, mlt_grid_positions
+//   mlt_tree.cpp       partition trees of a picture: mlt_predict_tree, mlt_tree_roots, mlt_tree_max_nodes
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -280,6 +281,10 @@ struct mlt_ctx {
   hipEvent_t ev_guard = nullptr;  // "count of flagged CUs has landed" (device-pointer entry)
   char *gstage = nullptr;
   size_t gstage_bytes = 0;
+  // mlt_predict_tree's device arena (grow-only: nodes, positions, per-node logits and records, roots, leaf map, count) and its pinned count
+  char *tree_dev = nullptr;
+  size_t tree_bytes = 0;
+  int32_t *tree_host = nullptr;
   std::vector<mlt_picture *> pictures;  // every picture created on / wrapped for this context (mlt_pictures.cpp); what is left is released by mlt_shutdown
   std::string err;
   bool profile = false;
@@ -299,6 +304,10 @@ struct mlt_ctx {
 static_assert(sizeof(mlt_decision) == 48 && sizeof(DecisionRec) == sizeof(mlt_decision), "mlt_decision is 48 bytes");
 static_assert(offsetof(mlt_decision, confidence) == offsetof(DecisionRec, confidence) && offsetof(mlt_decision, level_mode) == offsetof(DecisionRec, level_mode) &&
               offsetof(mlt_decision, level_conf) == offsetof(DecisionRec, level_conf) && offsetof(mlt_decision, level_conf) == 32, "mlt_decision layout");
+
+static_assert(sizeof(mlt_tree_node) == 32 && sizeof(TreeNodeRec) == 32 && offsetof(mlt_tree_node, size) == offsetof(TreeNodeRec, size) && offsetof(mlt_tree_node, parent) == 12 &&
+              offsetof(TreeNodeRec, parent) == 12 && offsetof(mlt_tree_node, cand_mask) == offsetof(TreeNodeRec, cand_mask) && offsetof(mlt_tree_node, cand_mask) == 28, "mlt_tree_node layout");
+static_assert(sizeof(mlt_tree_config) == 40, "mlt_tree_config is 40 bytes");
 
 static_assert(sizeof(mlt_candidates) == 40 && sizeof(CandRec) == sizeof(mlt_candidates) && offsetof(mlt_candidates, order) == offsetof(CandRec, order) &&
               offsetof(mlt_candidates, prob) == offsetof(CandRec, prob) && offsetof(mlt_candidates, prob) == 16, "mlt_candidates layout");
@@ -389,6 +398,24 @@ inline mlt_ctx *device_of(mlt_ctx *ctx, int i) { return i == 0 ? ctx : ctx->peer
 int ensure_stage(mlt_ctx *ctx, size_t bytes);   // the context's staging for the host-array entry points holds at least `bytes`
 // mlt_pictures.cpp
 void free_pictures(mlt_ctx *ctx);               // mlt_shutdown: before the peers go
+bool owns_picture(const mlt_ctx *ctx, const mlt_picture *pic);
+// the picture pair as one device sees it | the CUs of a call: a host list with poc / qp per CU, or a DEVICE list of positions that all take one (poc, qp) pair |
+// where the results go (host arrays for a host list, device arrays for a device list; any may be NULL)
+struct AtPlanes {
+  const int16_t *org; long org_pitch; bool org_vec;
+  const int16_t *pred; long pred_pitch; bool pred_vec;
+  static AtPlanes of(const mlt_picture *o, const mlt_picture *p, int g) { return AtPlanes{o->plane[(size_t)g], o->pitch, o->vec, p->plane[(size_t)g], p->pitch, p->vec}; }
+};
+struct AtList {
+  const int32_t *xy, *poc, *qp;
+  bool device; int32_t poc_all, qp_all;
+  static AtList host(const int32_t *xy, const int32_t *poc, const int32_t *qp) { return AtList{xy, poc, qp, false, 0, 0}; }
+  static AtList on_device(const int32_t *d_xy, int32_t poc, int32_t qp) { return AtList{d_xy, nullptr, nullptr, true, poc, qp}; }
+};
+struct AtOut { int32_t *split; float *logits; mlt_decision *dec; mlt_candidates *cand; };
+int predict_at_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &pl, int n, const AtList &at, const AtOut &out);
+// mlt_tree.cpp
+void free_tree(mlt_ctx *ctx);                   // mlt_shutdown
 // mlt_dispatch.cpp
 void release_ws(mlt_ctx *ctx);
 int run_network(mlt_ctx *ctx, SizeState &st, const NetCfg &c, int n, const PassIO &io, const GuardOut &go = GuardOut());

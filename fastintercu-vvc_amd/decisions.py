@@ -6,7 +6,10 @@ confidence gate.  It is what the tests compare the device against, the way synth
 tools/confidence_sweep.py evaluates on a call dump.
 
 `candidates_from_logits` restates the candidate records (include/mltcnn.h: mlt_candidates) the same way: rank, softmax, prefix sums, kept count, cap, mask,
-with the device's tie and NaN rules; tools/candidate_sweep.py evaluates it on a call dump."""
+with the device's tie and NaN rules; tools/candidate_sweep.py evaluates it on a call dump.
+
+`build_tree` restates the partition tree of a picture (include/mltcnn.h: mlt_predict_tree): levels, border roots, node order, descent rule and leaf map, with the
+network behind a callback -- the device's tree driven from the host, or any other decider's."""
 from __future__ import annotations
 
 import numpy as np
@@ -117,3 +120,78 @@ def candidates_from_logits(size: int, logits, head_index: int | None = None, cov
         gap[drop] = srt[drop, count[drop] - 1] - srt[drop, np.minimum(count[drop], K - 1)]
     out["gap"] = gap
     return out
+
+
+# the layout of capi.TREE_NODE_DTYPE (include/mltcnn.h: mlt_tree_node), restated here so that this module stays free of the library
+TREE_NODE_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("size", "<i2"), ("depth", "i1"), ("flags", "u1"), ("parent", "<i4"), ("first_child", "<i4"),
+                            ("split_mode", "<i4"), ("confidence", "<f4"), ("cand_mask", "<u4")])
+TREE_SIZES = (128, 64, 32, 16)
+
+
+def tree_roots(width: int, height: int, top: int, size: int) -> np.ndarray:
+    """[count, 2] int32 {x, y}, raster order: at `top` the complete CUs of the aligned grid; below, the complete size-aligned CUs whose enclosing 2 x size-aligned
+    block is not complete (mlt_tree_roots)."""
+    if top not in TREE_SIZES or size not in TREE_SIZES or size > top:
+        return np.zeros((0, 2), np.int32)
+    ys, xs = np.meshgrid(np.arange(height // size, dtype=np.int32) * size, np.arange(width // size, dtype=np.int32) * size, indexing="ij")
+    xy = np.stack([xs.ravel(), ys.ravel()], axis=1).astype(np.int32).reshape(-1, 2)
+    if size == top:
+        return xy
+    p = 2 * size
+    whole = (xy[:, 0] // p * p + p <= width) & (xy[:, 1] // p * p + p <= height)
+    return xy[~whole]
+
+
+def tree_max_nodes(width: int, height: int, top: int = 128, min_size: int = 16) -> int:
+    if top not in TREE_SIZES or min_size not in TREE_SIZES or min_size > top or not (16 <= width <= 16384 and 16 <= height <= 16384):
+        return 0
+    return sum((width // s) * (height // s) for s in TREE_SIZES if min_size <= s <= top)
+
+
+def build_tree(width: int, height: int, top: int, min_size: int, descend_mask, decide, by_candidates: bool = False):
+    """The partition tree in the contract's order, on the host.  descend_mask: {size: mask} (a missing or zero entry: 1 << 1).  decide(size, xy) -> (split_mode,
+    confidence, cand_mask), one entry per row of the [n, 2] int32 position list -- called once per level with at least one node, top level first.
+    -> (nodes TREE_NODE_DTYPE [n], leaf_map uint8 [height // 16, width // 16])."""
+    assert top in TREE_SIZES and min_size in TREE_SIZES and min_size <= top
+    levels = [s for s in TREE_SIZES if min_size <= s <= top]
+    leaf_map = np.full((height // 16, width // 16), 0xFF, np.uint8)
+    done = []
+    start = 0
+    prev = None          # the previous level's nodes (first_child filled in as their children are emitted)
+    for depth, size in enumerate(levels):
+        roots = tree_roots(width, height, top, size)
+        lvl = np.zeros((len(roots),), TREE_NODE_DTYPE)
+        lvl["x"], lvl["y"], lvl["parent"], lvl["flags"] = roots[:, 0], roots[:, 1], -1, (0 if size == top else 1)
+        if prev is not None:
+            par = np.flatnonzero(prev["_descends"])
+            kids = np.zeros((4 * len(par),), TREE_NODE_DTYPE)
+            for j in range(4):   # z-order: TL, TR, BL, BR
+                kids["x"][j::4] = prev["nodes"]["x"][par] + (j & 1) * size
+                kids["y"][j::4] = prev["nodes"]["y"][par] + (j >> 1) * size
+                kids["parent"][j::4] = prev["start"] + par
+            prev["nodes"]["first_child"][par] = start + len(roots) + 4 * np.arange(len(par))
+            lvl = np.concatenate([lvl, kids])
+        lvl["size"], lvl["depth"], lvl["first_child"] = size, depth, -1
+        descends = np.zeros(len(lvl), bool)
+        if len(lvl):
+            xy = np.stack([lvl["x"], lvl["y"]], axis=1).astype(np.int32)
+            split, conf, cmask = decide(size, xy)
+            lvl["split_mode"], lvl["confidence"], lvl["cand_mask"] = np.asarray(split), np.asarray(conf), np.asarray(cmask)
+            if size > min_size:
+                mask = int((descend_mask or {}).get(size, 0)) or 2
+                if by_candidates:
+                    descends = (lvl["cand_mask"] & np.uint32(mask)) != 0
+                else:
+                    sm = lvl["split_mode"].astype(np.int64)
+                    descends = (sm >= 0) & (((mask >> np.clip(sm, 0, 31)) & 1) != 0)
+        prev = {"nodes": lvl, "_descends": descends, "start": start}
+        done.append(lvl)
+        start += len(lvl)
+    nodes = np.concatenate(done) if done else np.zeros((0,), TREE_NODE_DTYPE)
+    for size in levels:   # leaves are disjoint: every block of a leaf takes (log2(size) - 4) | ((split_mode + 1) << 4)
+        lv = nodes[(nodes["first_child"] < 0) & (nodes["size"] == size)]
+        val = ((size.bit_length() - 5) | ((lv["split_mode"] + 1) << 4)).astype(np.uint8)
+        for dy in range(size // 16):
+            for dx in range(size // 16):
+                leaf_map[lv["y"] // 16 + dy, lv["x"] // 16 + dx] = val
+    return nodes, leaf_map

@@ -242,6 +242,41 @@ class SplitPredictor {
     return true;
   }
 
+  // The partition tree of a picture pair (include/mltcnn.h: mlt_predict_tree): the quadtree descent from topSize down to minSize on the device, one (poc, qp) pair
+  // for the picture.  nodes: level by level in the contract's order; leafMap: one byte per complete 16 x 16 block, [mapH][mapW], (log2(leaf size) - 4) |
+  // ((split_mode + 1) << 4), 0xFF where no node covers the block.  On failure the tree is EMPTY (no nodes, no map): the caller visits every CU, as with -1.
+  struct PartitionTree {
+    std::vector<mlt_tree_node> nodes;
+    std::vector<uint8_t> leafMap;
+    int mapW = 0, mapH = 0;
+    bool empty() const { return nodes.empty(); }
+  };
+  PartitionTree predictTree(const mlt_picture *org, const mlt_picture *pred, int width, int height, int poc, int qp, int topSize = 128, int minSize = 16,
+                            bool byCandidates = false) {
+    Timer tm(this, 0, 0);   // (a tree is one call, not a CU of one size)
+    PartitionTree t;
+    const int cap = mlt_tree_max_nodes(width, height, topSize, minSize);
+    mlt_tree_config cfg{};
+    cfg.struct_size = (uint32_t)sizeof cfg;
+    cfg.top_size = topSize; cfg.min_size = minSize; cfg.poc = poc; cfg.qp = qp;
+    cfg.flags = byCandidates ? MLT_TREE_BY_CANDIDATES : 0u;
+    int n = 0;
+    if (cap > 0) {
+      t.nodes.resize((size_t)cap);
+      t.mapW = width / 16; t.mapH = height / 16;
+      t.leafMap.assign((size_t)t.mapW * (size_t)t.mapH, (uint8_t)0xFF);
+    }
+    if (!m_ctx || cap <= 0 || mlt_predict_tree(m_ctx, org, pred, &cfg, t.nodes.data(), cap, &n, t.leafMap.data(), nullptr, 0, nullptr, nullptr) != MLT_OK) {
+      std::fprintf(stderr, "error\n");  // EncCu.cpp:925
+      ++m_failed;
+      return PartitionTree();
+    }
+    t.nodes.resize((size_t)n);
+    for (const mlt_tree_node &nd : t.nodes)
+      if (nd.split_mode < 0) ++m_gated;
+    return t;
+  }
+
   // The class indices a candidate record keeps, most probable first (classes[] holds up to 8); returns how many.
   static int keptClasses(const mlt_candidates &c, int classes[8]) {
     int n = 0;

@@ -353,6 +353,77 @@ int mlt_predict_at(mlt_ctx *ctx, int size, const mlt_picture *org, const mlt_pic
  * the size query.  0 for an unsupported size or a picture smaller than the size. */
 int mlt_grid_positions(int width, int height, int size, int32_t *xy, int cap);
 
+/* ---- Partition trees of a picture: quadtree descent on the device (new exports; MLT_ABI_VERSION stays 4) ----
+ * What a whole-picture caller wants from a multi-level tree network: evaluate the top_size CUs of a picture pair, evaluate the four half-size children only where
+ * the network says "quad split", and so on down to min_size.  The descent rule is the reference's own: head [2] of the 128 model, class 1, is QT
+ * (mlt_ctu_or_pq_dataset.py:17); the CU models' default head [0] returns 0 / 1 and EncModeCtrl::setNewModeList reads 1 as PartSplit 1 = QT (EncCu.cpp:913-921,
+ * EncModeCtrl.cpp:110-149); square children come only from QT and the network only takes square CUs (EncCu.cpp:801).  The whole descent stays on the device: per
+ * level the node list is compacted by a device kernel (tree_expand), the children's positions never visit the host, and the only host traffic per level is one
+ * 4-byte count.  Every network launch is the one mlt_predict_at makes on the same positions, so every node's result is bit-identical to that call's.
+ *
+ * LEVELS    top_size, top_size / 2, ... min_size (depth 0, 1, ...).
+ * ROOTS     of level top_size: the complete CUs of its aligned grid in raster order (mlt_grid_positions).  Of a lower level S: the complete S-aligned CUs whose
+ *           enclosing 2S-aligned block is NOT complete (it crosses the right or bottom border), in raster order; flags bit 0 set, parent = -1.  A partial CU is
+ *           split implicitly, as VTM does at picture borders, so the tree covers every complete min_size block of the picture.  (424 x 280: 6 roots at 128, 0 at
+ *           64, 8 at 32 -- the column x = 384 -- and 26 at 16 -- the row y = 256.)
+ * ORDER     nodes run level by level; within a level the roots come first, then the children: in the order of their parents in the previous level, four per
+ *           parent in z-order (TL, TR, BL, BR).  A complete parent's children are all complete, so a node has 0 or 4 children, contiguous from first_child.  The
+ *           order is part of the contract.
+ * DESCENT   a node of size S > min_size descends iff
+ *             default                   split_mode >= 0 && (descend_mask[S] >> split_mode) & 1   -- a split withheld by the confidence gate does not descend
+ *             MLT_TREE_BY_CANDIDATES    (cand_mask & descend_mask[S]) != 0                       -- an unsure CU that keeps every class descends
+ *           min_size nodes are evaluated and never descend.
+ * NODES     every node is evaluated: network, guards, confidence gate and candidate policy of its size exactly as in mlt_predict_at with the one (poc, qp) pair;
+ *           the optional per-node logits, decision and candidate records are bit-identical to mlt_predict_at on the nodes' positions.  cand_mask is
+ *           mlt_candidates.mask under the size's policy (default policy: 1 << raw_mode; every class of the head when a logit of the decision head is NaN).
+ * LEAF MAP  one byte per complete 16 x 16 block, [height / 16][width / 16]: (log2(leaf size) - 4) | ((split_mode + 1) << 4) of the leaf that covers the block;
+ *           0xFF for blocks no node covers (possible only with min_size > 16).
+ * ERRORS    all arguments are checked before anything is enqueued and on any error every output stays untouched: ctx, cfg, nodes, n_nodes non-NULL and
+ *           cfg->struct_size == sizeof(mlt_tree_config), top_size / min_size as below, descend_mask bits below the class count of the size's decision head,
+ *           logit_stride >= 15 when logits_opt is given (else MLT_ERR_ARG); every size top..min loaded (else MLT_ERR_SIZE_DISABLED); both pictures of ctx and of
+ *           equal geometry (else MLT_ERR_ARG); node_cap >= mlt_tree_max_nodes(width, height, top_size, min_size) (else MLT_ERR_ARG) -- capacity is a property of
+ *           the geometry, never of the content.
+ * Synchronous, like mlt_predict_at.  On a multi-device context the tree runs on devices[0] (the picture has a plane there); the bytes are a one-device context's. */
+typedef struct mlt_tree_config {
+  uint32_t struct_size;      /* = sizeof(mlt_tree_config); anything else -> MLT_ERR_ARG */
+  int32_t  top_size;         /* 128 / 64 / 32 / 16; 0 => 128 */
+  int32_t  min_size;         /* <= top_size; 0 => 16.  Every size top..min must be loaded, else MLT_ERR_SIZE_DISABLED */
+  uint32_t descend_mask[4];  /* per size {128,64,32,16}: bit k = class k of that size's DECISION head means "quad split".
+                                0 => 1u << 1 (QT of the reference's default heads).  A bit at or above the head's class count -> MLT_ERR_ARG */
+  uint32_t flags;            /* MLT_TREE_BY_CANDIDATES */
+  int32_t  poc, qp;          /* one pair for the whole picture */
+} mlt_tree_config;
+#define MLT_TREE_BY_CANDIDATES 0x1u
+
+typedef struct mlt_tree_node {   /* 32 bytes, little-endian, no padding */
+  int32_t  x, y;          /* top-left luma sample */
+  int16_t  size;          /* 128 / 64 / 32 / 16 */
+  int8_t   depth;         /* 0 at top_size */
+  uint8_t  flags;         /* bit 0: border root (above) */
+  int32_t  parent;        /* node index; -1 for roots */
+  int32_t  first_child;   /* node index of the first of its FOUR children (contiguous, z-order: TL, TR, BL, BR); -1 = leaf */
+  int32_t  split_mode;    /* as every entry point returns it (gate applied: -1 = withheld) */
+  float    confidence;    /* mlt_decision.confidence */
+  uint32_t cand_mask;     /* mlt_candidates.mask under the size's policy */
+} mlt_tree_node;
+
+/* Pure host, no context.  top_size / min_size as in mlt_tree_config: 0 => 128 / 16.
+ * mlt_tree_max_nodes: the sum over the levels top..min of (width / S) * (height / S) -- the node count of a tree that descends everywhere; 0 on bad arguments
+ * (a size outside 128 / 64 / 32 / 16, min_size > top_size, width or height outside 16 .. 16384).
+ * mlt_tree_roots: the roots of level `size` (ROOTS above), counted and capped like mlt_grid_positions: returns the total count and writes min(count, cap)
+ * entries of {x, y}; 0 on bad arguments or for a size above top_size. */
+int mlt_tree_max_nodes(int width, int height, int top_size, int min_size);
+int mlt_tree_roots(int width, int height, int top_size, int size, int32_t *xy, int cap);
+
+/* The partition tree of the picture pair.  nodes[0 .. *n_nodes): the nodes in the contract's order; leaf_map_opt: (height / 16) * (width / 16) bytes or NULL;
+ * logits_opt: node i at logits_opt + i * logit_stride, mlt_num_logits(node size) floats (the rest of the row is left alone), or NULL; dec_opt / cand_opt: one
+ * record per node or NULL.  All HOST memory, node_cap entries each.  A call with cand_opt does not make deferred batches carry candidate records. */
+int mlt_predict_tree(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pred, const mlt_tree_config *cfg,
+                     mlt_tree_node *nodes, int node_cap, int *n_nodes,
+                     uint8_t *leaf_map_opt,
+                     float *logits_opt, int logit_stride,
+                     mlt_decision *dec_opt, mlt_candidates *cand_opt);
+
 int mlt_synchronize(mlt_ctx *ctx);
 
 /* Use an existing hipStream_t (e.g. the caller's) instead of the context's own stream; NULL switches back to a

@@ -8,6 +8,11 @@ and writes per size `<out>_<S>_split.npy` (int32, -1 where the confidence gate w
 
   python tools/picture_map.py org.npy pred.npy --weights-dir DIR --sizes 128,64 --poc 8 --qp 32 --out maps/frame8
   python tools/picture_map.py org.yuv pred.yuv --width 1920 --height 1080 --synthetic 10 --coverage 0.9 --out /tmp/f
+  python tools/picture_map.py org.npy pred.npy --weights-dir DIR --tree --min-size 32 --out maps/frame8
+
+--tree [--min-size S]: the PARTITION TREE instead of the per-size maps (MltCnn.predict_tree): the CTUs, and only where the network says "quad split" their
+children, down to S (default 16); loads every size 128 .. S, writes `<out>_tree_nodes.npy` (capi.TREE_NODE_DTYPE, the contract's order) and `<out>_leafmap.npy`
+(uint8 [height // 16, width // 16]) and prints the nodes per level.
 
 File reading and grid logic (read_picture, grid, to_map, histogram) need neither a device nor the library; run_maps needs the MI355X."""
 import argparse
@@ -87,7 +92,31 @@ def run_maps(m, org: np.ndarray, pred: np.ndarray, sizes, poc: int, qp: int) -> 
     return out
 
 
-def main(argv=None):
+def tree_sizes(min_size: int) -> tuple:
+    """The CU sizes a tree from 128 down to min_size evaluates (what --tree loads instead of --sizes)."""
+    if min_size not in SIZES:
+        raise ValueError(f"--min-size {min_size}: want one of {SIZES}")
+    return tuple(s for s in SIZES if s >= min_size)
+
+
+def tree_summary(nodes: np.ndarray) -> list:
+    """[(size, nodes, of them descending)] per level of a node array."""
+    return [(int(s), int((nodes["size"] == s).sum()), int(((nodes["size"] == s) & (nodes["first_child"] >= 0)).sum())) for s in SIZES if (nodes["size"] == s).any()]
+
+
+def run_tree(m, org: np.ndarray, pred: np.ndarray, poc: int, qp: int, min_size: int = 16) -> dict:
+    """m: an MltCnn with tree_sizes(min_size) loaded -> {"nodes", "leaf_map"} (MltCnn.predict_tree)."""
+    assert org.shape == pred.shape
+    height, width = org.shape
+    p_org, p_pred = m.picture(width, height).upload(org), m.picture(width, height).upload(pred)
+    try:
+        return m.predict_tree(p_org, p_pred, poc, qp, top=128, min_size=min_size, want=("leaf_map",))
+    finally:
+        p_org.close()
+        p_pred.close()
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("org")
     ap.add_argument("pred")
@@ -103,10 +132,27 @@ def main(argv=None):
     ap.add_argument("--max-modes", type=int, default=0, help="candidate policy: cap")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", required=True, help="prefix of the .npy maps")
+    ap.add_argument("--tree", action="store_true", help="the partition tree (quadtree descent on the device) instead of the per-size maps")
+    ap.add_argument("--min-size", type=int, default=None, help="with --tree: the smallest CU size of the descent (default 16)")
     args = ap.parse_args(argv)
     sizes = tuple(int(s) for s in args.sizes.split(",") if s)
     if not sizes or any(s not in SIZES for s in sizes) or (args.weights_dir is None) == (args.synthetic is None):
         ap.error("--sizes from 128,64,32,16 and exactly one of --weights-dir / --synthetic")
+    if args.min_size is not None and not args.tree:
+        ap.error("--min-size goes with --tree")
+    if args.tree:
+        if args.min_size is None:
+            args.min_size = 16
+        if args.min_size not in SIZES:
+            ap.error("--min-size from 128,64,32,16")
+        sizes = tree_sizes(args.min_size)   # every level of the descent (--sizes is not consulted)
+    args.size_list = sizes
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    sizes = args.size_list
     org = read_picture(args.org, args.width, args.height)
     pred = read_picture(args.pred, org.shape[1], org.shape[0])
     import mltcnn_pkg
@@ -120,8 +166,18 @@ def main(argv=None):
             m.set_confidence_gate(s, args.min_conf)
         if args.coverage > 0 or args.max_modes > 0:
             m.set_candidate_policy(s, args.coverage, args.max_modes)
-    maps = run_maps(m, org, pred, sizes, args.poc, args.qp)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    if args.tree:
+        t = run_tree(m, org, pred, args.poc, args.qp, args.min_size)
+        np.save(f"{args.out}_tree_nodes.npy", t["nodes"])
+        np.save(f"{args.out}_leafmap.npy", t["leaf_map"])
+        for size, count, desc in tree_summary(t["nodes"]):
+            print(f"size {size}: {count} nodes, {desc} descend")
+        print(f"tree: {len(t['nodes'])} nodes of at most {pkg.capi.tree_max_nodes(org.shape[1], org.shape[0], 128, args.min_size)}, "
+              f"{int((t['leaf_map'] == 0xFF).sum())} of {t['leaf_map'].size} 16x16 blocks uncovered")
+        m.close()
+        return 0
+    maps = run_maps(m, org, pred, sizes, args.poc, args.qp)
     for s, r in maps.items():
         for name in ("split", "confidence", "mask"):
             np.save(f"{args.out}_{s}_{name}.npy", r[name])
