@@ -381,22 +381,44 @@ def make_mix_bulk(size: int, n: int, input_seed: int, flat_frac: float = 0.0, na
     return org, pred, is_flat
 
 
-def flat_quad_fraction(org: np.ndarray, pred: np.ndarray, flat_range: int = 6, return_exact: bool = False):
-    """Host restatement of the flat-content guard's statistic (csrc/mlt_kernels.hip: quad_near_flat): per CU, the fraction of aligned
-    4-pixel quads that are coherent in BOTH planes the network sees (org clipped to 10 bits, |org - pred| clipped) -- range <= flat_range
-    or linear to within one step.  The guard flags a CU when the fraction reaches 1/8."""
-    o = np.clip(org.astype(np.uint16).astype(np.int64), 0, 1023)
-    r = np.clip(np.abs(org.astype(np.uint16).astype(np.int64) - pred.astype(np.uint16).astype(np.int64)), 0, 1023)
+def _flat_quad_masks(org: np.ndarray, pred: np.ndarray, flat_range: int):
+    """(near-flat, exactly flat) bool [n, S, S // 4] per aligned 4-pixel quad: csrc/mlt_kernels.h (MLT_FLAT_RANGE) restated with numpy."""
+    uo, up = org.astype(np.uint16).astype(np.int64), pred.astype(np.uint16).astype(np.int64)
+    o = np.minimum(uo, 1023)
+    r = np.minimum(np.abs(uo - up), 1023)
     n, S, _ = o.shape
-    res = np.ones((n, S, S // 4), bool)
+    near = np.ones((n, S, S // 4), bool)
     exact = np.ones((n, S, S // 4), bool)
     for a in (o, r):
         q = a.reshape(n, S, S // 4, 4)
         rng = q.max(-1) - q.min(-1)
         d1 = np.abs(q[..., 0] + q[..., 2] - 2 * q[..., 1])
         d2 = np.abs(q[..., 1] + q[..., 3] - 2 * q[..., 2])
-        res &= (rng <= flat_range) | (np.maximum(d1, d2) <= 1)
+        near &= (rng <= flat_range) | (np.maximum(d1, d2) <= 1)
         exact &= (rng == 0) | (np.maximum(d1, d2) == 0)
+    return near, exact
+
+
+def flat_quad_fraction(org: np.ndarray, pred: np.ndarray, flat_range: int = 6, return_exact: bool = False):
+    """Host restatement of the flat-content guard's statistic (csrc/mlt_kernels.hip: quad_flat_bits): per CU, the fraction of aligned
+    4-pixel quads that are NEAR-FLAT -- coherent in BOTH planes the network sees (org clipped to 10 bits, |org - pred| clipped): range
+    <= flat_range or linear to within one step -- and, with return_exact, the fraction that are EXACTLY flat (each plane constant or
+    exactly linear).  The guard's rule is two-level (flat_guard_flags): a CU is flagged when the exactly flat fraction reaches
+    1 / flat_div (1/8, or 1/16 for the tiers behind the magnitude guard and the exact-lite tier) OR the near-flat fraction reaches 1/2."""
+    near, exact = _flat_quad_masks(org, pred, flat_range)
+    n = near.shape[0]
     if return_exact:
-        return res.reshape(n, -1).mean(1), exact.reshape(n, -1).mean(1)
-    return res.reshape(n, -1).mean(1)
+        return near.reshape(n, -1).mean(1), exact.reshape(n, -1).mean(1)
+    return near.reshape(n, -1).mean(1)
+
+
+def flat_guard_flags(org: np.ndarray, pred: np.ndarray, flat_div: int = 8, flat_range: int = 6):
+    """The flat-content guard on the host, in the integers the device compares (csrc/mlt_guards.cpp: guard_thresholds): per CU
+    (near_count, exact_count, flagged) with flagged = exact_count >= Q // flat_div or near_count >= Q // 2, Q = S * S // 4 quads."""
+    near, exact = _flat_quad_masks(org, pred, flat_range)
+    n, S, _ = near.shape
+    near_count = near.reshape(n, -1).sum(1).astype(np.int64)
+    exact_count = exact.reshape(n, -1).sum(1).astype(np.int64)
+    quads = S * S // 4
+    flagged = (exact_count >= quads // flat_div) | (near_count >= quads // 2)
+    return near_count, exact_count, flagged
