@@ -23,6 +23,19 @@ __device__ __forceinline__ void head_decision(const float *l, int K, int &best, 
   conf = 1.f / sum;
 }
 
+// The decision guard's rule on one head's K logits: the top-2 margin (head_decision's scan) is not >= thr, or a logit is NaN.  The NaN needs its own test: a NaN
+// loses both comparisons of the scan, which then reports the margin of the OTHER classes, and !(t1 - t2 >= thr) alone catches only a head whose logits are ALL
+// NaN.  Shared by the heads kernels' tail (batches and mlt_predict's one-CU launches) and guard_select_kernel.
+__device__ __forceinline__ bool margin_guard(const float *l, int K, float thr) {
+  float t1 = -3.4e38f, t2 = -3.4e38f;
+  bool nan = false;
+  for (int c = 0; c < K; ++c) {
+    nan = nan || l[c] != l[c];
+    if (l[c] > t1) { t2 = t1; t1 = l[c]; } else if (l[c] > t2) t2 = l[c];
+  }
+  return nan || !(t1 - t2 >= thr);
+}
+
 // Candidate set of one head from its K <= MLT_MAX_CAND_K logits, the counterpart of head_decision (include/mltcnn.h: mlt_candidates states the semantics):
 // classes ranked by logit, descending, equal logits in class order (an insertion sort by adjacent exchanges on registers: every index is a compile-time constant
 // after unrolling, nothing lives in scratch); the fp32 softmax of every class -- the operations of head_decision, so prob[argmax] is its confidence bit for bit --
@@ -190,11 +203,7 @@ __device__ __forceinline__ void heads_body(const HeadArgs &a) {
         a.g_flat[n] = 0;
       }
       if (a.g_margin > 0.f) {
-        float t1 = -3.4e38f, t2 = -3.4e38f;
-        for (int c = 0; c < a.classes[a.decision_head]; ++c) {
-          if (lg[off + c] > t1) { t2 = t1; t1 = lg[off + c]; } else if (lg[off + c] > t2) t2 = lg[off + c];
-        }
-        s = s || !(t1 - t2 >= a.g_margin);
+        s = s || margin_guard(lg + off, a.classes[a.decision_head], a.g_margin);
         if (DEC && a.g_conf_band > 0.f) s = s || !(fabsf(conf - a.min_conf) >= a.g_conf_band);   // the gate guard (mlt_kernels.h: MLT_CONF_BAND_FRAC); also catches NaN
         if (CAND) s = s || cflag;   // the candidate guard (head_candidates; off unless g_cand_band > 0)
       }
@@ -264,11 +273,7 @@ __global__ __launch_bounds__(1024) void guard_select_kernel(const GuardSelectArg
     bool s = a.flat && ((a.flat[i] >> MLT_FLAT_EXACT_SHIFT) >= a.flat_thr || (a.flat[i] & 0xFFFF) >= a.near_thr);
     if (a.logits && a.margin > 0.f) {
       const float *l = a.logits + (size_t)i * a.n_logits + a.head_off;
-      float t1 = -3.4e38f, t2 = -3.4e38f;
-      for (int c = 0; c < a.head_classes; ++c) {
-        if (l[c] > t1) { t2 = t1; t1 = l[c]; } else if (l[c] > t2) t2 = l[c];
-      }
-      s = s || !(t1 - t2 >= a.margin);  // also catches NaN
+      s = s || margin_guard(l, a.head_classes, a.margin);
       if (a.conf_band > 0.f) {   // the gate guard, on the confidence heads_kernel computed from these logits (same function, same operations)
         int bm; float cf, mg;
         head_decision(l, a.head_classes, bm, cf, mg);

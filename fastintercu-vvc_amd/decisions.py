@@ -26,6 +26,9 @@ def default_head(size: int) -> int:
 
 
 def from_logits(size: int, logits, head_index: int | None = None, min_confidence: float = 0.0) -> np.ndarray:
+    """The decision records of [n, num_logits] logits.  The margin is defined for finite logits: the device starts its top-2 scan from -3.4e38 and a NaN never
+    wins a comparison there, so a -inf logit gives a margin of 3.4e38 on the device and inf here, and a row with a NaN the margin of its other classes on the
+    device and NaN here (its argmax is np.argmax's here, the NaN, and the comparison scan's on the device)."""
     classes = HEAD_CLASSES[size]
     lg = np.asarray(logits, np.float64)
     if lg.ndim == 1:

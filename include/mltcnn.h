@@ -59,7 +59,8 @@ enum {
  *   decision guard (default on since ABI 4 -- split modes are what the encoder consumes, EncCu.cpp:921 -> EncModeCtrl.cpp:110-149;
  *                            MLT_FLAG_NO_DECISION_GUARD turns it off): CUs whose decision-head top-2 margin is below guard_margin
  *                            (default 3 x tolerance) are re-evaluated too, so the split mode handed to
- *                            EncModeCtrl::setNewModeList is the one ~fp32 arithmetic gives.
+ *                            EncModeCtrl::setNewModeList is the one ~fp32 arithmetic gives.  A CU with a NaN logit on the
+ *                            decision head is re-evaluated as well, whatever its other classes' margin.
  * Both cost a second (exact) copy of the weights on the device (11 MB). */
 #define MLT_FLAG_EXACT_128 0x1u
 #define MLT_FLAG_FAST_SMALL 0x2u       /* single-pass fp16 for 64/32/16 (measurement only: NO seeded weight set meets 1e-3 with it --
@@ -243,7 +244,9 @@ typedef struct mlt_decision {   /* 48 bytes, little-endian, no padding */
   int32_t split_mode;     /* what the encoder consumes: raw_mode, or -1 when the gate withholds it */
   int32_t raw_mode;       /* argmax of the decision head (first maximal index), gate ignored */
   float   confidence;     /* softmax probability of raw_mode within the decision head */
-  float   margin;         /* top-1 minus top-2 logit of the decision head */
+  float   margin;         /* top-1 minus top-2 logit of the decision head.  Defined for finite logits: the scan starts from -3.4e38, so a -inf logit
+                             counts as -3.4e38, and a NaN logit never wins a comparison (the margin is then that of the other classes; the decision
+                             guard tests for the NaN itself) */
   int32_t level_mode[4];  /* argmax of every head, lvl1..lvl4 (first-max rule); -1 for a head the model lacks */
   float   level_conf[4];  /* its softmax probability; 0 for a head the model lacks */
 } mlt_decision;
