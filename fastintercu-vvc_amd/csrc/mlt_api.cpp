@@ -16,11 +16,13 @@ std::mutex g_mutex;
 
 }  // namespace
 
-int ensure_stage(mlt_ctx *ctx, size_t bytes) {
-  if (bytes <= ctx->stage_bytes) return MLT_OK;
-  if (ctx->stage) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->stage); ctx->stage = nullptr; ctx->stage_bytes = 0; }
-  HIP_TRY(ctx, hipMalloc((void **)&ctx->stage, bytes));
-  ctx->stage_bytes = bytes;
+int GrowBuf::reserve(mlt_ctx *ctx, size_t want, const char *what, bool zero) {
+  if (want <= bytes) return MLT_OK;
+  if (p) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); release(); }
+  const hipError_t e = pinned ? hipHostMalloc((void **)&p, want, hipHostMallocDefault) : hipMalloc((void **)&p, want);
+  if (e != hipSuccess) { p = nullptr; ctx->err = std::string(what) + ": " + hipGetErrorString(e); return e == hipErrorOutOfMemory ? MLT_ERR_NOMEM : MLT_ERR_HIP; }
+  bytes = want;
+  if (zero) HIP_TRY(ctx, hipMemset(p, 0, want));
   return MLT_OK;
 }
 
@@ -193,13 +195,10 @@ void mlt_shutdown(mlt_ctx *ctx) {
   }
   if (ctx->ws) (void)hipFree(ctx->ws);
   if (ctx->zero_page) (void)hipFree(ctx->zero_page);
-  if (ctx->h_res) (void)hipHostFree(ctx->h_res);
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   for (int b = 0; b < 2; ++b) { if (ctx->ev_h2d[b]) (void)hipEventDestroy(ctx->ev_h2d[b]); if (ctx->ev_done[b]) (void)hipEventDestroy(ctx->ev_done[b]); }
-  if (ctx->stage) (void)hipFree(ctx->stage);
-  if (ctx->guard_dev) (void)hipFree(ctx->guard_dev);
-  if (ctx->gstage) (void)hipFree(ctx->gstage);
-  free_tree(ctx);
+  for (GrowBuf *buf : {&ctx->stage, &ctx->guard_dev, &ctx->gstage, &ctx->tree_dev, &ctx->h_res}) buf->release();
+  if (ctx->tree_host) (void)hipHostFree(ctx->tree_host);
   if (ctx->guard_host) (void)hipHostFree(ctx->guard_host);
   if (ctx->ev_guard) (void)hipEventDestroy(ctx->ev_guard);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -294,7 +293,7 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
   const StageSet lay(size, cap, nl, dec != nullptr, cand != nullptr);   // (the records sit beside the split modes and the logits)
   const size_t setbytes = lay.bytes();
   const int nset = n > cap ? 2 : 1;
-  if ((rc = ensure_stage(ctx, nset * setbytes))) return rc;
+  if ((rc = ctx->stage.reserve(ctx, nset * setbytes, "staging"))) return rc;
   if (nset == 2 && !ctx->copy_stream) {
     HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     for (int b = 0; b < 2; ++b) {
@@ -303,7 +302,7 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
     }
   }
   using Set = StageSet::Ptrs;
-  auto set_of = [&](int b) { return lay.at(ctx->stage + (size_t)b * setbytes); };
+  auto set_of = [&](int b) { return lay.at(ctx->stage.p + (size_t)b * setbytes); };
   // (the fast results of a sub-chunk, and what the exact re-run of its flagged CUs overwrites)
   auto io_of = [&](const Set &S) { return PassIO{Planes::dense(S.d_org, S.d_pred, size), S.d_poc, S.d_qp, S.d_split, logits ? S.d_lg : nullptr, S.d_dec, S.d_cand}; };
   const bool guards = st->guards();
@@ -313,23 +312,16 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
       if ((rc = guard_slot(ctx, b, cap, nl, &gs[b]))) return rc;
   // Results come back through pinned buffers owned by the context: a D2H into the caller's (usually pageable) arrays
   // would block the host until the kernels are done and serialise the next sub-chunk's H2D behind them.
-  const size_t hres_dec = (size_t)cap * 4 + (size_t)cap * nl * 4;
-  const size_t hres_cand = hres_dec + (dec ? (size_t)cap * sizeof(DecisionRec) : 0);
-  const size_t hres_set = hres_cand + (cand ? (size_t)cap * sizeof(CandRec) : 0);
-  if (ctx->h_res_bytes < 2 * hres_set) {
-    if (ctx->h_res) (void)hipHostFree(ctx->h_res);
-    ctx->h_res = nullptr; ctx->h_res_bytes = 0;
-    HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_res, 2 * hres_set, hipHostMallocDefault));
-    ctx->h_res_bytes = 2 * hres_set;
-  }
+  const Lay::ResultSet res(cap, nl, dec != nullptr, cand != nullptr);
+  if ((rc = ctx->h_res.reserve(ctx, 2 * res.bytes(), "result staging"))) return rc;
   int pend_i0[2] = {-1, -1}, pend_c[2] = {0, 0};
   auto fetch = [&](int b, int c) -> int {  // results of set b -> pinned (asynchronous)
     const Set S = set_of(b);
-    char *hb = ctx->h_res + (size_t)b * hres_set;
-    HIP_TRY(ctx, hipMemcpyAsync(hb, S.d_split, (size_t)c * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (logits) HIP_TRY(ctx, hipMemcpyAsync(hb + (size_t)cap * 4, S.d_lg, (size_t)c * nl * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (dec) HIP_TRY(ctx, hipMemcpyAsync(hb + hres_dec, S.d_dec, (size_t)c * sizeof(DecisionRec), hipMemcpyDeviceToHost, ctx->stream));
-    if (cand) HIP_TRY(ctx, hipMemcpyAsync(hb + hres_cand, S.d_cand, (size_t)c * sizeof(CandRec), hipMemcpyDeviceToHost, ctx->stream));
+    char *hb = ctx->h_res.p + (size_t)b * res.bytes();
+    HIP_TRY(ctx, hipMemcpyAsync(hb + res.split.off, S.d_split, (size_t)c * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (logits) HIP_TRY(ctx, hipMemcpyAsync(hb + res.lg.off, S.d_lg, (size_t)c * nl * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (dec) HIP_TRY(ctx, hipMemcpyAsync(hb + res.dec.off, S.d_dec, (size_t)c * sizeof(DecisionRec), hipMemcpyDeviceToHost, ctx->stream));
+    if (cand) HIP_TRY(ctx, hipMemcpyAsync(hb + res.cand.off, S.d_cand, (size_t)c * sizeof(CandRec), hipMemcpyDeviceToHost, ctx->stream));
     return MLT_OK;
   };
   auto flush = [&](int b) -> int {  // sub-chunk in set b has completed: guard fix-up if needed, then hand its results to the caller
@@ -345,11 +337,11 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       }
     }
-    const char *hb = ctx->h_res + (size_t)b * hres_set;
-    if (split_mode) std::memcpy(split_mode + pend_i0[b], hb, (size_t)pend_c[b] * 4);
-    if (logits) std::memcpy(logits + (size_t)pend_i0[b] * nl, hb + (size_t)cap * 4, (size_t)pend_c[b] * nl * 4);
-    if (dec) std::memcpy(dec + pend_i0[b], hb + hres_dec, (size_t)pend_c[b] * sizeof(DecisionRec));
-    if (cand) std::memcpy(cand + pend_i0[b], hb + hres_cand, (size_t)pend_c[b] * sizeof(CandRec));
+    const char *hb = ctx->h_res.p + (size_t)b * res.bytes();
+    if (split_mode) std::memcpy(split_mode + pend_i0[b], hb + res.split.off, (size_t)pend_c[b] * 4);
+    if (logits) std::memcpy(logits + (size_t)pend_i0[b] * nl, hb + res.lg.off, (size_t)pend_c[b] * nl * 4);
+    if (dec) std::memcpy(dec + pend_i0[b], hb + res.dec.off, (size_t)pend_c[b] * sizeof(DecisionRec));
+    if (cand) std::memcpy(cand + pend_i0[b], hb + res.cand.off, (size_t)pend_c[b] * sizeof(CandRec));
     pend_i0[b] = -1;
     return MLT_OK;
   };
@@ -391,26 +383,13 @@ static int predict_batch_impl(mlt_ctx *ctx, int n, int size, const int16_t *org,
   int rc = check_size(ctx, size, &st);
   if (rc) return rc;
   if (n == 0) return MLT_OK;
-  if (!ctx->peers.empty() && n > 1) {
-    // multi-device context: contiguous shards (device g gets CUs [n g / G, n (g + 1) / G)), one host thread per further device, no
-    // exchange between them; every device runs the single-device path on its shard, so the results are those of one device
-    const int G = 1 + (int)ctx->peers.size(), nlg = st->model.n_logits;
+  if (!ctx->peers.empty() && n > 1) {   // multi-device context: every device runs the single-device path on its shard
+    const int nlg = st->model.n_logits;
     const size_t csz = (size_t)size * size;
-    std::vector<mlt_ctx *> devs;
-    for (int g = 0; g < G; ++g) devs.push_back(device_of(ctx, g));
-    std::vector<int> rcs((size_t)G, MLT_OK);
-    auto run = [&](int g) {
-      const int lo = shard_lo(n, g, G), hi = shard_lo(n, g + 1, G);
-      if (hi > lo) rcs[(size_t)g] = predict_batch_single(devs[(size_t)g], hi - lo, size, org + (size_t)lo * csz, pred + (size_t)lo * csz, poc + lo, qp + lo,
-                                                         split_mode ? split_mode + lo : nullptr, logits ? logits + (size_t)lo * nlg : nullptr, dec ? dec + lo : nullptr, cand ? cand + lo : nullptr);
-    };
-    std::vector<std::thread> th;
-    for (int g = 1; g < G; ++g) th.emplace_back(run, g);
-    run(0);
-    for (std::thread &t : th) t.join();
-    for (int g = 0; g < G; ++g)
-      if (rcs[(size_t)g]) { if (g) ctx->err = "device " + std::to_string(devs[(size_t)g]->device) + ": " + devs[(size_t)g]->err; return rcs[(size_t)g]; }
-    return MLT_OK;
+    return run_sharded(ctx, n, [&](int g, int lo, int hi) {
+      return predict_batch_single(device_of(ctx, g), hi - lo, size, org + (size_t)lo * csz, pred + (size_t)lo * csz, poc + lo, qp + lo,
+                                  split_mode ? split_mode + lo : nullptr, logits ? logits + (size_t)lo * nlg : nullptr, dec ? dec + lo : nullptr, cand ? cand + lo : nullptr);
+    });
   }
   return predict_batch_single(ctx, n, size, org, pred, poc, qp, split_mode, logits, dec, cand);
 }
@@ -443,36 +422,32 @@ static int predict_one(mlt_ctx *ctx, const int16_t *org, int org_stride, const i
   if (rc) return rc;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
   const int nl = st->model.n_logits;
-  const size_t cs = (size_t)size * size;
   if (cand) st->cand_used = true;
   // (a graph of its own for the calls that want the record, and one for those that want the candidate record -- which always carries the decision record along:
   // plain calls replay the launches they always did)
   SingleCu &sg = ctx->single[size_index(size) + (cand ? 8 : dec ? 4 : 0)];
   if (!sg.h_stage) {
-    sg.plane = (cs * 2 + 255) / 256 * 256;
-    HIP_TRY(ctx, hipHostMalloc((void **)&sg.h_stage, 2 * sg.plane + 256, hipHostMallocDefault));
-    HIP_TRY(ctx, hipMalloc((void **)&sg.d_stage, 2 * sg.plane + 256));
-    HIP_TRY(ctx, hipMemset(sg.d_stage + 2 * sg.plane, 0, 256));  // the flat-guard statistic of the single-CU path starts at zero (consume-and-clear)
+    sg.lay = Lay::SingleLay(size, nl);
+    HIP_TRY(ctx, hipHostMalloc((void **)&sg.h_stage, sg.lay.bytes(), hipHostMallocDefault));
+    HIP_TRY(ctx, hipMalloc((void **)&sg.d_stage, sg.lay.bytes()));
+    HIP_TRY(ctx, hipMemset(sg.d_stage + sg.lay.scalars().off, 0, sg.lay.scalars().bytes));  // the flat-guard statistic of the single-CU path starts at zero (consume-and-clear)
   }
+  const Lay::SingleLay &lay = sg.lay;
+  const Lay::CuFields::Ptrs H = lay.at(sg.h_stage), D = lay.at(sg.d_stage);   // (H: the pinned mirror)
   // the gather of EncCu.cpp:810-830: rows of `size` Pels out of a `stride`-Pel pitch -> dense planes (pinned)
   for (int y = 0; y < size; ++y) {
-    std::memcpy(sg.h_stage + (size_t)y * size * 2, org + (size_t)y * org_stride, (size_t)size * 2);
-    std::memcpy(sg.h_stage + sg.plane + (size_t)y * size * 2, pred + (size_t)y * pred_stride, (size_t)size * 2);
+    std::memcpy(H.d_org + (size_t)y * size, org + (size_t)y * org_stride, (size_t)size * 2);
+    std::memcpy(H.d_pred + (size_t)y * size, pred + (size_t)y * pred_stride, (size_t)size * 2);
   }
-  int32_t *h_sc = (int32_t *)(sg.h_stage + 2 * sg.plane);  // [poc, qp, split, pad, logits...]
-  h_sc[0] = poc; h_sc[1] = qp;
-  HIP_TRY(ctx, hipMemcpyAsync(sg.d_stage, sg.h_stage, 2 * sg.plane + 8, hipMemcpyHostToDevice, ctx->stream));
-  int16_t *d_org = (int16_t *)sg.d_stage, *d_pred = (int16_t *)(sg.d_stage + sg.plane);
-  int32_t *d_sc = (int32_t *)(sg.d_stage + 2 * sg.plane);  // [poc, qp, split, flagged count, logits (<= 16) ..., flat, idx, mag, pad, record (12 words at 24), candidate record (10 words at 36)]
-  DecisionRec *d_dec = (dec || cand) ? (DecisionRec *)(d_sc + 24) : nullptr;
-  CandRec *d_cand = cand ? (CandRec *)(d_sc + 36) : nullptr;
-  const size_t fetch = cand ? (size_t)(22 + 12 + 10) * 4 : dec ? (size_t)(22 + 12) * 4 : (size_t)(2 + nl) * 4;   // split, count, logits [.. record [, candidate record]]
-  const PassIO io{Planes::dense(d_org, d_pred, size), d_sc, d_sc + 1, d_sc + 2, (float *)(d_sc + 4), d_dec, d_cand};
+  *H.d_poc = poc; *H.d_qp = qp;
+  HIP_TRY(ctx, hipMemcpyAsync(sg.d_stage, sg.h_stage, lay.h2d_bytes(), hipMemcpyHostToDevice, ctx->stream));
+  const Lay::Field fetch = lay.fetch(dec != nullptr, cand != nullptr);   // split, flagged count, logits [, record [, candidate record]]
+  const PassIO io{Planes::dense(D.d_org, D.d_pred, size), D.d_poc, D.d_qp, D.d_split, D.d_lg, (dec || cand) ? D.d_dec : nullptr, cand ? D.d_cand : nullptr};
   const bool guards = st->guards();
-  GuardSlot g;
-  g.d_count = d_sc + 3; g.d_flat = d_sc + 20; g.d_idx = d_sc + 21; g.d_lg = (float *)(d_sc + 4); g.d_mag = (float *)(d_sc + 22); g.h_count = h_sc + 3;
-  g.single = true;  // (d_flat was zeroed with the staging buffer and is cleared by every call's heads kernel)
-  // the kernel chain of one CU (captured into a hipGraph below); with guards the flagged count comes back in h_sc[3] with the results
+  int32_t *h_count = lay.g.count.in<int32_t>(sg.h_stage);
+  // (d_flat was zeroed with the staging buffer and is cleared by every call's heads kernel)
+  const GuardSlot g{lay.g.at(sg.d_stage), nullptr, h_count, true};
+  // the kernel chain of one CU (captured into a hipGraph below); with guards the flagged count comes back in *h_count with the results
   auto chain = [&]() -> int { return run_fast_async(ctx, *st, 1, io, g); };
   const bool no_graph = tuning().no_graph;
   bool replayed = false;
@@ -504,17 +479,17 @@ static int predict_one(mlt_ctx *ctx, const int16_t *org, int org_stride, const i
     }
   }
   if (!replayed && (rc = chain())) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(h_sc + 2, d_sc + 2, fetch, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(sg.h_stage + fetch.off, sg.d_stage + fetch.off, fetch.bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (guards && h_sc[3] != 0) {  // flagged (flat content / near-tie on the decision head): re-evaluate with the exact arithmetic
+  if (guards && *h_count != 0) {  // flagged (flat content / near-tie on the decision head): re-evaluate with the exact arithmetic
     if ((rc = guard_fixup_async(ctx, *st, 1, io, g))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(h_sc + 2, d_sc + 2, fetch, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(sg.h_stage + fetch.off, sg.d_stage + fetch.off, fetch.bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
-  if (split_mode) *split_mode = h_sc[2];
-  if (logits_opt) std::memcpy(logits_opt, h_sc + 4, (size_t)nl * 4);
-  if (dec) std::memcpy(dec, h_sc + 24, sizeof(DecisionRec));
-  if (cand) std::memcpy(cand, h_sc + 36, sizeof(CandRec));
+  if (split_mode) *split_mode = *H.d_split;
+  if (logits_opt) std::memcpy(logits_opt, H.d_lg, (size_t)nl * 4);
+  if (dec) std::memcpy(dec, H.d_dec, sizeof(DecisionRec));
+  if (cand) std::memcpy(cand, H.d_cand, sizeof(CandRec));
   return MLT_OK;
 }
 
@@ -538,43 +513,33 @@ int mlt_predict_candidates(mlt_ctx *ctx, const int16_t *org, int org_stride, con
 
 // ---- deferred single-CU prediction ----
 namespace {
-// device / pinned layout of one output set: split[CAP] | logits[CAP * nl] | flagged count (16 ints) | records[CAP] | candidate records[CAP] | flat[CAP] | idx[CAP] | mag[CAP]
-// (a deferred batch always carries its CUs' decision records -- whether a ticket is read with mlt_wait or mlt_wait_decision is not known when the batch is launched:
-// 3 KiB more in the batch's one result copy; the candidate records are filled and fetched only by batches launched once the size has a policy or has seen a
-// candidate call -- SizeState.cand_used -- so that every other batch launches and copies what it always did)
-struct DeferredOut { int32_t *split; float *lg; int32_t *count, *flat, *idx; float *mag; DecisionRec *dec; CandRec *cand; };
-DeferredOut deferred_out(char *base, int nl) {
-  DeferredOut o;
-  o.split = (int32_t *)base; o.lg = (float *)(base + (size_t)MLT_DEFER_CAP * 4);
-  o.count = (int32_t *)(base + (size_t)MLT_DEFER_CAP * 4 * (1 + nl));
-  o.dec = (DecisionRec *)(o.count + 16);
-  o.cand = (CandRec *)(o.dec + MLT_DEFER_CAP);
-  o.flat = (int32_t *)(o.cand + MLT_DEFER_CAP); o.idx = o.flat + MLT_DEFER_CAP; o.mag = (float *)(o.idx + MLT_DEFER_CAP);
-  return o;
-}
-size_t deferred_fetch_bytes(int nl, bool cand) { return (size_t)MLT_DEFER_CAP * 4 * (1 + nl) + 64 + (size_t)MLT_DEFER_CAP * (sizeof(DecisionRec) + (cand ? sizeof(CandRec) : 0)); }
+// what a pass over set b of the size's deferred buffers reads and writes, and the set's guard slot (its counter pair toggles per launch: df.phase)
+struct DeferredIO {
+  PassIO io;
+  GuardSlot g;
+  DeferredIO(SizeState *st, Deferred &df, int b) {
+    char *dout = df.d_out + (size_t)b * df.out.bytes();
+    const Lay::CuFields::Ptrs in = df.in.at(df.d_in + (size_t)b * df.in.bytes()), od = df.out.at(dout);
+    const long cu = (long)(df.in.plane / 2);
+    io = PassIO{Planes{in.d_org, in.d_pred, st->size, cu, st->size, cu}, in.d_poc, in.d_qp, od.d_split, od.d_lg, od.d_dec, df.has_cand[b] ? od.d_cand : nullptr};
+    g = GuardSlot{df.out.g.at(dout), &df.phase[b], df.out.g.count.in<int32_t>(df.h_out + (size_t)b * df.out.bytes())};
+  }
+};
 
 int deferred_launch(mlt_ctx *ctx, SizeState *st, Deferred &df) {  // launch the accumulating generation as one batch
   if (df.n == 0) return MLT_OK;
-  const int size = st->size, nl = st->model.n_logits, b = (int)(df.gen & 1), n = df.n;
-  char *hi = df.h_in + (size_t)b * df.in_set, *di = df.d_in + (size_t)b * df.in_set;
-  char *ho = df.h_out + (size_t)b * df.out_set, *dout = df.d_out + (size_t)b * df.out_set;
-  const size_t planes = (size_t)MLT_DEFER_CAP * df.plane;
-  // org planes, pred planes, poc, qp: four regions of the set, only the first n entries of each are live
-  HIP_TRY(ctx, hipMemcpyAsync(di, hi, (size_t)n * df.plane, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(di + planes, hi + planes, (size_t)n * df.plane, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(di + 2 * planes, hi + 2 * planes, (size_t)MLT_DEFER_CAP * 8, hipMemcpyHostToDevice, ctx->stream));
-  int32_t *d_poc = (int32_t *)(di + 2 * planes), *d_qp = d_poc + MLT_DEFER_CAP;
-  const DeferredOut od = deferred_out(dout, nl), oh = deferred_out(ho, nl);
+  const int b = (int)(df.gen & 1), n = df.n;
+  char *hi = df.h_in + (size_t)b * df.in.bytes(), *di = df.d_in + (size_t)b * df.in.bytes();
+  // org planes, pred planes, poc + qp: only the first n planes of each are live
+  HIP_TRY(ctx, hipMemcpyAsync(di + df.in.org.off, hi + df.in.org.off, (size_t)n * df.in.plane, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(di + df.in.pred.off, hi + df.in.pred.off, (size_t)n * df.in.plane, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(di + df.in.scalars().off, hi + df.in.scalars().off, df.in.scalars().bytes, hipMemcpyHostToDevice, ctx->stream));
   df.has_cand[b] = st->cand_used;
-  const PassIO io{Planes{(const int16_t *)di, (const int16_t *)(di + planes), size, (long)(df.plane / 2), size, (long)(df.plane / 2)}, d_poc, d_qp, od.split, od.lg, od.dec,
-                  df.has_cand[b] ? od.cand : nullptr};
-  GuardSlot g;
-  g.d_flat = od.flat; g.d_idx = od.idx; g.d_count = od.count; g.d_lg = od.lg; g.d_mag = od.mag; g.phase = &df.phase[b]; g.h_count = oh.count;
-  const int rc = run_fast_async(ctx, *st, n, io, g);
+  const DeferredIO d(st, df, b);
+  const int rc = run_fast_async(ctx, *st, n, d.io, d.g);
   df.guard_pending[b] = st->guards();
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ho, dout, deferred_fetch_bytes(nl, df.has_cand[b]), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(df.h_out + (size_t)b * df.out.bytes(), df.d_out + (size_t)b * df.out.bytes(), df.out.fetch_bytes(df.has_cand[b]), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipEventRecord(df.done[b], ctx->stream));
   df.n_launched[b] = n;
   df.gen_of_set[b] = df.gen;
@@ -588,22 +553,14 @@ int deferred_launch(mlt_ctx *ctx, SizeState *st, Deferred &df) {  // launch the 
 int deferred_guard_fixup(mlt_ctx *ctx, SizeState *st, Deferred &df, int b) {
   if (!df.guard_pending[b]) return MLT_OK;
   df.guard_pending[b] = false;
-  const int size = st->size, nl = st->model.n_logits;
-  char *di = df.d_in + (size_t)b * df.in_set, *ho = df.h_out + (size_t)b * df.out_set, *dout = df.d_out + (size_t)b * df.out_set;
-  const size_t planes = (size_t)MLT_DEFER_CAP * df.plane;
-  const DeferredOut od = deferred_out(dout, nl), oh = deferred_out(ho, nl);
+  const DeferredIO d(st, df, b);
   // (the set's two selection counters came back with the results: the launch counted on one and zeroed the other -- GuardSlot.phase -- so their sum is the count)
-  const int k = oh.count[0] + oh.count[1];
+  const int k = d.g.h_count[0] + d.g.h_count[1];
   if (k == 0) return MLT_OK;
   if (k < 0 || k > df.n_launched[b] || !st->guards()) { ctx->err = "guard: bad flagged-CU count"; return MLT_ERR_HIP; }
-  int32_t *d_poc = (int32_t *)(di + 2 * planes), *d_qp = d_poc + MLT_DEFER_CAP;
-  const PassIO io{Planes{(const int16_t *)di, (const int16_t *)(di + planes), size, (long)(df.plane / 2), size, (long)(df.plane / 2)}, d_poc, d_qp, od.split, od.lg, od.dec,
-                  df.has_cand[b] ? od.cand : nullptr};
-  GuardSlot g;
-  g.d_flat = od.flat; g.d_idx = od.idx; g.d_count = od.count; g.d_lg = od.lg; g.d_mag = od.mag; g.h_count = oh.count;
-  int rc = guard_fixup_async(ctx, *st, k, io, g);
+  int rc = guard_fixup_async(ctx, *st, k, d.io, d.g);
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ho, dout, deferred_fetch_bytes(nl, df.has_cand[b]), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(df.h_out + (size_t)b * df.out.bytes(), df.d_out + (size_t)b * df.out.bytes(), df.out.fetch_bytes(df.has_cand[b]), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return MLT_OK;
 }
@@ -628,31 +585,27 @@ int mlt_submit(mlt_ctx *ctx, const int16_t *org, int org_stride, const int16_t *
   if (rc) return rc;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
   Deferred &df = ctx->deferred[size_index(size)];
-  const int nl = st->model.n_logits;
   if (!df.h_in) {
-    df.plane = ((size_t)size * size * 2 + 255) / 256 * 256;
-    df.in_set = 2 * (size_t)MLT_DEFER_CAP * df.plane + (size_t)MLT_DEFER_CAP * 8;
-    df.out_set = (deferred_fetch_bytes(nl, true) + (size_t)MLT_DEFER_CAP * 12 + 255) / 256 * 256;
-    HIP_TRY(ctx, hipHostMalloc((void **)&df.h_in, 2 * df.in_set, hipHostMallocDefault));
-    HIP_TRY(ctx, hipHostMalloc((void **)&df.h_out, 2 * df.out_set, hipHostMallocDefault));
-    HIP_TRY(ctx, hipMalloc((void **)&df.d_in, 2 * df.in_set));
-    HIP_TRY(ctx, hipMalloc((void **)&df.d_out, 2 * df.out_set));
-    HIP_TRY(ctx, hipMemset(df.d_out, 0, 2 * df.out_set));   // (the selection's ticket words start at zero)
+    df.in = Lay::DeferIn(size, MLT_DEFER_CAP);
+    df.out = Lay::DeferOut(MLT_DEFER_CAP, st->model.n_logits);
+    HIP_TRY(ctx, hipHostMalloc((void **)&df.h_in, 2 * df.in.bytes(), hipHostMallocDefault));
+    HIP_TRY(ctx, hipHostMalloc((void **)&df.h_out, 2 * df.out.bytes(), hipHostMallocDefault));
+    HIP_TRY(ctx, hipMalloc((void **)&df.d_in, 2 * df.in.bytes()));
+    HIP_TRY(ctx, hipMalloc((void **)&df.d_out, 2 * df.out.bytes()));
+    HIP_TRY(ctx, hipMemset(df.d_out, 0, 2 * df.out.bytes()));   // (the selection's counters start at zero)
     for (int b = 0; b < 2; ++b) HIP_TRY(ctx, hipEventCreateWithFlags(&df.done[b], hipEventDisableTiming));
   }
   if (df.n == MLT_DEFER_CAP && (rc = deferred_launch(ctx, st, df))) return rc;  // full: flush, start the next generation
   const int b = (int)(df.gen & 1);
   if (df.n == 0 && df.gen_of_set[b] != ~0ull) HIP_TRY(ctx, hipEventSynchronize(df.done[b]));  // set b's previous batch fully drained
-  char *hi = df.h_in + (size_t)b * df.in_set;
-  const size_t planes = (size_t)MLT_DEFER_CAP * df.plane;
-  char *ho = hi + (size_t)df.n * df.plane, *hp = hi + planes + (size_t)df.n * df.plane;
+  char *hi = df.h_in + (size_t)b * df.in.bytes();
+  char *ho = hi + df.in.org.off + (size_t)df.n * df.in.plane, *hp = hi + df.in.pred.off + (size_t)df.n * df.in.plane;
   for (int y = 0; y < size; ++y) {  // the gather of EncCu.cpp:810-830
     std::memcpy(ho + (size_t)y * size * 2, org + (size_t)y * org_stride, (size_t)size * 2);
     std::memcpy(hp + (size_t)y * size * 2, pred + (size_t)y * pred_stride, (size_t)size * 2);
   }
-  int32_t *h_poc = (int32_t *)(hi + 2 * planes);
-  h_poc[df.n] = poc;
-  h_poc[MLT_DEFER_CAP + df.n] = qp;
+  df.in.at(hi).d_poc[df.n] = poc;
+  df.in.at(hi).d_qp[df.n] = qp;
   *ticket = df.gen * MLT_DEFER_CAP + (uint64_t)df.n;
   ++df.n;
   return MLT_OK;
@@ -700,11 +653,11 @@ static int wait_impl(mlt_ctx *ctx, int size, mlt_ticket ticket, int32_t *split_m
   if (cand && !df.has_cand[b]) { ctx->err = "the ticket's batch was flushed before the size had a candidate policy or a candidate call: it carries no candidate records"; return MLT_ERR_ARG; }
   HIP_TRY(ctx, hipEventSynchronize(df.done[b]));
   if ((rc = deferred_guard_fixup(ctx, st, df, b))) return rc;
-  const char *ho = df.h_out + (size_t)b * df.out_set;
-  if (split_mode) *split_mode = ((const int32_t *)ho)[slot];
-  if (logits_opt) std::memcpy(logits_opt, ho + (size_t)MLT_DEFER_CAP * 4 + (size_t)slot * nl * 4, (size_t)nl * 4);
-  if (dec) std::memcpy(dec, deferred_out(const_cast<char *>(ho), nl).dec + slot, sizeof(DecisionRec));
-  if (cand) std::memcpy(cand, deferred_out(const_cast<char *>(ho), nl).cand + slot, sizeof(CandRec));
+  const Lay::CuFields::Ptrs oh = df.out.at(df.h_out + (size_t)b * df.out.bytes());   // (the pinned mirror)
+  if (split_mode) *split_mode = oh.d_split[slot];
+  if (logits_opt) std::memcpy(logits_opt, oh.d_lg + (size_t)slot * nl, (size_t)nl * 4);
+  if (dec) std::memcpy(dec, oh.d_dec + slot, sizeof(DecisionRec));
+  if (cand) std::memcpy(cand, oh.d_cand + slot, sizeof(CandRec));
   return MLT_OK;
 }
 

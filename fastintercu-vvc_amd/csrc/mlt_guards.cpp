@@ -1,46 +1,32 @@
 // mlt_guards.cpp -- the parity guards of the host runtime (include/mltcnn.h: flat guard, decision guard, magnitude guard).
 #include "mlt_runtime.h"
 
-// ---- parity guards (include/mltcnn.h: flat guard, decision guard) --------------------------------------------------
-// Per batch: [flat_stat_kernel] -> fast network -> guard_select_kernel (ascending list of flagged CUs + count) -> 4-byte
-// D2H of the count.  Once the host knows the count k it enqueues, for k > 0: gather of the flagged CUs' planes -> exact
-// network on k CUs -> scatter of their split modes / logits over the fast results.
+// ---- parity guards (include/mltcnn.h: flat guard, decision guard, magnitude guard) ---------------------------------
+// Per batch: [flat_stat_kernel] -> fast network, whose heads kernel ends with the selection (an unordered list of the flagged CUs + their count; mlt_predict's one CU
+// likewise) -> 4-byte D2H of the count.  MLT_GUARD_SELECT_KERNEL: the selection as guard_select_kernel, a launch of its own (ascending list) -- the A/B form.  Once
+// the host knows the count k it enqueues, for k > 0: gather of the flagged CUs' planes -> exact network on k CUs -> scatter of their results over the fast ones.
 
 int guard_slot(mlt_ctx *ctx, int which, int n, int nl, GuardSlot *g) {
-  if (n > ctx->guard_cap_n || nl > ctx->guard_cap_nl || !ctx->guard_dev) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->guard_dev) (void)hipFree(ctx->guard_dev);
-    ctx->guard_dev = nullptr;
-    const int cn = n > ctx->guard_cap_n ? n : ctx->guard_cap_n, cl = nl > ctx->guard_cap_nl ? nl : ctx->guard_cap_nl;
-    const size_t ints = ((size_t)cn * 4 + 255) / 256 * 256;
-    ctx->guard_slot_bytes = 3 * ints + 256 + ((size_t)cn * cl * 4 + 255) / 256 * 256;
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->guard_dev, 2 * ctx->guard_slot_bytes));
-    HIP_TRY(ctx, hipMemset(ctx->guard_dev, 0, 2 * ctx->guard_slot_bytes));   // (the selection's ticket words must start at zero)
-    ctx->guard_cap_n = cn; ctx->guard_cap_nl = cl;
-  }
+  Lay::GuardLay &lay = ctx->guard_lay;
+  if ((size_t)n > lay.n || (size_t)nl > lay.nl) lay = Lay::GuardLay(std::max((size_t)n, lay.n), std::max((size_t)nl, lay.nl));
+  int rc;
+  if ((rc = ctx->guard_dev.reserve(ctx, 2 * lay.bytes(), "guard slots", true))) return rc;   // (the selection's counters must start at zero)
   if (!ctx->guard_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->guard_host, 64, hipHostMallocDefault));
-  const size_t ints = ((size_t)ctx->guard_cap_n * 4 + 255) / 256 * 256;
-  char *base = ctx->guard_dev + (size_t)which * ctx->guard_slot_bytes;
-  g->d_flat = (int32_t *)base; g->d_idx = (int32_t *)(base + ints); g->d_count = (int32_t *)(base + 2 * ints);
-  g->phase = &ctx->guard_phase[which];   // (the pair d_count[0 .. 1] sits inside the 256 bytes reserved for the count)
-  g->d_lg = (float *)(base + 2 * ints + 256);
-  g->d_mag = (float *)(base + 2 * ints + 256 + ((size_t)ctx->guard_cap_n * ctx->guard_cap_nl * 4 + 255) / 256 * 256);
-  g->h_count = ctx->guard_host + which;
+  *g = GuardSlot{lay.at(ctx->guard_dev.p + (size_t)which * lay.bytes()), &ctx->guard_phase[which], ctx->guard_host + which};
   return MLT_OK;
 }
 
 namespace {
 
-// the thresholds of the size's guards: what the selection -- as a tail of the heads kernel or as guard_select_kernel -- compares against
-struct GuardThr { int flat_thr, near_thr; float margin, mag_thr, band, cand_band; };
-GuardThr guard_thresholds(const mlt_ctx *ctx, const SizeState &st) {
+// the thresholds of the size's guards: what the selection -- as a tail of the heads kernel or as guard_select_kernel -- compares against (no pointers yet)
+GuardTail guard_thresholds(const mlt_ctx *ctx, const SizeState &st) {
   const int quads = st.size * st.size / 4;
-  GuardThr t;
+  GuardTail t{};
   t.flat_thr = quads / st.flat_div;  // >= 1/8 (tiers behind the magnitude guard, exact-lite tier: 1/16) of the quads exactly flat (constant / exactly linear in both planes)
   t.near_thr = quads / 2;            // or >= 1/2 of them near-flat (mlt_kernels.h: MLT_FLAT_RANGE)
   t.margin = st.margin_guard ? st.guard_margin : 0.f;
   t.mag_thr = st.mag_thr;
-  t.band = st.conf_band(ctx->tolerance);
+  t.conf_band = st.conf_band(ctx->tolerance);
   t.cand_band = st.cand_band(ctx->tolerance);
   return t;
 }
@@ -52,18 +38,18 @@ GuardThr guard_thresholds(const mlt_ctx *ctx, const SizeState &st) {
 // caller then re-evaluates them with guard_fixup_async.  io.logits may be NULL.
 int run_fast_async(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io, const GuardSlot &g) {
   if (!st.guards()) return run_network(ctx, st, st.main_cfg(), n, io);
-  const GuardThr thr = guard_thresholds(ctx, st);
+  GuardTail tail = guard_thresholds(ctx, st);
   int rc;
   PassIO fast = io;
-  if (!fast.logits && st.margin_guard) fast.logits = g.d_lg;
+  if (!fast.logits && st.margin_guard) fast.logits = g.d.lg;
   GuardOut go;
-  go.d_flat = st.flat_guard ? g.d_flat : nullptr;
-  GuardTail tail{nullptr, g.d_idx, go.d_flat, thr.flat_thr, thr.near_thr, thr.margin, thr.mag_thr, nullptr, thr.band, thr.cand_band};
+  go.d_flat = st.flat_guard ? g.d.flat : nullptr;
+  tail.idx = g.d.idx; tail.flat = go.d_flat;
   if (g.single && n == 1) {
     // one CU (mlt_predict's captured graph): the selection is a tail of the heads kernel -- no guard_select launch, no memset of the
     // statistic (the tail clears it for the next call; it is only consumed when the first kernel is the one that produces it: aligned planes,
     // S >= 64 -- else flat_stat_kernel overwrites it), no separate copy of the count (the caller's result copy carries it)
-    tail.count = g.d_count;
+    tail.count = g.d.count;
     go.tail = &tail; go.flat_is_clear = true;
     return run_network(ctx, st, st.main_cfg(), 1, fast, go);
   }
@@ -72,64 +58,57 @@ int run_fast_async(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io, const G
     // zero on entry; the launch zeroes the slot's OTHER counter for the next one (whose predecessor's count has left the device by then: same stream).  One launch and
     // one launch gap less per step.  (A first version counted finished workgroups to let the last one publish and re-arm a single counter: 4096 same-address atomics
     // and release fences made the heads launch 0.123 ms instead of 0.030 -- more than the launch it saved.)
-    tail.count = g.d_count + *g.phase; tail.next = g.d_count + (*g.phase ^ 1);
+    tail.count = g.d.count + *g.phase; tail.next = g.d.count + (*g.phase ^ 1);
     go.tail = &tail;
     if ((rc = run_network(ctx, st, st.main_cfg(), n, fast, go))) {
       // a pass that failed (e.g. no memory for the workspace of an oversized batch -- the caller may come back with a smaller one) may or may not have run its heads
       // kernel: both counters back to zero, the phase stays -- whichever counter the next launch counts on is zero on entry
-      (void)hipMemsetAsync(g.d_count, 0, 8, ctx->stream);
+      (void)hipMemsetAsync(g.d.count, 0, 8, ctx->stream);
       return rc;
     }
     *g.phase ^= 1;
     HIP_TRY(ctx, hipMemcpyAsync(g.h_count, tail.count, 4, hipMemcpyDeviceToHost, ctx->stream));
     return MLT_OK;
   }
-  go.d_mag = st.mag_thr > 0.f ? g.d_mag : nullptr;
+  go.d_mag = st.mag_thr > 0.f ? g.d.mag : nullptr;
   if ((rc = run_network(ctx, st, st.main_cfg(), n, fast, go))) return rc;
   GuardSelectArgs sa{};
-  sa.mag = go.d_mag; sa.mag_thr = thr.mag_thr;
+  sa.mag = go.d_mag; sa.mag_thr = tail.mag_thr;
   sa.flat = go.d_flat;
   sa.logits = st.margin_guard ? fast.logits : nullptr;
-  sa.idx = g.d_idx; sa.count = g.d_count; sa.n = n; sa.n_logits = st.model.n_logits;
-  int off = 0;
-  for (int h = 0; h < st.head_index; ++h) off += st.model.heads[h].classes;
-  sa.head_off = off; sa.head_classes = st.model.heads[st.head_index].classes;
-  sa.flat_thr = thr.flat_thr; sa.near_thr = thr.near_thr; sa.margin = thr.margin;
-  sa.min_conf = st.min_conf; sa.conf_band = thr.band;
-  sa.cand_cov = st.cand_cov; sa.cand_max = st.cand_max; sa.cand_band = thr.cand_band;
+  sa.idx = g.d.idx; sa.count = g.d.count; sa.n = n; sa.n_logits = st.model.n_logits;
+  sa.head_off = st.head_off(); sa.head_classes = st.head_classes();
+  sa.flat_thr = tail.flat_thr; sa.near_thr = tail.near_thr; sa.margin = tail.margin;
+  sa.min_conf = st.min_conf; sa.conf_band = tail.conf_band;
+  sa.cand_cov = st.cand_cov; sa.cand_max = st.cand_max; sa.cand_band = tail.cand_band;
   Launch L{ctx};
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if ((rc = L.prof_begin("guard_select", 0.0, 0.0, e0, e1))) return rc;
   LAUNCH_TRY(ctx, mlt_launch_guard_select(sa, ctx->stream));
   if ((rc = L.prof_end(e1))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(g.h_count, g.d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(g.h_count, g.d.count, 4, hipMemcpyDeviceToHost, ctx->stream));
   return MLT_OK;
 }
 
-// k > 0 flagged CUs (g.d_idx) of a batch whose fast results are in io.split / io.logits / io.dec / io.cand: exact re-evaluation, asynchronous.
+// k > 0 flagged CUs (g.d.idx) of a batch whose fast results are in io.split / io.logits / io.dec / io.cand: exact re-evaluation, asynchronous.
 int guard_fixup_async(mlt_ctx *ctx, SizeState &st, int k, const PassIO &io, const GuardSlot &g) {
   const int S = st.size, nl = st.model.n_logits;
   const StageSet lay(S, k, nl, io.dec != nullptr, io.cand != nullptr);
-  if (lay.bytes() > ctx->gstage_bytes) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->gstage) (void)hipFree(ctx->gstage);
-    ctx->gstage = nullptr; ctx->gstage_bytes = 0;
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->gstage, lay.bytes()));
-    ctx->gstage_bytes = lay.bytes();
-  }
-  const StageSet::Ptrs gs = lay.at(ctx->gstage);
+  int rc = ctx->gstage.reserve(ctx, lay.bytes(), "guard staging");
+  if (rc) return rc;
+  const StageSet::Ptrs gs = lay.at(ctx->gstage.p);
   GuardGatherArgs ga{};
   io.pl.fill(ga);
-  ga.poc = io.poc; ga.qp = io.qp; ga.idx = g.d_idx; ga.k = k; ga.s_l = ilog2(S);
+  ga.poc = io.poc; ga.qp = io.qp; ga.idx = g.d.idx; ga.k = k; ga.s_l = ilog2(S);
   ga.g_org = gs.d_org; ga.g_pred = gs.d_pred; ga.g_poc = gs.d_poc; ga.g_qp = gs.d_qp;
   HIP_TRY(ctx, mlt_launch_guard_gather(ga, ctx->stream));
   // (the re-run's heads kernel applies the size's confidence gate to the gathered split modes and fills the flagged CUs' records -- decision and candidate -- from the exact logits)
-  int rc = run_network(ctx, st, st.exact_cfg(), k, PassIO{Planes::dense(gs.d_org, gs.d_pred, S), gs.d_poc, gs.d_qp, gs.d_split, gs.d_lg, gs.d_dec, gs.d_cand});
+  rc = run_network(ctx, st, st.exact_cfg(), k, PassIO{Planes::dense(gs.d_org, gs.d_pred, S), gs.d_poc, gs.d_qp, gs.d_split, gs.d_lg, gs.d_dec, gs.d_cand});
   if (rc) return rc;
   GuardScatterArgs sc{};
   sc.g_dec = gs.d_dec; sc.dec = io.dec;
   sc.g_cand = gs.d_cand; sc.cand = io.cand;
-  sc.idx = g.d_idx; sc.g_split = gs.d_split; sc.g_logits = gs.d_lg; sc.split = io.split; sc.logits = io.logits; sc.k = k; sc.n_logits = nl;
+  sc.idx = g.d.idx; sc.g_split = gs.d_split; sc.g_logits = gs.d_lg; sc.split = io.split; sc.logits = io.logits; sc.k = k; sc.n_logits = nl;
   HIP_TRY(ctx, mlt_launch_guard_scatter(sc, ctx->stream));
   st.reruns += (uint64_t)k;
   return MLT_OK;

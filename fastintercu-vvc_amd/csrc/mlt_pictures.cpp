@@ -36,9 +36,9 @@ int predict_at_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &pl, int n, co
   const int cap = n < dev->chunk ? n : dev->chunk;
   const StageSet lay(size, cap, nl, out.dec != nullptr && !at.device, out.cand != nullptr && !at.device);
   int rc;
-  if ((rc = ensure_stage(dev, lay.bytes() + (at.device ? 0 : StageSet::up256((size_t)cap * 8))))) return rc;   // the set, then the chunk's positions
-  const StageSet::Ptrs S = lay.at(dev->stage);
-  int32_t *d_xy = (int32_t *)(dev->stage + lay.bytes());
+  if ((rc = dev->stage.reserve(dev, lay.bytes() + (at.device ? 0 : Lay::up256((size_t)cap * 8)), "staging"))) return rc;   // the set, then the chunk's positions
+  const StageSet::Ptrs S = lay.at(dev->stage.p);
+  int32_t *d_xy = (int32_t *)(dev->stage.p + lay.bytes());
   if (at.device) {   // one (poc, qp) pair: filled once, every chunk reads its first c entries
     HIP_TRY(dev, hipMemsetD32Async((hipDeviceptr_t)S.d_poc, at.poc_all, (size_t)cap, dev->stream));
     HIP_TRY(dev, hipMemsetD32Async((hipDeviceptr_t)S.d_qp, at.qp_all, (size_t)cap, dev->stream));
@@ -179,28 +179,14 @@ int mlt_predict_at(mlt_ctx *ctx, int size, const mlt_picture *org, const mlt_pic
     }
   }
   const AtOut out{split_mode_opt, logits_opt, dec_opt, cand_opt};
-  const int G = (int)org->plane.size();   // (both pictures belong to ctx: a plane per device of it)
-  if (G > 1 && n > 1) {
-    // multi-device context: contiguous shards, one host thread per further device, every device gathers from its own copy of the planes (predict_batch_impl)
-    const int nlg = st->model.n_logits, si = size_index(size);
-    std::vector<int> rcs((size_t)G, MLT_OK);
-    auto run = [&](int g) {
-      const int lo = shard_lo(n, g, G), hi = shard_lo(n, g + 1, G);
-      if (hi <= lo) return;
+  if (!ctx->peers.empty() && n > 1)   // every device gathers from its own copy of the planes (both pictures belong to ctx: a plane per device of it)
+    return run_sharded(ctx, n, [&](int g, int lo, int hi) -> int {
       mlt_ctx *dev = device_of(ctx, g);
-      SizeState *sg = &dev->sz[si];
-      if (!sg->enabled || !sg->loaded) { dev->err = "CU size not enabled or weights not loaded"; rcs[(size_t)g] = MLT_ERR_SIZE_DISABLED; return; }
-      const AtOut o{out.split ? out.split + lo : nullptr, out.logits ? out.logits + (size_t)lo * nlg : nullptr, out.dec ? out.dec + lo : nullptr, out.cand ? out.cand + lo : nullptr};
-      rcs[(size_t)g] = predict_at_chunks(dev, sg, AtPlanes::of(org, pred, g), hi - lo, AtList::host(xy + 2 * (size_t)lo, poc + lo, qp + lo), o);
-    };
-    std::vector<std::thread> th;
-    for (int g = 1; g < G; ++g) th.emplace_back(run, g);
-    run(0);
-    for (std::thread &t : th) t.join();
-    for (int g = 0; g < G; ++g)
-      if (rcs[(size_t)g]) { if (g) ctx->err = "device " + std::to_string(device_of(ctx, g)->device) + ": " + device_of(ctx, g)->err; return rcs[(size_t)g]; }
-    return MLT_OK;
-  }
+      SizeState *sg = &dev->sz[size_index(size)];
+      if (!sg->enabled || !sg->loaded) { dev->err = "CU size not enabled or weights not loaded"; return MLT_ERR_SIZE_DISABLED; }
+      const AtOut o{out.split ? out.split + lo : nullptr, out.logits ? out.logits + (size_t)lo * sg->model.n_logits : nullptr, out.dec ? out.dec + lo : nullptr, out.cand ? out.cand + lo : nullptr};
+      return predict_at_chunks(dev, sg, AtPlanes::of(org, pred, g), hi - lo, AtList::host(xy + 2 * (size_t)lo, poc + lo, qp + lo), o);
+    });
   return predict_at_chunks(ctx, st, AtPlanes::of(org, pred, 0), n, AtList::host(xy, poc, qp), out);
 }
 

@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstddef>
@@ -23,6 +24,7 @@
 
 #include "../../include/mltcnn.h"
 #include "mlt_kernels.h"
+#include "mlt_layout.h"
 #include "mlt_model.h"
 #include "mlt_tier_search.h"
 
@@ -153,6 +155,9 @@ struct SizeState {
   double guard_us[16] = {0};
   int guard_n[16] = {0};
   int size = 0, head_index = 0;
+  // the decision head inside a CU's logits: first logit, class count
+  int head_off() const { int off = 0; for (int h = 0; h < head_index; ++h) off += model.heads[h].classes; return off; }
+  int head_classes() const { return model.heads[head_index].classes; }
   float min_conf = 0.f;        // confidence gate (mlt_set_confidence_gate): split = -1 unless the decision head's softmax probability reaches it.  0: off.  Not a
                                // property of the weights: (re)loads and calibrations keep it
   // the gate guard's band (mlt_kernels.h: MLT_CONF_BAND_FRAC x the tolerance the tier was calibrated against); 0 unless gate and decision guard are both on
@@ -183,25 +188,35 @@ struct SizeState {
   NetCfg exact_cfg() { NetCfg c; c.S = size; c.m = &model_exact; return c; }
 };
 
-// device-side guard state of one in-flight batch (mlt_kernels.hip: flat_stat / guard_select kernels)
+// guard state of one in-flight batch (mlt_kernels.hip: flat_stat / guard_select kernels): any layout's guard fields on the device, {fields.at(base), phase, h_count[, single]}
 struct GuardSlot {
-  int32_t *d_flat = nullptr, *d_idx = nullptr, *d_count = nullptr;
-  float *d_lg = nullptr;       // logits for the margin test when the caller wants none
-  float *d_mag = nullptr;      // per-CU logit magnitude (HeadArgs.mag) for the magnitude guard
-  int *phase = nullptr;        // batches with the selection inside the heads kernel: d_count[*phase] is the launch's running count (zero on entry), d_count[*phase ^ 1] the
+  Lay::GuardFields::Ptrs d{};
+  int *phase = nullptr;        // batches with the selection inside the heads kernel: d.count[*phase] is the launch's running count (zero on entry), d.count[*phase ^ 1] the
                                // one it zeroes for the NEXT launch of the slot; toggled per launch (run_guarded_async).  NULL: no such pair (the slot serves one-CU launches)
   int32_t *h_count = nullptr;  // pinned
-  bool single = false;         // mlt_predict's slot: one CU, d_flat zero on entry and cleared by the heads kernel (consume-and-clear), the
+  bool single = false;         // mlt_predict's slot: one CU, d.flat zero on entry and cleared by the heads kernel (consume-and-clear), the
                                // selection rides on the heads kernel, and the caller's own result copy brings the count back
 };
-// guard selection fused into the heads kernel of a single-CU launch (HeadArgs.g_*)
+// the thresholds of a size's guards (guard_thresholds) and, with the pointers set, the selection as a tail of the heads kernel (HeadArgs.g_*)
 struct GuardTail { int32_t *count, *idx, *flat; int flat_thr, near_thr; float margin, mag_thr; int32_t *next; float conf_band, cand_band; };  // next != NULL: batches (HeadArgs.g_next)
 
+using Lay::StageSet;
+
+// A grow-only buffer of a context, device memory or (pinned) page-locked host memory: reserve() keeps the allocation when it is large enough, else synchronises
+// the context's stream, frees and allocates anew (zero: cleared).  hipErrorOutOfMemory -> MLT_ERR_NOMEM; `what` opens the message.
+struct GrowBuf {
+  bool pinned = false;
+  char *p = nullptr;
+  size_t bytes = 0;
+  int reserve(mlt_ctx *ctx, size_t want, const char *what, bool zero = false);
+  void release() { if (p) (void)(pinned ? hipHostFree(p) : hipFree(p)); p = nullptr; bytes = 0; }
+};
+
 // mlt_predict (one CU per call, the encoder's use): pinned host staging, one H2D, the kernel chain replayed from a
-// hipGraph captured once per CU size, one D2H.
+// hipGraph captured once per CU size and call kind, one D2H.
 struct SingleCu {
-  char *h_stage = nullptr, *d_stage = nullptr;  // [org plane][pred plane][poc, qp, split, pad, logits...]
-  size_t plane = 0;
+  char *h_stage = nullptr, *d_stage = nullptr;  // Lay::SingleLay, twice: planes, poc, qp | split, flagged count, logits, record, candidate record | the guards' scratch
+  Lay::SingleLay lay;
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
   uint64_t ws_gen_at_capture = 0;       // the graph bakes in workspace pointers: valid only for the workspace allocation it was captured on
@@ -211,9 +226,10 @@ struct SingleCu {
 // mlt_submit / mlt_flush / mlt_wait: two generations of up to MLT_DEFER_CAP CUs per size (one accumulating, one in
 // flight or finished).  Generation g uses buffer set g & 1; ticket = g * MLT_DEFER_CAP + slot.
 struct Deferred {
-  char *h_in = nullptr, *d_in = nullptr;    // [2 sets][org planes CAP][pred planes CAP][poc CAP][qp CAP]
-  char *h_out = nullptr, *d_out = nullptr;  // [2 sets][split CAP][logits CAP * nl]
-  size_t in_set = 0, out_set = 0, plane = 0;
+  char *h_in = nullptr, *d_in = nullptr;    // [2 sets] of Lay::DeferIn: org planes, pred planes, poc, qp
+  char *h_out = nullptr, *d_out = nullptr;  // [2 sets] of Lay::DeferOut: split, logits, flagged count, records, candidate records | the guards' scratch
+  Lay::DeferIn in;
+  Lay::DeferOut out;
   uint64_t gen = 0;                         // generation being filled
   int n = 0;                                // CUs submitted into it
   int n_launched[2] = {0, 0};               // CUs of the generation occupying each set (0: never launched)
@@ -262,28 +278,23 @@ struct mlt_ctx {
   hipStream_t copy_stream = nullptr;
   hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
   int stage_chunk = 512;  // measured on 4096 x 128x128 from pinned memory: 512 -> 526 k, 1024 -> 498 k, 2048 -> 426 k CU/s
-  char *h_res = nullptr;  // pinned result staging (split + logits) for the two sets
-  size_t h_res_bytes = 0;
+  GrowBuf h_res{true};  // pinned result staging for the two sets (Lay::ResultSet: split, logits, records, candidate records)
   SingleCu single[12];  // [4 + si]: the calls that want the decision record (their graph bakes the record pointer into the heads kernel's arguments); [8 + si]: the
                         // calls that want the candidate record (and the decision record with it)
   Deferred deferred[4];
   // staging for the host-pointer entry points
-  char *stage = nullptr;
-  size_t stage_bytes = 0;
+  GrowBuf stage;
   // parity guards: selection buffers for two in-flight batches, gather staging for the flagged CUs
   float tolerance = 1e-3f;
   bool xlite = false;  // MLT_FLAG_EXACT_LITE: sizes configured exact run the exact-lite arithmetic (FP8 cross terms, mlt_model.h: xl)
-  char *guard_dev = nullptr;
-  size_t guard_slot_bytes = 0;
-  int guard_cap_n = 0, guard_cap_nl = 0;
+  GrowBuf guard_dev;              // two slots of guard_lay, zero when allocated
+  Lay::GuardLay guard_lay;        // (sized for the largest batch and logit count seen: a slot's counters stay where they are while the buffer does)
   int32_t *guard_host = nullptr;  // pinned: two counters
   int guard_phase[2] = {0, 0};    // which counter of a slot's pair the next batch launch counts on (GuardSlot.phase)
   hipEvent_t ev_guard = nullptr;  // "count of flagged CUs has landed" (device-pointer entry)
-  char *gstage = nullptr;
-  size_t gstage_bytes = 0;
-  // mlt_predict_tree's device arena (grow-only: nodes, positions, per-node logits and records, roots, leaf map, count) and its pinned count
-  char *tree_dev = nullptr;
-  size_t tree_bytes = 0;
+  GrowBuf gstage;
+  // mlt_predict_tree's device arena (Lay::TreeArena) and its pinned count
+  GrowBuf tree_dev;
   int32_t *tree_host = nullptr;
   std::vector<mlt_picture *> pictures;  // every picture created on / wrapped for this context (mlt_pictures.cpp); what is left is released by mlt_shutdown
   std::string err;
@@ -365,23 +376,6 @@ struct GuardOut {
   float *d_mag = nullptr;           // per-CU logit magnitude (HeadArgs.mag)
 };
 
-// One staging set for `cap` dense CUs in device memory: org | pred | poc | qp | split | logits [| records] [| candidate records], every part rounded up to 256 bytes
-// (so every pointer keeps the alignment the quad-fetching kernels want).
-struct StageSet {
-  struct Ptrs { int16_t *d_org, *d_pred; int32_t *d_poc, *d_qp, *d_split; float *d_lg; DecisionRec *d_dec; CandRec *d_cand; };
-  size_t plane, small, lgb, decb, candb;
-  static size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-  StageSet(int S, int cap, int nl, bool records, bool cands = false)
-      : plane(up256((size_t)S * S * 2 * cap)), small(up256((size_t)cap * 4)), lgb(up256((size_t)cap * nl * 4)), decb(records ? up256((size_t)cap * sizeof(DecisionRec)) : 0),
-        candb(cands ? up256((size_t)cap * sizeof(CandRec)) : 0) {}
-  size_t bytes() const { return 2 * plane + 3 * small + lgb + decb + candb; }
-  Ptrs at(char *base) const {
-    return Ptrs{(int16_t *)base, (int16_t *)(base + plane), (int32_t *)(base + 2 * plane), (int32_t *)(base + 2 * plane + small), (int32_t *)(base + 2 * plane + 2 * small),
-                (float *)(base + 2 * plane + 3 * small), decb ? (DecisionRec *)(base + 2 * plane + 3 * small + lgb) : nullptr,
-                candb ? (CandRec *)(base + 2 * plane + 3 * small + lgb + decb) : nullptr};
-  }
-};
-
 // profile / plan bookkeeping around one kernel launch (mlt_dispatch.cpp)
 struct Launch {
   mlt_ctx *ctx;
@@ -392,10 +386,22 @@ struct Launch {
 // contiguous shard of n items for device g of G (fastintercu-vvc_amd/shard.py: shard_bounds)
 inline int shard_lo(int n, int g, int G) { return (int)(((long long)n * g) / G); }
 inline mlt_ctx *device_of(mlt_ctx *ctx, int i) { return i == 0 ? ctx : ctx->peers[(size_t)i - 1]; }
+// A call on n items of a multi-device context: per_device(g, lo, hi) on device g's shard, one host thread per further device, no exchange between them (every
+// device runs the single-device path, so the results are those of one device).  The first failing device's code; a peer's message is prefixed "device N: ".
+template <class F> int run_sharded(mlt_ctx *ctx, int n, F per_device) {
+  const int G = 1 + (int)ctx->peers.size();
+  std::vector<int> rcs((size_t)G, MLT_OK);
+  auto run = [&](int g) { const int lo = shard_lo(n, g, G), hi = shard_lo(n, g + 1, G); if (hi > lo) rcs[(size_t)g] = per_device(g, lo, hi); };
+  std::vector<std::thread> th;
+  for (int g = 1; g < G; ++g) th.emplace_back(run, g);
+  run(0);
+  for (std::thread &t : th) t.join();
+  for (int g = 0; g < G; ++g)
+    if (rcs[(size_t)g]) { if (g) ctx->err = "device " + std::to_string(device_of(ctx, g)->device) + ": " + device_of(ctx, g)->err; return rcs[(size_t)g]; }
+  return MLT_OK;
+}
 
 // ---- functions that cross translation units ----
-// mlt_api.cpp
-int ensure_stage(mlt_ctx *ctx, size_t bytes);   // the context's staging for the host-array entry points holds at least `bytes`
 // mlt_pictures.cpp
 void free_pictures(mlt_ctx *ctx);               // mlt_shutdown: before the peers go
 bool owns_picture(const mlt_ctx *ctx, const mlt_picture *pic);
@@ -414,8 +420,6 @@ struct AtList {
 };
 struct AtOut { int32_t *split; float *logits; mlt_decision *dec; mlt_candidates *cand; };
 int predict_at_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &pl, int n, const AtList &at, const AtOut &out);
-// mlt_tree.cpp
-void free_tree(mlt_ctx *ctx);                   // mlt_shutdown
 // mlt_dispatch.cpp
 void release_ws(mlt_ctx *ctx);
 int run_network(mlt_ctx *ctx, SizeState &st, const NetCfg &c, int n, const PassIO &io, const GuardOut &go = GuardOut());

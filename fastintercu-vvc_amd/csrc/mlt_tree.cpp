@@ -10,7 +10,7 @@
 namespace {
 
 const int kMinDim = 16, kMaxDim = 16384;   // a picture's geometry (mlt_picture_create)
-const int kRowLogits = MLT_MAX_LOGITS;     // floats the arena reserves per node (a level's logits are dense [n][n_logits] from the level's first row)
+const int kRowLogits = Lay::TreeArena::kRow;   // floats the arena reserves per node (a level's logits are dense [n][n_logits] from the level's first row)
 
 bool tree_sizes(int &top, int &mn) {
   if (top == 0) top = 128;
@@ -34,44 +34,7 @@ int roots_of(int w, int h, int top, int S, int32_t *xy, int cap) {
   return (int)count;
 }
 
-size_t up256(size_t b) { return StageSet::up256(b); }
-
-struct Arena {
-  TreeNodeRec *nodes; int32_t *xy; float *logits; DecisionRec *dec; CandRec *cand; int32_t *roots; uint8_t *map; int32_t *count;
-};
-// nodes | xy | logits | decision records | [candidate records] | roots | map | count
-int ensure_arena(mlt_ctx *ctx, size_t n, size_t n_roots, size_t map_bytes, bool cands, Arena *a) {
-  const size_t b_nodes = up256(n * sizeof(TreeNodeRec)), b_xy = up256(n * 8), b_lg = up256(n * kRowLogits * 4), b_dec = up256(n * sizeof(DecisionRec)),
-               b_cand = cands ? up256(n * sizeof(CandRec)) : 0, b_roots = up256(n_roots * 8), b_map = up256(map_bytes);
-  const size_t bytes = b_nodes + b_xy + b_lg + b_dec + b_cand + b_roots + b_map + 256;
-  if (bytes > ctx->tree_bytes) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->tree_dev) (void)hipFree(ctx->tree_dev);
-    ctx->tree_dev = nullptr; ctx->tree_bytes = 0;
-    hipError_t e = hipMalloc((void **)&ctx->tree_dev, bytes);
-    if (e != hipSuccess) { ctx->err = std::string("mlt_predict_tree: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? MLT_ERR_NOMEM : MLT_ERR_HIP; }
-    ctx->tree_bytes = bytes;
-  }
-  if (!ctx->tree_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->tree_host, 64, hipHostMallocDefault));
-  char *p = ctx->tree_dev;
-  a->nodes = (TreeNodeRec *)p; p += b_nodes;
-  a->xy = (int32_t *)p; p += b_xy;
-  a->logits = (float *)p; p += b_lg;
-  a->dec = (DecisionRec *)p; p += b_dec;
-  a->cand = cands ? (CandRec *)p : nullptr; p += b_cand;
-  a->roots = (int32_t *)p; p += b_roots;
-  a->map = (uint8_t *)p; p += b_map;
-  a->count = (int32_t *)p;
-  return MLT_OK;
-}
-
 }  // namespace
-
-void free_tree(mlt_ctx *ctx) {
-  if (ctx->tree_dev) (void)hipFree(ctx->tree_dev);
-  if (ctx->tree_host) (void)hipHostFree(ctx->tree_host);
-  ctx->tree_dev = nullptr; ctx->tree_bytes = 0; ctx->tree_host = nullptr;
-}
 
 extern "C" {
 #pragma GCC visibility push(default)
@@ -107,7 +70,7 @@ int mlt_predict_tree(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pr
     if ((rc = check_size(ctx, S, &st[L]))) return rc;
     const uint32_t m = cfg->descend_mask[size_index(S)];
     mask[L] = m ? m : 1u << 1;
-    const int K = st[L]->model.heads[st[L]->head_index].classes;
+    const int K = st[L]->head_classes();
     if (mask[L] >> K) {
       char msg[160];
       std::snprintf(msg, sizeof msg, "mlt_predict_tree: descend_mask of size %d names a class at or above the %d classes of its decision head", S, K);
@@ -141,8 +104,10 @@ int mlt_predict_tree(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pr
   }
   const int map_w = W / 16, map_h = H / 16;
   const size_t map_bytes = (size_t)map_w * map_h;
-  Arena A;
-  if ((rc = ensure_arena(ctx, (size_t)max_nodes, roots.size() / 2, map_bytes, any_cand, &A))) return rc;
+  const Lay::TreeArena arena((size_t)max_nodes, roots.size() / 2, map_bytes, any_cand);
+  if ((rc = ctx->tree_dev.reserve(ctx, arena.bytes(), "mlt_predict_tree"))) return rc;
+  if (!ctx->tree_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->tree_host, 64, hipHostMallocDefault));
+  const Lay::TreeArena::Ptrs A = arena.at(ctx->tree_dev.p);
   if (!roots.empty()) HIP_TRY(ctx, hipMemcpyAsync(A.roots, roots.data(), roots.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(A.map, 0xFF, map_bytes, ctx->stream));
   const AtPlanes pl = AtPlanes::of(org, pred, 0);
@@ -176,9 +141,7 @@ int mlt_predict_tree(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pr
     }
     ea.lvl_start = start; ea.lvl_n = n; ea.size = S; ea.depth = l;
     ea.dec = d_dec; ea.cand = d_cand; ea.logits = d_lg; ea.n_logits = nl;
-    int off = 0;
-    for (int h = 0; h < s->head_index; ++h) off += s->model.heads[h].classes;
-    ea.head_off = off; ea.head_classes = s->model.heads[s->head_index].classes;
+    ea.head_off = s->head_off(); ea.head_classes = s->head_classes();
     ea.descend_mask = last ? 0u : mask[l];
     ea.next_roots = last ? nullptr : A.roots + 2 * (size_t)root_off[l + 1];
     ea.n_next_roots = last ? 0 : n_roots[l + 1];

@@ -515,6 +515,74 @@ def test_pipelined_host_batch_equals_single_pass(gpu):
     m.close()
 
 
+def _guarded_batch_with_flat_cus(pkg, size, n, seed, flat_at):
+    """n seeded CUs with a KIND_FLAT CU (the flat guard re-runs it exactly) at every index of flat_at; the others are checked against the CPU oracle to lie far from
+    everything the decision guard and the candidate guard look at -- top-2 margin of the decision head > 0.1 where the guard's threshold is 3e-3, every cumulative
+    rank probability > 0.01 from the 0.9 coverage where the guard's band is 7.5e-4, with fast logits within 1e-3 of the oracle -- so the flat CUs are the only re-runs."""
+    import oracle
+    org, pred = pkg.synth.make_patches(size, n, seed)
+    of, pf = pkg.synth.make_patches(size, len(flat_at), seed + 1, pkg.synth.KIND_FLAT)
+    for j, i in enumerate(flat_at):
+        org[i], pred[i] = of[j], pf[j]
+    poc, qp = pkg.synth.make_scalars(n, seed)
+    blob = pkg.weights.synthetic_blob(0, 21)
+    ref, _ = oracle.Oracle(blob).forward(org, pred, poc, qp)
+    head = np.delete(ref[:, 5:9].astype(np.float64), flat_at, axis=0)   # CTU model decision head = element [2]
+    top = np.sort(head, axis=1)
+    prob = np.exp(head - head.max(1, keepdims=True))
+    cum = np.cumsum(-np.sort(-prob / prob.sum(1, keepdims=True), axis=1), axis=1)
+    assert (top[:, -1] - top[:, -2]).min() > 0.1 and np.abs(cum - 0.9).min() > 0.01
+    return blob, org, pred, poc, qp
+
+
+def test_pipelined_host_batch_with_every_output_equals_the_device_entry(gpu, monkeypatch):
+    """mlt_predict_batch / _decisions / _candidates through the two staging sets and the two pinned result sets, both reused (8-CU sub-chunks: 8 + 8 + 8 + 5), with an
+    exact re-run in every sub-chunk: split modes, logits, decision records and candidate records are those of mlt_predict_batch_device* on the same context (one
+    pass, no staging set, no pinned result set), byte for byte, and every call re-runs the four flat CUs and nothing else."""
+    import torch
+    pkg = gpu
+    size, n, flat_at = 128, 29, [2, 9, 18, 26]
+    blob, org, pred, poc, qp = _guarded_batch_with_flat_cus(pkg, size, n, 42, flat_at)
+    monkeypatch.setenv("MLT_TUNING", "1")
+    monkeypatch.setenv("MLT_STAGE_CHUNK", "8")
+    m = _ctx(pkg, size, blob, flags=pkg.capi.FLAG_NO_CALIBRATION)
+    m.set_candidate_policy(size, 0.9, 0)
+    dev = torch.device("cuda", 0)
+    t_in = [torch.from_numpy(x).to(dev) for x in (org, pred, poc, qp)]
+    d = [t.data_ptr() for t in t_in]
+    d_split = torch.full((n,), -7, dtype=torch.int32, device=dev)
+    d_lg = torch.zeros((n, 9), dtype=torch.float32, device=dev)
+    d_dec = torch.zeros((n, 48), dtype=torch.uint8, device=dev)
+    d_cand = torch.zeros((n, 40), dtype=torch.uint8, device=dev)
+    reruns = lambda: m.arithmetic(size)["guard_reruns"]
+    r0 = reruns()
+    m.predict_batch_device(n, size, *d, d_split.data_ptr(), d_lg.data_ptr())
+    m.predict_batch_device(n, size, *d, None, None, d_decisions=d_dec.data_ptr(), d_candidates=d_cand.data_ptr())
+    m.synchronize()
+    assert reruns() == r0 + 8
+    want_split, want_lg = d_split.cpu().numpy(), d_lg.cpu().numpy()
+    want_dec, want_cand = d_dec.cpu().numpy().tobytes(), d_cand.cpu().numpy().tobytes()
+    assert (want_split[flat_at] >= 0).all() and len(set(want_dec)) > 2 and len(set(want_cand)) > 2
+
+    def call(fn, *a, **kw):
+        before = reruns()
+        out = fn(org, pred, poc, qp, *a, **kw)
+        assert reruns() == before + 4, fn.__name__
+        return out
+
+    split, lg = call(m.predict_batch)
+    assert np.array_equal(split, want_split) and np.array_equal(lg, want_lg)
+    split, none = call(m.predict_batch, want_logits=False)
+    assert none is None and np.array_equal(split, want_split)
+    dec, lg = call(m.predict_batch_decisions)
+    assert dec.tobytes() == want_dec and np.array_equal(lg, want_lg) and np.array_equal(dec["split_mode"], want_split)
+    cand, dec, lg = call(m.predict_batch_candidates)
+    assert cand.tobytes() == want_cand and dec.tobytes() == want_dec and np.array_equal(lg, want_lg)
+    cand, dec, lg = call(m.predict_batch_candidates, want_logits=False, want_decisions=False)
+    assert cand.tobytes() == want_cand and dec is None and lg is None
+    m.close()
+
+
 def test_deferred_submit_flush_wait(gpu):
     """mlt_submit / mlt_flush / mlt_wait (encoder-side batching): tickets resolve to exactly what mlt_predict returns, in any
     wait order, across an automatic flush of a full batch, and expired / unknown tickets are rejected."""
@@ -544,6 +612,45 @@ def test_deferred_submit_flush_wait(gpu):
         m.wait(size, tickets[0])  # two newer batches were started since
     with pytest.raises(pkg.MltError):
         m.wait(size, t3 + 5)  # never issued
+    m.close()
+
+
+def test_deferred_records_across_a_set_reuse(gpu):
+    """mlt_wait / mlt_wait_decision / mlt_wait_candidates in mixed order over two generations with an exact re-run in each (a flat CU at 5 and at 70): every ticket
+    resolves to the bytes mlt_predict_candidates returns for its CU.  Then a third generation reuses set 0, counting its flagged CUs on the other counter of the pair."""
+    pkg = gpu
+    size, cap = 128, 64  # MLT_DEFER_CAP
+    n = cap + 9
+    blob, org, pred, poc, qp = _guarded_batch_with_flat_cus(pkg, size, n, 45, [5, 70])
+    m = _ctx(pkg, size, blob, flags=pkg.capi.FLAG_NO_CALIBRATION)
+    m.set_candidate_policy(size, 0.9, 0)
+    want = [m.predict_candidates(org[i], pred[i], int(poc[i]), int(qp[i])) for i in range(n)]   # (candidate record, decision record, logits)
+    r0 = m.arithmetic(size)["guard_reruns"]
+
+    def check(i, ticket, shift=0):
+        c0, d0, l0 = want[i]
+        kind = (i + shift) % 3
+        if kind == 0:
+            c, dd, l = m.wait_candidates(size, ticket)
+            assert c.tobytes() == c0.tobytes() and dd.tobytes() == d0.tobytes() and np.array_equal(l, l0), i
+        elif kind == 1:
+            dd, l = m.wait_decision(size, ticket)
+            assert dd.tobytes() == d0.tobytes() and np.array_equal(l, l0), i
+        else:
+            s, l = m.wait(size, ticket)
+            assert s == int(d0["split_mode"]) and np.array_equal(l, l0), i
+
+    tickets = [m.submit(org[i], pred[i], int(poc[i]), int(qp[i])) for i in range(n)]  # 64 -> auto flush -> 9 pending
+    for i in list(range(n - 1, cap - 1, -1)) + [5, 0, 63, 17, 6, 4, 33]:  # second generation first (the first wait launches it), then the first
+        check(i, tickets[i])
+    assert m.arithmetic(size)["guard_reruns"] == r0 + 2
+    picks = [5, 0, 70]   # third generation: set 0 again, its counter pair toggled, one exact re-run per kind of wait
+    t2 = [m.submit(org[i], pred[i], int(poc[i]), int(qp[i])) for i in picks]
+    m.flush(size)
+    for shift in (0, 1, 2):   # every ticket through every kind of wait
+        for i, t in zip(picks, t2):
+            check(i, t, shift)
+    assert m.arithmetic(size)["guard_reruns"] == r0 + 4
     m.close()
 
 
