@@ -33,7 +33,8 @@ EXPORTS = ["mlt_abi_version", "mlt_build_signature", "mlt_init", "mlt_num_device
            "mlt_set_candidate_policy", "mlt_get_candidate_policy", "mlt_predict_candidates", "mlt_predict_batch_candidates",
            "mlt_predict_batch_device_candidates", "mlt_wait_candidates",
            "mlt_picture_create", "mlt_picture_upload", "mlt_picture_wrap_device", "mlt_picture_destroy", "mlt_predict_at", "mlt_grid_positions",
-           "mlt_tree_max_nodes", "mlt_tree_roots", "mlt_predict_tree"]
+           "mlt_tree_max_nodes", "mlt_tree_roots", "mlt_predict_tree", "mlt_predict_trees"]
+TREES_MAX_PICTURES = 256  # MLT_TREES_MAX_PICTURES
 TREE_BY_CANDIDATES = 0x1  # mlt_tree_config.flags: descend on cand_mask & descend_mask instead of on split_mode
 
 
@@ -75,6 +76,11 @@ class MltTreeConfig(C.Structure):
     """`struct mlt_tree_config` (include/mltcnn.h): 40 bytes."""
     _fields_ = [("struct_size", C.c_uint32), ("top_size", C.c_int32), ("min_size", C.c_int32), ("descend_mask", C.c_uint32 * 4), ("flags", C.c_uint32),
                 ("poc", C.c_int32), ("qp", C.c_int32)]
+
+
+class MltTreePicture(C.Structure):
+    """`struct mlt_tree_picture` (include/mltcnn.h): 24 bytes -- one entry of mlt_predict_trees."""
+    _fields_ = [("org", C.c_void_p), ("pred", C.c_void_p), ("poc", C.c_int32), ("qp", C.c_int32)]
 
 
 # `struct mlt_tree_node` (include/mltcnn.h): 32 bytes, no padding
@@ -156,6 +162,7 @@ def load_library():
     lib.mlt_tree_max_nodes.argtypes = [i32, i32, i32, i32]
     lib.mlt_tree_roots.argtypes = [i32, i32, i32, i32, vp, i32]
     lib.mlt_predict_tree.argtypes = [vp, vp, vp, C.POINTER(MltTreeConfig), vp, i32, C.POINTER(i32), vp, vp, i32, vp, vp]
+    lib.mlt_predict_trees.argtypes = [vp, i32, C.POINTER(MltTreePicture), C.POINTER(MltTreeConfig), vp, i32, vp, vp, vp, i32, vp, vp]
     lib.mlt_synchronize.argtypes = [vp]
     lib.mlt_set_stream.argtypes = [vp, vp]
     lib.mlt_alloc_pinned.restype = vp
@@ -527,6 +534,54 @@ class MltCnn:
             if k in out:
                 out[k] = out[k][:n.value].copy()
         return out
+
+    def predict_trees(self, pairs, poc, qp, top: int = 128, min_size: int = 16, descend: dict | None = None, by_candidates: bool = False,
+                      want=("leaf_map",)) -> list:
+        """The partition trees of several picture pairs of one geometry in ONE descent (mlt_predict_trees).  pairs: [(org_pic, pred_pic), ...]; poc / qp: one int
+        for all pairs or one per pair; the other arguments as predict_tree.
+        -> one dict per pair, shaped like predict_tree's ("logits" rows are zero beyond the size's logit count) + "first_node": the pair's first index in the call's
+        node array."""
+        assert set(want) <= {"leaf_map", "logits", "decisions", "candidates"}
+        pairs = list(pairs)
+        P = len(pairs)
+        poc = np.broadcast_to(np.asarray(poc, np.int32), (P,))
+        qp = np.broadcast_to(np.asarray(qp, np.int32), (P,))
+        entries = (MltTreePicture * max(P, 1))()
+        for i, (o, q) in enumerate(pairs):
+            entries[i].org, entries[i].pred, entries[i].poc, entries[i].qp = o._h, q._h, int(poc[i]), int(qp[i])
+        cfg = MltTreeConfig()
+        cfg.struct_size = C.sizeof(MltTreeConfig)
+        cfg.top_size, cfg.min_size = int(top), int(min_size)
+        cfg.flags = TREE_BY_CANDIDATES if by_candidates else 0
+        for i, s in enumerate((128, 64, 32, 16)):
+            cfg.descend_mask[i] = int((descend or {}).get(s, 0))
+        w, h = (pairs[0][0].width, pairs[0][0].height) if P else (0, 0)
+        cap = P * tree_max_nodes(w, h, top, min_size)
+        nodes = np.zeros((max(cap, 1),), TREE_NODE_DTYPE)
+        first = np.zeros((P + 1,), np.int32)
+        out = {}
+        if "leaf_map" in want:
+            out["leaf_map"] = np.zeros((max(P, 1), h // 16, w // 16), np.uint8)
+        if "logits" in want:
+            out["logits"] = np.zeros((max(cap, 1), 15), np.float32)
+        if "decisions" in want:
+            out["decisions"] = np.zeros((max(cap, 1),), DECISION_DTYPE)
+        if "candidates" in want:
+            out["candidates"] = np.zeros((max(cap, 1),), CANDIDATES_DTYPE)
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        self._check(self._lib.mlt_predict_trees(self._h, P, entries, C.byref(cfg), nodes.ctypes.data, cap, first.ctypes.data, ptr("leaf_map"),
+                                                ptr("logits"), 15, ptr("decisions"), ptr("candidates")))
+        res = []
+        for p in range(P):
+            lo, hi = int(first[p]), int(first[p + 1])
+            r = {"nodes": nodes[lo:hi].copy(), "first_node": lo}
+            if "leaf_map" in out:
+                r["leaf_map"] = out["leaf_map"][p].copy()
+            for k in ("logits", "decisions", "candidates"):
+                if k in out:
+                    r[k] = out[k][lo:hi].copy()
+            res.append(r)
+        return res
 
     def synchronize(self):
         self._check(self._lib.mlt_synchronize(self._h))

@@ -332,6 +332,53 @@ struct TreeRasterArgs {
 };
 hipError_t mlt_launch_tree_expand(const TreeExpandArgs &a, hipStream_t st);
 hipError_t mlt_launch_tree_raster(const TreeRasterArgs &a, hipStream_t st);
+// ---- partition trees of several pictures in one call (mlt_predict_trees): the arena is LEVEL-MAJOR over all pictures -- level l is one node range, picture 0's
+// segment, then picture 1's, ...; a segment in the single tree's order (roots, then children in their parents' order) ----
+#define MLT_TREES_LEVELS 4
+#define MLT_TREES_ROW 15      // floats of a node's logits row, in the arena and in the output (include/mltcnn.h: MLT_MAX_LOGITS; mlt_runtime.h asserts it)
+// One entry of the call (mlt_tree_picture as the device sees it): the gather's per-launch arguments of the one-picture path, per entry.
+struct TreesEntry {
+  const int16_t *org, *pred;   // sample (0, 0)
+  long org_pitch, pred_pitch;  // elements
+  int32_t vec_org, vec_pred;   // PictureGatherArgs.vec_org / vec_pred of THIS entry's planes
+  int32_t poc, qp;
+};
+// The segment table, [MLT_TREES_LEVELS][n_pictures] each: where picture p's nodes of level l start in the arena, how many they are, and where they start in the
+// packed (picture-major) output.  Written by the expand launches (a level's rows by the launch that writes the level's nodes; pack_base by the last one).
+struct TreesSegs { int32_t *start, *n, *pack_base; };
+struct TreesExpandArgs {
+  TreeExpandArgs t;            // the level as one list; t.next_roots / t.n_next_roots: the roots EVERY picture's next segment opens with; t.count: the whole next level
+  int32_t *pic;                // [node_cap] picture index of every node, beside t.xy
+  TreesSegs segs;
+  int n_pictures;
+  int lvl, n_levels;           // t.depth = lvl (-1 opens the tree); lvl == n_levels - 1: the last launch also writes pack_base and first_node
+  int32_t *first_node;         // [n_pictures + 1] out (last launch)
+};
+struct PictureGatherMultiArgs {
+  const TreesEntry *entries;   // [n_entries]
+  const int32_t *pic;          // [c] entry of every CU
+  const int32_t *xy;           // [c][2], inside every entry's (common) width x height
+  int16_t *g_org, *g_pred;     // dense [c][S][S], 16-byte aligned
+  int32_t *g_poc, *g_qp;       // [c] out: the CU's entry's poc / qp
+  int c, s_l, n_entries;
+};
+struct TreesRasterArgs {
+  TreeRasterArgs t;            // t.map: picture 0's map
+  const int32_t *pic;
+  size_t map_bytes;            // picture p's map starts at t.map + p * map_bytes
+};
+struct TreesPackArgs {
+  const TreeNodeRec *nodes; const int32_t *pic; const float *logits; const DecisionRec *dec; const CandRec *cand;   // level-major (logits / dec / cand: NULL = not wanted)
+  TreeNodeRec *o_nodes; float *o_logits; DecisionRec *o_dec; CandRec *o_cand;                                       // picture-major; o_logits: MLT_TREES_ROW floats per node
+  TreesSegs segs;
+  const int32_t *first_node;
+  int n_pictures, n_levels, total;
+  int lvl_start[MLT_TREES_LEVELS], n_logits[MLT_TREES_LEVELS];   // a level's logits are dense [lvl_n][n_logits] from row lvl_start of the MLT_TREES_ROW-float rows
+};
+hipError_t mlt_launch_trees_expand(const TreesExpandArgs &a, hipStream_t st);
+hipError_t mlt_launch_picture_gather_multi(const PictureGatherMultiArgs &a, hipStream_t st);
+hipError_t mlt_launch_trees_raster(const TreesRasterArgs &a, hipStream_t st);
+hipError_t mlt_launch_trees_pack(const TreesPackArgs &a, hipStream_t st);
 hipError_t mlt_launch_flat_stat(const FlatStatArgs &a, bool aligned8, hipStream_t st);
 hipError_t mlt_launch_guard_select(const GuardSelectArgs &a, hipStream_t st);
 hipError_t mlt_launch_guard_gather(const GuardGatherArgs &a, hipStream_t st);

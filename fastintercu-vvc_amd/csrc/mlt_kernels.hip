@@ -280,8 +280,8 @@ template <int Q, class ACC = float16v> __device__ __forceinline__ half4 act_quad
 #include "mlt_layer0_kernel.inc"  // layer0_stream_kernel
 #include "mlt_layer1_kernel.inc"  // layer1_stream_kernel
 #include "mlt_tail_kernels.inc"   // heads_kernel, flat_stat / guard kernels
-#include "mlt_picture_kernels.inc"  // picture_gather_kernel
-#include "mlt_tree_kernels.inc"  // tree_expand_kernel, tree_raster_kernel
+#include "mlt_picture_kernels.inc"  // picture_gather_kernel, picture_gather_multi_kernel
+#include "mlt_tree_kernels.inc"  // tree_expand_kernel, tree_raster_kernel, trees_expand_kernel, trees_raster_kernel, tree_pack_kernel
 
 // ---------------------------------------------------------------------------------------------
 // launchers
@@ -869,5 +869,36 @@ hipError_t mlt_launch_tree_raster(const TreeRasterArgs &a, hipStream_t st) {
   if (!items) return hipSuccess;
   const size_t want = (items + 255) / 256;
   hipLaunchKernelGGL(tree_raster_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// ---- trees of several pictures in one call: the same launch shapes as their one-picture forms ----
+hipError_t mlt_launch_picture_gather_multi(const PictureGatherMultiArgs &a, hipStream_t st) {
+  const size_t items = (size_t)a.c << (2 * a.s_l - 2);
+  if (!items) return hipSuccess;
+  const size_t want = (items + 255) / 256;
+  hipLaunchKernelGGL(picture_gather_multi_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t mlt_launch_trees_expand(const TreesExpandArgs &a, hipStream_t st) {
+  if (a.n_pictures < 1 || a.n_pictures > MLT_TREES_MAX_PICTURES_K) return hipErrorInvalidValue;   // the per-picture ranks live in LDS arrays of that size
+  hipLaunchKernelGGL(trees_expand_kernel, dim3(1), dim3(MLT_TREE_TILE), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t mlt_launch_trees_raster(const TreesRasterArgs &a, hipStream_t st) {
+  const size_t items = (size_t)a.t.lvl_n << (2 * a.t.blk_l);
+  if (!items) return hipSuccess;
+  const size_t want = (items + 255) / 256;
+  hipLaunchKernelGGL(trees_raster_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// flat grid-stride launch over the nodes of all levels
+hipError_t mlt_launch_trees_pack(const TreesPackArgs &a, hipStream_t st) {
+  if (a.total <= 0) return hipSuccess;
+  const int want = (a.total + 255) / 256;
+  hipLaunchKernelGGL(tree_pack_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
   return hipGetLastError();
 }

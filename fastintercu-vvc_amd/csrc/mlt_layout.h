@@ -106,5 +106,31 @@ struct TreeArena : Carved {
     return Ptrs{nodes.in<TreeNodeRec>(b), xy.in<int32_t>(b), logits.in<float>(b), dec.in<DecisionRec>(b), cand.in<CandRec>(b), roots.in<int32_t>(b), map.in<uint8_t>(b), count.in<int32_t>(b)};
   }
 };
+// mlt_predict_trees' device arena for `pics` pictures of up to n nodes each, on the same buffer of the context: the parts of TreeArena over pics x n nodes, LEVEL-major
+// (a level of all pictures is one node range) and one map per picture | the per-node picture index | the segment table ([4 levels][pics]: start, count, start in the
+// output) | first_node [pics + 1] | the entry table (entry_bytes each) | the picture-major output: nodes [| logits] [| records] [| candidate records].
+struct TreesArena : Carved {
+  static const int kRow = MLT_MAX_LOGITS, kLevels = 4;
+  struct Ptrs {
+    TreeNodeRec *nodes; int32_t *xy; float *logits; DecisionRec *dec; CandRec *cand; int32_t *roots; uint8_t *map; int32_t *count;
+    int32_t *pic, *seg_start, *seg_n, *pack_base, *first_node; char *entries;
+    TreeNodeRec *o_nodes; float *o_logits; DecisionRec *o_dec; CandRec *o_cand;
+  };
+  Field nodes, xy, logits, dec, cand, roots, map, count, pic, seg_start, seg_n, pack_base, first_node, entries, o_nodes, o_logits, o_dec, o_cand;
+  TreesArena(size_t pics, size_t n, size_t n_roots, size_t map_bytes, size_t entry_bytes, bool cands, bool out_logits, bool out_dec, bool out_cand) {
+    const size_t N = pics * n;
+    nodes = put(N * sizeof(mlt_tree_node), 256); xy = put(N * 8, 256); logits = put(N * kRow * 4, 256); dec = put(N * sizeof(mlt_decision), 256);
+    cand = put(N * sizeof(mlt_candidates), 256, cands); roots = put(n_roots * 8, 256); map = put(pics * map_bytes, 256); count = put(4, 256);
+    pic = put(N * 4, 256); seg_start = put(kLevels * pics * 4, 256); seg_n = put(kLevels * pics * 4, 256); pack_base = put(kLevels * pics * 4, 256);
+    first_node = put((pics + 1) * 4, 256); entries = put(pics * entry_bytes, 256);
+    o_nodes = put(N * sizeof(mlt_tree_node), 256); o_logits = put(N * kRow * 4, 256, out_logits); o_dec = put(N * sizeof(mlt_decision), 256, out_dec);
+    o_cand = put(N * sizeof(mlt_candidates), 256, out_cand);
+  }
+  Ptrs at(char *b) const {
+    return Ptrs{nodes.in<TreeNodeRec>(b), xy.in<int32_t>(b), logits.in<float>(b), dec.in<DecisionRec>(b), cand.in<CandRec>(b), roots.in<int32_t>(b), map.in<uint8_t>(b),
+                count.in<int32_t>(b), pic.in<int32_t>(b), seg_start.in<int32_t>(b), seg_n.in<int32_t>(b), pack_base.in<int32_t>(b), first_node.in<int32_t>(b),
+                entries.in<char>(b), o_nodes.in<TreeNodeRec>(b), o_logits.in<float>(b), o_dec.in<DecisionRec>(b), o_cand.in<CandRec>(b)};
+  }
+};
 
 }  // namespace Lay

@@ -59,3 +59,27 @@ __global__ __launch_bounds__(256) void picture_gather_kernel(const PictureGather
     *(pic_u32x4 *)((is_pred ? a.g_pred : a.g_org) + 8 * j) = v;   // dense [c][S][S]: item j of the plane starts at element 8 j
   }
 }
+
+// picture_gather_kernel for CUs of SEVERAL picture pairs in one list (mlt_predict_trees): CU cu belongs to entry pic[cu] of a per-call table, which holds what
+// the one-pair launch takes as arguments -- the two plane bases, pitches and alignment classes -- and the entry's poc / qp.  The alignment class is therefore a
+// property of the ITEM, and the argument above holds per entry: the host validates every entry's geometry (all entries of a call share width and height, and the
+// positions are complete CUs of that geometry), and sets an entry's vec flags from that entry's own extents.  The first item of a CU also writes the CU's poc / qp
+// into the staging set, so a chunk that cuts through several pictures needs no fill of its own.
+__global__ __launch_bounds__(256) void picture_gather_multi_kernel(const PictureGatherMultiArgs a) {
+  const int seg_l = a.s_l - 3;
+  const size_t per_plane = (size_t)a.c << (2 * a.s_l - 3);
+  const size_t total = 2 * per_plane, step = (size_t)gridDim.x * 256;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += step) {
+    const bool is_pred = i >= per_plane;
+    const size_t j = is_pred ? i - per_plane : i;
+    const int seg = (int)(j & ((1u << seg_l) - 1)), row = (int)((j >> seg_l) & ((1u << a.s_l) - 1)), cu = (int)(j >> (seg_l + a.s_l));
+    const int p = a.pic[cu];
+    if ((unsigned)p >= (unsigned)a.n_entries) continue;   // (the expand kernel writes indices below n_pictures only: never taken)
+    const TreesEntry &e = a.entries[p];
+    const int x = a.xy[2 * cu], y = a.xy[2 * cu + 1];
+    const int16_t *src = (is_pred ? e.pred : e.org) + (size_t)(y + row) * (size_t)(is_pred ? e.pred_pitch : e.org_pitch) + x + 8 * seg;
+    const pic_u32x4 v = picture_fetch8(src, is_pred ? e.vec_pred != 0 : e.vec_org != 0);
+    *(pic_u32x4 *)((is_pred ? a.g_pred : a.g_org) + 8 * j) = v;
+    if (!is_pred && seg == 0 && row == 0) { a.g_poc[cu] = e.poc; a.g_qp[cu] = e.qp; }
+  }
+}

@@ -27,7 +27,8 @@ void release(mlt_ctx *ctx, mlt_picture *pic) {
 
 // One device: CUs [0, n) of a position list from the planes this device holds (dev: the device's own context), in chunks of the pass size.  Host lists
 // (mlt_predict_at): positions, poc and qp go H2D per chunk and the results D2H.  Device lists (mlt_predict_tree: at.device): the gather reads the positions where
-// they are, every CU takes (poc_all, qp_all) and the network writes logits and records straight into the caller's device arrays (every store to them is a
+// they are, every CU takes (poc_all, qp_all) -- or, for a list over several picture pairs (mlt_predict_trees: at.pic), its entry's planes, poc and qp from the
+// device table, through picture_gather_multi_kernel -- and the network writes logits and records straight into the caller's device arrays (every store to them is a
 // 4-byte or a struct store: no alignment beyond the arrays' own is assumed) -- the launches in between are the same, so are the results.
 int predict_at_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &pl, int n, const AtList &at, const AtOut &out) {
   if (hipSetDevice(dev->device) != hipSuccess) { dev->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
@@ -39,7 +40,7 @@ int predict_at_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &pl, int n, co
   if ((rc = dev->stage.reserve(dev, lay.bytes() + (at.device ? 0 : Lay::up256((size_t)cap * 8)), "staging"))) return rc;   // the set, then the chunk's positions
   const StageSet::Ptrs S = lay.at(dev->stage.p);
   int32_t *d_xy = (int32_t *)(dev->stage.p + lay.bytes());
-  if (at.device) {   // one (poc, qp) pair: filled once, every chunk reads its first c entries
+  if (at.device && !at.pic) {   // one (poc, qp) pair: filled once, every chunk reads its first c entries
     HIP_TRY(dev, hipMemsetD32Async((hipDeviceptr_t)S.d_poc, at.poc_all, (size_t)cap, dev->stream));
     HIP_TRY(dev, hipMemsetD32Async((hipDeviceptr_t)S.d_qp, at.qp_all, (size_t)cap, dev->stream));
   }
@@ -50,14 +51,22 @@ int predict_at_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &pl, int n, co
       HIP_TRY(dev, hipMemcpyAsync(S.d_poc, at.poc + i0, (size_t)c * 4, hipMemcpyHostToDevice, dev->stream));
       HIP_TRY(dev, hipMemcpyAsync(S.d_qp, at.qp + i0, (size_t)c * 4, hipMemcpyHostToDevice, dev->stream));
     }
-    PictureGatherArgs ga{};
-    ga.org = pl.org; ga.pred = pl.pred; ga.org_pitch = pl.org_pitch; ga.pred_pitch = pl.pred_pitch; ga.vec_org = pl.org_vec; ga.vec_pred = pl.pred_vec;
-    ga.xy = at.device ? at.xy + 2 * (size_t)i0 : d_xy; ga.g_org = S.d_org; ga.g_pred = S.d_pred; ga.c = c; ga.s_l = ilog2(size);
     Launch L{dev};
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    // algorithmic bytes: both planes of every CU read once and written once
-    if ((rc = L.prof_begin("picture_gather", 0.0, (double)c * size * size * 2 * 2 * 2, e0, e1))) return rc;
-    LAUNCH_TRY(dev, mlt_launch_picture_gather(ga, dev->stream));
+    if (at.pic) {   // the chunk's slice of the list and of its entry indices; the launch writes the chunk's poc / qp as well
+      PictureGatherMultiArgs ga{};
+      ga.entries = at.entries; ga.n_entries = at.n_entries; ga.pic = at.pic + i0; ga.xy = at.xy + 2 * (size_t)i0;
+      ga.g_org = S.d_org; ga.g_pred = S.d_pred; ga.g_poc = S.d_poc; ga.g_qp = S.d_qp; ga.c = c; ga.s_l = ilog2(size);
+      if ((rc = L.prof_begin("picture_gather_multi", 0.0, (double)c * (size * size * 2 * 2 * 2 + 12), e0, e1))) return rc;
+      LAUNCH_TRY(dev, mlt_launch_picture_gather_multi(ga, dev->stream));
+    } else {
+      PictureGatherArgs ga{};
+      ga.org = pl.org; ga.pred = pl.pred; ga.org_pitch = pl.org_pitch; ga.pred_pitch = pl.pred_pitch; ga.vec_org = pl.org_vec; ga.vec_pred = pl.pred_vec;
+      ga.xy = at.device ? at.xy + 2 * (size_t)i0 : d_xy; ga.g_org = S.d_org; ga.g_pred = S.d_pred; ga.c = c; ga.s_l = ilog2(size);
+      // algorithmic bytes: both planes of every CU read once and written once
+      if ((rc = L.prof_begin("picture_gather", 0.0, (double)c * size * size * 2 * 2 * 2, e0, e1))) return rc;
+      LAUNCH_TRY(dev, mlt_launch_picture_gather(ga, dev->stream));
+    }
     if ((rc = L.prof_end(e1))) return rc;
     // (the guards and their exact re-run read the gathered planes; the staging pointers are 256-byte aligned: CLS_QUADS whatever the picture's alignment)
     if (at.device) {

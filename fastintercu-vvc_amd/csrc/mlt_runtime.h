@@ -4,7 +4,7 @@
 //   mlt_calibrate.cpp  model upload, calibration sets and session, the loader, mlt_load_weights / mlt_calibrate / mlt_arithmetic
 //   mlt_api.cpp        init / shutdown / stream, the predict entry points, deferred prediction, confidence gate, profile
 //   mlt_pictures.cpp   device-resident pictures: create / upload / wrap / destroy, mlt_predict_at, mlt_grid_positions
-//   mlt_tree.cpp       partition trees of a picture: mlt_predict_tree, mlt_tree_roots, mlt_tree_max_nodes
+//   mlt_tree.cpp       partition trees of a picture: mlt_predict_tree, mlt_predict_trees, mlt_tree_roots, mlt_tree_max_nodes
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -293,7 +293,7 @@ struct mlt_ctx {
   int guard_phase[2] = {0, 0};    // which counter of a slot's pair the next batch launch counts on (GuardSlot.phase)
   hipEvent_t ev_guard = nullptr;  // "count of flagged CUs has landed" (device-pointer entry)
   GrowBuf gstage;
-  // mlt_predict_tree's device arena (Lay::TreeArena) and its pinned count
+  // mlt_predict_tree's / mlt_predict_trees' device arena (Lay::TreeArena / Lay::TreesArena) and its pinned count
   GrowBuf tree_dev;
   int32_t *tree_host = nullptr;
   std::vector<mlt_picture *> pictures;  // every picture created on / wrapped for this context (mlt_pictures.cpp); what is left is released by mlt_shutdown
@@ -319,6 +319,7 @@ static_assert(offsetof(mlt_decision, confidence) == offsetof(DecisionRec, confid
 static_assert(sizeof(mlt_tree_node) == 32 && sizeof(TreeNodeRec) == 32 && offsetof(mlt_tree_node, size) == offsetof(TreeNodeRec, size) && offsetof(mlt_tree_node, parent) == 12 &&
               offsetof(TreeNodeRec, parent) == 12 && offsetof(mlt_tree_node, cand_mask) == offsetof(TreeNodeRec, cand_mask) && offsetof(mlt_tree_node, cand_mask) == 28, "mlt_tree_node layout");
 static_assert(sizeof(mlt_tree_config) == 40, "mlt_tree_config is 40 bytes");
+static_assert(sizeof(mlt_tree_picture) == 24 && MLT_TREES_ROW == MLT_MAX_LOGITS && MLT_TREES_LEVELS == Lay::TreesArena::kLevels && sizeof(TreesEntry) == 48, "mlt_predict_trees layouts");
 
 static_assert(sizeof(mlt_candidates) == 40 && sizeof(CandRec) == sizeof(mlt_candidates) && offsetof(mlt_candidates, order) == offsetof(CandRec, order) &&
               offsetof(mlt_candidates, prob) == offsetof(CandRec, prob) && offsetof(mlt_candidates, prob) == 16, "mlt_candidates layout");
@@ -405,7 +406,8 @@ template <class F> int run_sharded(mlt_ctx *ctx, int n, F per_device) {
 // mlt_pictures.cpp
 void free_pictures(mlt_ctx *ctx);               // mlt_shutdown: before the peers go
 bool owns_picture(const mlt_ctx *ctx, const mlt_picture *pic);
-// the picture pair as one device sees it | the CUs of a call: a host list with poc / qp per CU, or a DEVICE list of positions that all take one (poc, qp) pair |
+// the picture pair as one device sees it | the CUs of a call: a host list with poc / qp per CU, a DEVICE list of positions that all take one (poc, qp) pair, or a
+// device list over the entries of a device table (mlt_predict_trees: AtPlanes is not read) |
 // where the results go (host arrays for a host list, device arrays for a device list; any may be NULL)
 struct AtPlanes {
   const int16_t *org; long org_pitch; bool org_vec;
@@ -415,8 +417,10 @@ struct AtPlanes {
 struct AtList {
   const int32_t *xy, *poc, *qp;
   bool device; int32_t poc_all, qp_all;
+  const int32_t *pic = nullptr; const TreesEntry *entries = nullptr; int n_entries = 0;   // device lists of SEVERAL pairs: CU i is of entry pic[i] (planes, poc, qp from the table)
   static AtList host(const int32_t *xy, const int32_t *poc, const int32_t *qp) { return AtList{xy, poc, qp, false, 0, 0}; }
   static AtList on_device(const int32_t *d_xy, int32_t poc, int32_t qp) { return AtList{d_xy, nullptr, nullptr, true, poc, qp}; }
+  static AtList of_entries(const int32_t *d_xy, const int32_t *d_pic, const TreesEntry *d_entries, int n) { return AtList{d_xy, nullptr, nullptr, true, 0, 0, d_pic, d_entries, n}; }
 };
 struct AtOut { int32_t *split; float *logits; mlt_decision *dec; mlt_candidates *cand; };
 int predict_at_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &pl, int n, const AtList &at, const AtOut &out);

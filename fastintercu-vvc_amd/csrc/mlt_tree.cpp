@@ -1,4 +1,4 @@
-// mlt_tree.cpp -- partition trees of a picture (include/mltcnn.h): mlt_predict_tree, mlt_tree_roots, mlt_tree_max_nodes.
+// mlt_tree.cpp -- partition trees of a picture (include/mltcnn.h): mlt_predict_tree, mlt_predict_trees, mlt_tree_roots, mlt_tree_max_nodes.
 //
 // Per level: the network on the level's nodes -- predict_at_chunks (mlt_pictures.cpp) on the slice of the device-resident position list that IS the level, so
 // launches, guards and exact re-runs are mlt_predict_at's and so is every result -- then tree_expand_kernel (mlt_tree_kernels.inc): the level's decisions into its
@@ -34,6 +34,38 @@ int roots_of(int w, int h, int top, int S, int32_t *xy, int cap) {
   return (int)count;
 }
 
+// the levels of a tree call: every size top..min loaded, every descend mask inside its decision head (`who` opens the messages)
+struct TreeLevels { int top, mn, L; SizeState *st[4]; uint32_t mask[4]; };
+int tree_levels(mlt_ctx *ctx, const char *who, const mlt_tree_config *cfg, TreeLevels &lv) {
+  lv.top = cfg->top_size; lv.mn = cfg->min_size; lv.L = 0;
+  if (!tree_sizes(lv.top, lv.mn)) { ctx->err = std::string(who) + ": top_size / min_size must be 128, 64, 32 or 16 with min_size <= top_size"; return MLT_ERR_ARG; }
+  int rc;
+  for (int S = lv.top; S >= lv.mn; S >>= 1, ++lv.L) {
+    if ((rc = check_size(ctx, S, &lv.st[lv.L]))) return rc;
+    const uint32_t m = cfg->descend_mask[size_index(S)];
+    lv.mask[lv.L] = m ? m : 1u << 1;
+    const int K = lv.st[lv.L]->head_classes();
+    if (lv.mask[lv.L] >> K) {
+      char msg[160];
+      std::snprintf(msg, sizeof msg, "%s: descend_mask of size %d names a class at or above the %d classes of its decision head", who, S, K);
+      ctx->err = msg;
+      return MLT_ERR_ARG;
+    }
+  }
+  return MLT_OK;
+}
+
+// the roots of every level, level after level: roots[2 * off[l] ..], n[l] of them
+struct TreeRoots { std::vector<int32_t> xy; int off[4], n[4]; };
+void tree_roots_of(int W, int H, int top, int L, TreeRoots &r) {
+  for (int l = 0, S = top; l < L; ++l, S >>= 1) {
+    r.off[l] = (int)(r.xy.size() / 2);
+    r.n[l] = roots_of(W, H, top, S, nullptr, 0);
+    r.xy.resize(r.xy.size() + 2 * (size_t)r.n[l]);
+    if (r.n[l]) (void)roots_of(W, H, top, S, r.xy.data() + 2 * (size_t)r.off[l], r.n[l]);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -60,24 +92,12 @@ int mlt_predict_tree(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pr
     ctx->err = "mlt_predict_tree: bad argument (cfg with struct_size = sizeof(mlt_tree_config), nodes, n_nodes, both pictures; logit_stride >= 15)";
     return MLT_ERR_ARG;
   }
-  int top = cfg->top_size, mn = cfg->min_size;
-  if (!tree_sizes(top, mn)) { ctx->err = "mlt_predict_tree: top_size / min_size must be 128, 64, 32 or 16 with min_size <= top_size"; return MLT_ERR_ARG; }
-  // the levels: every size top..min loaded, every descend mask inside its decision head
-  SizeState *st[4];
-  uint32_t mask[4];
-  int L = 0, rc;
-  for (int S = top; S >= mn; S >>= 1, ++L) {
-    if ((rc = check_size(ctx, S, &st[L]))) return rc;
-    const uint32_t m = cfg->descend_mask[size_index(S)];
-    mask[L] = m ? m : 1u << 1;
-    const int K = st[L]->head_classes();
-    if (mask[L] >> K) {
-      char msg[160];
-      std::snprintf(msg, sizeof msg, "mlt_predict_tree: descend_mask of size %d names a class at or above the %d classes of its decision head", S, K);
-      ctx->err = msg;
-      return MLT_ERR_ARG;
-    }
-  }
+  TreeLevels lv;
+  int rc;
+  if ((rc = tree_levels(ctx, "mlt_predict_tree", cfg, lv))) return rc;
+  const int top = lv.top, mn = lv.mn, L = lv.L;
+  SizeState **st = lv.st;
+  const uint32_t *mask = lv.mask;
   if (!owns_picture(ctx, org) || !owns_picture(ctx, pred)) { ctx->err = "mlt_predict_tree: both pictures must belong to this context"; return MLT_ERR_ARG; }
   if (org->width != pred->width || org->height != pred->height) { ctx->err = "mlt_predict_tree: the two pictures differ in width or height"; return MLT_ERR_ARG; }
   const int W = org->width, H = org->height;
@@ -94,14 +114,10 @@ int mlt_predict_tree(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pr
   // candidate records come from the heads launch only where cand_mask can differ from 1 << raw_mode (a policy is set) or the caller asks for them
   bool want_cand[4], any_cand = false;
   for (int l = 0; l < L; ++l) any_cand = (want_cand[l] = cand_opt || by_cand || st[l]->cand_policy()) || any_cand;
-  std::vector<int32_t> roots;
-  int root_off[4], n_roots[4];
-  for (int l = 0, S = top; l < L; ++l, S >>= 1) {
-    root_off[l] = (int)(roots.size() / 2);
-    n_roots[l] = roots_of(W, H, top, S, nullptr, 0);
-    roots.resize(roots.size() + 2 * (size_t)n_roots[l]);
-    if (n_roots[l]) (void)roots_of(W, H, top, S, roots.data() + 2 * (size_t)root_off[l], n_roots[l]);
-  }
+  TreeRoots tr;
+  tree_roots_of(W, H, top, L, tr);
+  const std::vector<int32_t> &roots = tr.xy;
+  const int *root_off = tr.off, *n_roots = tr.n;
   const int map_w = W / 16, map_h = H / 16;
   const size_t map_bytes = (size_t)map_w * map_h;
   const Lay::TreeArena arena((size_t)max_nodes, roots.size() / 2, map_bytes, any_cand);
@@ -181,6 +197,157 @@ int mlt_predict_tree(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pr
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   *n_nodes = total;
+  return MLT_OK;
+}
+
+// The trees of several picture pairs of one geometry in one descent: per level ONE position list over all pictures (the arena is level-major: picture 0's segment,
+// picture 1's, ...), one network pass through predict_at_chunks -- picture_gather_multi_kernel looks every CU's entry up -- one guard re-run, one 4-byte count; then
+// tree_pack_kernel permutes into the picture-major order of the contract and the call ends in one D2H copy per requested array.
+int mlt_predict_trees(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture *pics, const mlt_tree_config *cfg, mlt_tree_node *nodes, int node_cap, int32_t *first_node,
+                      uint8_t *leaf_maps_opt, float *logits_opt, int logit_stride, mlt_decision *dec_opt, mlt_candidates *cand_opt) {
+  if (!ctx) return MLT_ERR_ARG;
+  if (n_pictures < 1 || n_pictures > MLT_TREES_MAX_PICTURES || !pics || !cfg || cfg->struct_size != sizeof(mlt_tree_config) || !nodes || !first_node ||
+      (logits_opt && logit_stride < MLT_MAX_LOGITS) || (cfg->flags & ~MLT_TREE_BY_CANDIDATES)) {
+    ctx->err = "mlt_predict_trees: bad argument (1 .. 256 pictures, pics, cfg with struct_size = sizeof(mlt_tree_config), nodes, first_node; logit_stride >= 15)";
+    return MLT_ERR_ARG;
+  }
+  TreeLevels lv;
+  int rc;
+  if ((rc = tree_levels(ctx, "mlt_predict_trees", cfg, lv))) return rc;
+  const int top = lv.top, mn = lv.mn, L = lv.L, P = n_pictures;
+  SizeState **st = lv.st;
+  for (int p = 0; p < P; ++p) {
+    const mlt_picture *o = pics[p].org, *q = pics[p].pred;
+    char msg[192];
+    if (!o || !q || !owns_picture(ctx, o) || !owns_picture(ctx, q)) {
+      std::snprintf(msg, sizeof msg, "mlt_predict_trees: entry %d: both pictures must be given and belong to this context", p);
+      ctx->err = msg;
+      return MLT_ERR_ARG;
+    }
+    if (o->width != q->width || o->height != q->height || o->width != pics[0].org->width || o->height != pics[0].org->height) {
+      std::snprintf(msg, sizeof msg, "mlt_predict_trees: entry %d: every picture of a call must have the width and height of entry 0's (%d x %d)", p, pics[0].org->width,
+                    pics[0].org->height);
+      ctx->err = msg;
+      return MLT_ERR_ARG;
+    }
+  }
+  const int W = pics[0].org->width, H = pics[0].org->height;
+  const int max_nodes = mlt_tree_max_nodes(W, H, top, mn);
+  const long long cap_all = (long long)P * max_nodes;
+  if (node_cap < cap_all || cap_all > 0x7fffffff) {
+    char msg[192];
+    std::snprintf(msg, sizeof msg, "mlt_predict_trees: node_cap %d is below %d x mlt_tree_max_nodes = %d of a %d x %d picture", node_cap, P, max_nodes, W, H);
+    ctx->err = msg;
+    return MLT_ERR_ARG;
+  }
+  // ---- arguments are good: the trees run on this context's own device (devices[0] of a multi-device context) ----
+  if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
+  const bool by_cand = (cfg->flags & MLT_TREE_BY_CANDIDATES) != 0;
+  bool want_cand[4], any_cand = false;
+  for (int l = 0; l < L; ++l) any_cand = (want_cand[l] = cand_opt || by_cand || st[l]->cand_policy()) || any_cand;
+  TreeRoots tr;
+  tree_roots_of(W, H, top, L, tr);
+  const int map_w = W / 16, map_h = H / 16, N = (int)cap_all;
+  const size_t map_bytes = (size_t)map_w * map_h;
+  const Lay::TreesArena arena((size_t)P, (size_t)max_nodes, tr.xy.size() / 2, map_bytes, sizeof(TreesEntry), any_cand, logits_opt != nullptr, dec_opt != nullptr,
+                              cand_opt != nullptr);
+  if ((rc = ctx->tree_dev.reserve(ctx, arena.bytes(), "mlt_predict_trees"))) return rc;
+  if (!ctx->tree_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->tree_host, 64, hipHostMallocDefault));
+  const Lay::TreesArena::Ptrs A = arena.at(ctx->tree_dev.p);
+  std::vector<TreesEntry> entries((size_t)P);
+  for (int p = 0; p < P; ++p) {
+    const AtPlanes pl = AtPlanes::of(pics[p].org, pics[p].pred, 0);
+    entries[(size_t)p] = TreesEntry{pl.org, pl.pred, pl.org_pitch, pl.pred_pitch, pl.org_vec ? 1 : 0, pl.pred_vec ? 1 : 0, pics[p].poc, pics[p].qp};
+  }
+  // (pageable sources: both copies have read them when they return)
+  HIP_TRY(ctx, hipMemcpyAsync(A.entries, entries.data(), entries.size() * sizeof(TreesEntry), hipMemcpyHostToDevice, ctx->stream));
+  if (!tr.xy.empty()) HIP_TRY(ctx, hipMemcpyAsync(A.roots, tr.xy.data(), tr.xy.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (leaf_maps_opt && map_bytes) HIP_TRY(ctx, hipMemsetAsync(A.map, 0xFF, (size_t)P * map_bytes, ctx->stream));
+  Launch prof{ctx};
+  auto expand = [&](const TreesExpandArgs &xa) -> int {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int r;
+    // algorithmic bytes the host knows, as for tree_expand: + the picture index per node, the segment table's rows
+    if ((r = prof.prof_begin("trees_expand", 0.0, (double)xa.t.lvl_n * (sizeof(DecisionRec) + 20) + (double)P * xa.t.n_next_roots * (sizeof(TreeNodeRec) + 12) + (double)P * 8, e0, e1)))
+      return r;
+    HIP_TRY(ctx, mlt_launch_trees_expand(xa, ctx->stream));
+    return prof.prof_end(e1);
+  };
+  TreesExpandArgs xa{};
+  TreeExpandArgs &ea = xa.t;
+  xa.pic = A.pic; xa.segs = TreesSegs{A.seg_start, A.seg_n, A.pack_base}; xa.n_pictures = P; xa.n_levels = L; xa.first_node = A.first_node;
+  ea.nodes = A.nodes; ea.xy = A.xy; ea.node_cap = N; ea.by_candidates = by_cand ? 1 : 0;
+  // the trees open: no parents, every picture's top-level roots
+  xa.lvl = -1;
+  ea.lvl_start = 0; ea.lvl_n = 0; ea.size = 2 * top; ea.depth = -1;
+  ea.next_roots = A.roots; ea.n_next_roots = tr.n[0]; ea.root_flags = 0; ea.count = nullptr;
+  if ((rc = expand(xa))) return rc;
+  int start = 0, n = P * tr.n[0];
+  TreesPackArgs pa{};
+  for (int l = 0, S = top; l < L; ++l, S >>= 1) {
+    SizeState *s = st[l];
+    const int nl = s->model.n_logits;
+    const bool last = l == L - 1;
+    pa.lvl_start[l] = start; pa.n_logits[l] = nl;
+    float *d_lg = A.logits + (size_t)start * kRowLogits;
+    DecisionRec *d_dec = A.dec + start;
+    CandRec *d_cand = want_cand[l] ? A.cand + start : nullptr;
+    if (n > 0) {
+      const AtOut out{nullptr, d_lg, (mlt_decision *)d_dec, (mlt_candidates *)d_cand};
+      const AtPlanes none{};
+      if ((rc = predict_at_chunks(ctx, s, none, n, AtList::of_entries(A.xy + 2 * (size_t)start, A.pic + start, (const TreesEntry *)A.entries, P), out))) return rc;
+    }
+    xa.lvl = l;
+    ea.lvl_start = start; ea.lvl_n = n; ea.size = S; ea.depth = l;
+    ea.dec = d_dec; ea.cand = d_cand; ea.logits = d_lg; ea.n_logits = nl;
+    ea.head_off = s->head_off(); ea.head_classes = s->head_classes();
+    ea.descend_mask = last ? 0u : lv.mask[l];
+    ea.next_roots = last ? nullptr : A.roots + 2 * (size_t)tr.off[l + 1];
+    ea.n_next_roots = last ? 0 : tr.n[l + 1];
+    ea.root_flags = 1;
+    ea.count = last ? nullptr : A.count;
+    if ((rc = expand(xa))) return rc;
+    if (n > 0 && leaf_maps_opt) {
+      TreesRasterArgs ra{};
+      ra.t.nodes = A.nodes; ra.t.lvl_start = start; ra.t.lvl_n = n; ra.t.blk_l = ilog2(S) - 4; ra.t.map = A.map; ra.t.map_w = map_w; ra.t.map_h = map_h;
+      ra.pic = A.pic; ra.map_bytes = map_bytes;
+      hipEvent_t e0 = nullptr, e1 = nullptr;
+      if ((rc = prof.prof_begin("trees_raster", 0.0, (double)n * (sizeof(TreeNodeRec) + 4 + (double)(1 << (2 * ra.t.blk_l))), e0, e1))) return rc;
+      HIP_TRY(ctx, mlt_launch_trees_raster(ra, ctx->stream));
+      if ((rc = prof.prof_end(e1))) return rc;
+    }
+    start += n;
+    if (last) break;
+    // the one host synchronisation of the level beside the guards': how many nodes the next level has, over all pictures
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->tree_host, A.count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    n = ctx->tree_host[0];
+    const int nr = P * tr.n[l + 1];
+    if (n < nr || ((n - nr) & 3) || (long long)start + n > N) { ctx->err = "mlt_predict_trees: bad node count from the device"; return MLT_ERR_HIP; }
+  }
+  // ---- level-major -> picture-major, then everything the caller asked for and one synchronisation ----
+  const int total = start;
+  pa.nodes = A.nodes; pa.pic = A.pic; pa.logits = A.logits; pa.dec = A.dec; pa.cand = A.cand;
+  pa.o_nodes = A.o_nodes; pa.o_logits = A.o_logits; pa.o_dec = A.o_dec; pa.o_cand = A.o_cand;
+  pa.segs = xa.segs; pa.first_node = A.first_node; pa.n_pictures = P; pa.n_levels = L; pa.total = total;
+  if (total) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const double per_node = 2.0 * sizeof(TreeNodeRec) + 4 + (logits_opt ? 2.0 * kRowLogits * 4 : 0) + (dec_opt ? 2.0 * sizeof(DecisionRec) : 0) + (cand_opt ? 2.0 * sizeof(CandRec) : 0);
+    if ((rc = prof.prof_begin("tree_pack", 0.0, (double)total * per_node, e0, e1))) return rc;
+    HIP_TRY(ctx, mlt_launch_trees_pack(pa, ctx->stream));
+    if ((rc = prof.prof_end(e1))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(nodes, A.o_nodes, (size_t)total * sizeof(TreeNodeRec), hipMemcpyDeviceToHost, ctx->stream));
+    if (logits_opt) {
+      if (logit_stride == kRowLogits) HIP_TRY(ctx, hipMemcpyAsync(logits_opt, A.o_logits, (size_t)total * kRowLogits * 4, hipMemcpyDeviceToHost, ctx->stream));
+      else HIP_TRY(ctx, hipMemcpy2DAsync(logits_opt, (size_t)logit_stride * 4, A.o_logits, (size_t)kRowLogits * 4, (size_t)kRowLogits * 4, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (dec_opt) HIP_TRY(ctx, hipMemcpyAsync(dec_opt, A.o_dec, (size_t)total * sizeof(DecisionRec), hipMemcpyDeviceToHost, ctx->stream));
+    if (cand_opt) HIP_TRY(ctx, hipMemcpyAsync(cand_opt, A.o_cand, (size_t)total * sizeof(CandRec), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (leaf_maps_opt && map_bytes) HIP_TRY(ctx, hipMemcpyAsync(leaf_maps_opt, A.map, (size_t)P * map_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(first_node, A.first_node, ((size_t)P + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (first_node[P] != total) { ctx->err = "mlt_predict_trees: bad node count from the device"; return MLT_ERR_HIP; }
   return MLT_OK;
 }
 

@@ -94,3 +94,167 @@ __global__ __launch_bounds__(256) void tree_raster_kernel(const TreeRasterArgs a
     a.map[(size_t)my * a.map_w + mx] = (uint8_t)(a.blk_l | ((r.split_mode + 1) << 4));
   }
 }
+
+// ---- trees of several pictures in one call (include/mltcnn.h: mlt_predict_trees) ----
+// trees_expand_kernel   tree_expand_kernel over a level that holds the segments of n_pictures pictures: the same tiled scan over the WHOLE level, segmented output.
+// trees_raster_kernel   tree_raster_kernel with the map chosen by the node's picture.
+// tree_pack_kernel      after the last level: level-major arena -> picture-major output, parent / first_child rewritten to indices inside the picture's slice.
+//
+// The next level, with nr = n_next_roots roots per picture (all pictures share the geometry), R_i the exclusive rank of descending parent i over the whole level,
+// p_i its picture and D_p the rank at the start of picture p's segment (the descending parents of the pictures before p):
+//   picture p's segment   starts at next_start + p nr + 4 D_p and holds nr + 4 (D_{p+1} - D_p) nodes: its roots, then its children
+//   parent i's children   start at next_start + (p_i + 1) nr + 4 R_i   (= its segment's start + nr + 4 (R_i - D_{p_i}))
+// D_p is known once the scan has passed the segment's first node, so the scan comes first and the roots after it.  The first node of a non-empty segment publishes
+// its rank as D_p; an EMPTY segment (no roots at that level and nothing descended into it) has no node to do so and takes the rank of the first non-empty segment
+// behind it, or the level's total.  Still no atomics: the order is the scan's, every output word has one writer, all stores are ordinary vector stores.
+
+#define MLT_TREES_MAX_PICTURES_K 256   // include/mltcnn.h: MLT_TREES_MAX_PICTURES (the per-picture ranks live in LDS)
+
+__device__ __forceinline__ void trees_write_node(const TreesExpandArgs &a, int idx, int pic, int x, int y, int size, int depth, int flags, int parent) {
+  if (idx < 0 || idx >= a.t.node_cap) return;   // (never taken, as in tree_write_node)
+  tree_write_node(a.t, idx, x, y, size, depth, flags, parent);
+  a.pic[idx] = pic;
+}
+
+__global__ __launch_bounds__(MLT_TREE_TILE) void trees_expand_kernel(const TreesExpandArgs a) {
+  __shared__ int wave_total[MLT_TREE_TILE / 64];
+  __shared__ int seg_rank[MLT_TREES_MAX_PICTURES_K];       // D_p as published by the first node of a non-empty segment
+  __shared__ int seg_first[MLT_TREES_MAX_PICTURES_K + 1];  // D_p of every picture; [n_pictures] = the level's total
+  __shared__ int pic_total[MLT_TREES_MAX_PICTURES_K];      // last launch: nodes of picture p over all levels
+  const TreeExpandArgs &t = a.t;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, P = a.n_pictures, nr = t.n_next_roots;
+  const int next_start = t.lvl_start + t.lvl_n, child_size = t.size >> 1;
+  const int32_t *cur_start = a.segs.start + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P, *cur_n = a.segs.n + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P;
+  int base = 0;
+  for (int t0 = 0; t0 < t.lvl_n; t0 += MLT_TREE_TILE) {
+    const int i = t0 + tid;
+    const bool in = i < t.lvl_n;
+    const int node = t.lvl_start + (in ? i : 0);
+    bool desc = false;
+    int32_t split = -1;
+    float conf = 0.f;
+    uint32_t cmask = 0u;
+    int p = 0;
+    if (in) {
+      p = a.pic[node];
+      const DecisionRec &d = t.dec[i];
+      split = d.split_mode;
+      conf = d.confidence;
+      if (t.cand) cmask = t.cand[i].mask;
+      else {
+        const float *l = t.logits + (size_t)i * t.n_logits + t.head_off;
+        bool nan = false;
+        for (int k = 0; k < t.head_classes; ++k) nan = nan || (l[k] != l[k]);
+        cmask = nan ? (1u << t.head_classes) - 1u : 1u << d.raw_mode;
+      }
+      desc = t.by_candidates ? (cmask & t.descend_mask) != 0u : (split >= 0 && ((t.descend_mask >> split) & 1u) != 0u);
+    }
+    const unsigned long long b = __ballot(desc);
+    const int before = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_total[wave] = __popcll(b);
+    __syncthreads();
+    int woff = 0, total = 0;
+    for (int w = 0; w < MLT_TREE_TILE / 64; ++w) {
+      const int s = wave_total[w];
+      woff += w < wave ? s : 0;
+      total += s;
+    }
+    __syncthreads();   // (the next tile overwrites wave_total)
+    if (in) {
+      const int rank = base + woff + before;
+      if ((unsigned)p < (unsigned)P && node == cur_start[p]) seg_rank[p] = rank;   // the segment's first node: one writer per picture
+      int first_child = -1;
+      if (desc) {
+        const int fc = next_start + (p + 1) * nr + 4 * rank;
+        if (fc + 3 < t.node_cap) {
+          first_child = fc;
+          const int x = t.xy[2 * (size_t)node], y = t.xy[2 * (size_t)node + 1];
+          for (int j = 0; j < 4; ++j) trees_write_node(a, fc + j, p, x + (j & 1) * child_size, y + (j >> 1) * child_size, child_size, t.depth + 1, 0, node);
+        }
+      }
+      TreeNodeRec &r = t.nodes[node];
+      r.first_child = first_child; r.split_mode = split; r.confidence = conf; r.cand_mask = cmask;
+    }
+    base += total;
+  }
+  __syncthreads();   // seg_rank is complete
+  // D_p of every picture: its own first node's rank, or (empty segment) that of the first non-empty segment behind it
+  if (tid <= P) {
+    int q = tid;
+    while (q < P && (a.lvl < 0 || cur_n[q] == 0)) ++q;
+    seg_first[tid] = q < P ? seg_rank[q] : base;
+  }
+  __syncthreads();
+  const bool last = a.lvl == a.n_levels - 1;
+  if (!last) {
+    int32_t *nx_start = a.segs.start + (size_t)(a.lvl + 1) * P, *nx_n = a.segs.n + (size_t)(a.lvl + 1) * P;
+    if (tid < P) {
+      nx_start[tid] = next_start + tid * nr + 4 * seg_first[tid];
+      nx_n[tid] = nr + 4 * (seg_first[tid + 1] - seg_first[tid]);
+    }
+    // every picture's next segment opens with the border roots (host-known, raster order, the same for all pictures)
+    for (int i = tid; i < P * nr; i += MLT_TREE_TILE) {
+      const int p = i / nr, r = i - p * nr;
+      trees_write_node(a, next_start + p * nr + 4 * seg_first[p] + r, p, t.next_roots[2 * r], t.next_roots[2 * r + 1], child_size, t.depth + 1, t.root_flags, -1);
+    }
+    if (tid == 0 && t.count) t.count[0] = P * nr + 4 * base;
+    return;
+  }
+  // the last level: where every (level, picture) segment starts in the picture-major output, and first_node[]
+  if (tid < P) {
+    int s = 0;
+    for (int l = 0; l < a.n_levels; ++l) s += a.segs.n[(size_t)l * P + tid];
+    pic_total[tid] = s;
+  }
+  __syncthreads();
+  if (tid <= P) {
+    int first = 0;
+    for (int q = 0; q < tid; ++q) first += pic_total[q];
+    a.first_node[tid] = first;
+    if (tid < P)
+      for (int l = 0; l < a.n_levels; ++l) {
+        a.segs.pack_base[(size_t)l * P + tid] = first;
+        first += a.segs.n[(size_t)l * P + tid];
+      }
+  }
+}
+
+__global__ __launch_bounds__(256) void trees_raster_kernel(const TreesRasterArgs a) {
+  const TreeRasterArgs &t = a.t;
+  const size_t total = (size_t)t.lvl_n << (2 * t.blk_l), step = (size_t)gridDim.x * 256;
+  for (size_t it = (size_t)blockIdx.x * 256 + threadIdx.x; it < total; it += step) {
+    const int i = (int)(it >> (2 * t.blk_l)), b = (int)(it & ((1u << (2 * t.blk_l)) - 1u));
+    const TreeNodeRec &r = t.nodes[t.lvl_start + i];
+    if (r.first_child >= 0) continue;
+    const int mx = (r.x >> 4) + (b & ((1 << t.blk_l) - 1)), my = (r.y >> 4) + (b >> t.blk_l);
+    if (mx < 0 || my < 0 || mx >= t.map_w || my >= t.map_h) continue;   // (never taken)
+    t.map[(size_t)a.pic[t.lvl_start + i] * a.map_bytes + (size_t)my * t.map_w + mx] = (uint8_t)(t.blk_l | ((r.split_mode + 1) << 4));
+  }
+}
+
+// One work item per node.  Node g of level l, picture p goes to pack_base[l][p] + (g - seg_start[l][p]); its parent (level l - 1) and first child (level l + 1) lie
+// in the same picture's segments of those levels, and an index inside the slice is the packed position minus first_node[p].
+__global__ __launch_bounds__(256) void tree_pack_kernel(const TreesPackArgs a) {
+  const int P = a.n_pictures, step = (int)gridDim.x * 256;
+  for (int g = (int)(blockIdx.x * 256 + threadIdx.x); g < a.total; g += step) {
+    TreeNodeRec r = a.nodes[g];
+    const int p = a.pic[g], l = r.depth;
+    if ((unsigned)p >= (unsigned)P || (unsigned)l >= (unsigned)a.n_levels) continue;   // (never taken)
+    const size_t at = (size_t)l * P + p;
+    const int first = a.first_node[p], dst = a.segs.pack_base[at] + (g - a.segs.start[at]);
+    if ((unsigned)dst >= (unsigned)a.total) continue;                                     // (never taken)
+    if (r.parent >= 0 && l > 0) r.parent = a.segs.pack_base[at - P] + (r.parent - a.segs.start[at - P]) - first;
+    if (r.first_child >= 0 && l + 1 < a.n_levels) r.first_child = a.segs.pack_base[at + P] + (r.first_child - a.segs.start[at + P]) - first;
+    a.o_nodes[dst] = r;
+    if (a.o_logits) {
+      // (selected, not indexed: a dynamically indexed argument array would be copied to scratch or LDS)
+      const int nl = l == 0 ? a.n_logits[0] : l == 1 ? a.n_logits[1] : l == 2 ? a.n_logits[2] : a.n_logits[3];
+      const int ls = l == 0 ? a.lvl_start[0] : l == 1 ? a.lvl_start[1] : l == 2 ? a.lvl_start[2] : a.lvl_start[3];
+      const float *src = a.logits + (size_t)ls * MLT_TREES_ROW + (size_t)(g - ls) * nl;
+      float *o = a.o_logits + (size_t)dst * MLT_TREES_ROW;
+      for (int k = 0; k < MLT_TREES_ROW; ++k) o[k] = k < nl ? src[k] : 0.f;
+    }
+    if (a.o_dec) a.o_dec[dst] = a.dec[g];
+    if (a.o_cand) a.o_cand[dst] = a.cand[g];
+  }
+}

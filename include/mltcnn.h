@@ -427,6 +427,37 @@ int mlt_predict_tree(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pr
                      float *logits_opt, int logit_stride,
                      mlt_decision *dec_opt, mlt_candidates *cand_opt);
 
+/* ---- Partition trees of SEVERAL picture pairs in one call (new exports; MLT_ABI_VERSION stays 4) ----
+ * What a caller with a GOP, or with one original and several candidate predictions, in device memory wants: per level ONE network pass over the nodes of all
+ * pictures, one guard re-run and one 4-byte count, instead of those per picture.  On the device a level of all pictures is one position list (picture 0's nodes,
+ * then picture 1's, ...), gathered from the entries' planes by one launch; after the last level tree_pack_kernel permutes into the order below.
+ *
+ * ENTRIES   pics[0 .. n_pictures): an (org, pred) pair of ctx and the pair's poc / qp.  ALL pictures of a call have ONE width x height.  The same picture may
+ *           appear in several entries (one original against several predictions) and entries may repeat.  cfg->poc / cfg->qp are NOT read.
+ * RESULT    picture p's tree is nodes[first_node[p] .. first_node[p + 1]); first_node[n_pictures] is the total node count.  The slice is BYTE FOR BYTE what
+ *           mlt_predict_tree returns for (pics[p].org, pics[p].pred) with the same cfg and cfg.poc / qp = pics[p].poc / qp: node order, parent / first_child
+ *           (indices inside the slice: every slice is a self-contained tree), split_mode, confidence, cand_mask.  Leaf map p (leaf_maps_opt + p * (height / 16) *
+ *           (width / 16)), the decision and the candidate records (one per node, at the node's index) are those of that single call as well.
+ * LOGITS    node i at logits_opt + i * logit_stride; unlike mlt_predict_tree the WHOLE 15-float row of every node is written: the first mlt_num_logits(size)
+ *           floats are the single call's, the rest zeros.
+ * GUARDS    confidence gate, candidate policy, the three guards and MLT_TREE_BY_CANDIDATES act as in mlt_predict_tree; guard_reruns (mlt_arithmetic) grows by
+ *           the sum of what the single calls add.
+ * ERRORS    everything is checked before anything is enqueued and on any error every output stays untouched.  MLT_ERR_ARG: n_pictures outside 1 ..
+ *           MLT_TREES_MAX_PICTURES; pics, cfg, nodes or first_node NULL; cfg->struct_size wrong; a picture NULL or of another context; unequal geometry inside a
+ *           pair or between entries; node_cap < n_pictures * mlt_tree_max_nodes(width, height, top_size, min_size); logit_stride < 15 with logits_opt; sizes,
+ *           masks and flags as in mlt_predict_tree.  MLT_ERR_SIZE_DISABLED: a size top..min is not loaded.  NULL ctx: MLT_ERR_ARG.
+ * All arrays are HOST memory.  Synchronous.  On a multi-device context the call runs on devices[0], like mlt_predict_tree, with a one-device context's bytes. */
+#define MLT_TREES_MAX_PICTURES 256
+typedef struct mlt_tree_picture {   /* 24 bytes on LP64 */
+  const mlt_picture *org, *pred;    /* both of ctx, all pictures of the call of ONE width x height */
+  int32_t poc, qp;                  /* per picture */
+} mlt_tree_picture;
+
+int mlt_predict_trees(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture *pics, const mlt_tree_config *cfg,
+                      mlt_tree_node *nodes, int node_cap, int32_t *first_node /* [n_pictures + 1] */,
+                      uint8_t *leaf_maps_opt /* [n_pictures][height/16][width/16] */,
+                      float *logits_opt, int logit_stride, mlt_decision *dec_opt, mlt_candidates *cand_opt);
+
 int mlt_synchronize(mlt_ctx *ctx);
 
 /* Use an existing hipStream_t (e.g. the caller's) instead of the context's own stream; NULL switches back to a

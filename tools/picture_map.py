@@ -13,6 +13,9 @@ and writes per size `<out>_<S>_split.npy` (int32, -1 where the confidence gate w
 --tree [--min-size S]: the PARTITION TREE instead of the per-size maps (MltCnn.predict_tree): the CTUs, and only where the network says "quad split" their
 children, down to S (default 16); loads every size 128 .. S, writes `<out>_tree_nodes.npy` (capi.TREE_NODE_DTYPE, the contract's order) and `<out>_leafmap.npy`
 (uint8 [height // 16, width // 16]) and prints the nodes per level.
+--tree --frames N: the inputs hold N frames -- `.npy` int16 [N, height, width], or N consecutive raw planes -- and ALL N trees come from ONE call
+(MltCnn.predict_trees: one network pass per level over the nodes of all frames); --poc is the first frame's POC, frame f takes --poc + f.  Writes
+`<out>_f<f>_tree_nodes.npy` and `<out>_f<f>_leafmap.npy` per frame.
 
 File reading and grid logic (read_picture, grid, to_map, histogram) need neither a device nor the library; run_maps needs the MI355X."""
 import argparse
@@ -46,6 +49,33 @@ def read_picture(path: str, width: int | None = None, height: int | None = None)
     if a.max(initial=0) > 0x7FFF:
         raise ValueError(f"{path}: samples above 32767 do not fit a Pel (int16)")
     return a.astype(np.int16).reshape(height, width)
+
+
+def read_frames(path: str, frames: int, width: int | None = None, height: int | None = None) -> np.ndarray:
+    """-> int16 [frames, height, width], C-contiguous.  `.npy`: a 3-D int16 array of exactly `frames` frames (a 2-D array is one frame).  Anything else: raw 16-bit
+    little-endian samples, `frames` consecutive width x height planes from the start of the file."""
+    if frames < 1:
+        raise ValueError(f"--frames {frames}: want at least 1")
+    if path.endswith(".npy"):
+        a = np.load(path)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.dtype != np.int16:
+            raise ValueError(f"{path}: want an int16 array [frames, height, width], got {a.dtype} {a.shape}")
+        if a.shape[0] != frames:
+            raise ValueError(f"{path}: holds {a.shape[0]} frames, --frames says {frames}")
+        if (width and a.shape[2] != width) or (height and a.shape[1] != height):
+            raise ValueError(f"{path}: {a.shape[2]}x{a.shape[1]}, not the {width}x{height} asked for")
+        return np.ascontiguousarray(a)
+    if not width or not height:
+        raise ValueError(f"{path}: a raw file needs --width and --height")
+    count = frames * width * height
+    a = np.fromfile(path, dtype="<u2", count=count)
+    if a.size != count:
+        raise ValueError(f"{path}: {frames} planes of {width}x{height} need {count} samples of 16 bits, the file holds {a.size}")
+    if a.max(initial=0) > 0x7FFF:
+        raise ValueError(f"{path}: samples above 32767 do not fit a Pel (int16)")
+    return a.astype(np.int16).reshape(frames, height, width)
 
 
 def grid(width: int, height: int, size: int) -> np.ndarray:
@@ -116,6 +146,20 @@ def run_tree(m, org: np.ndarray, pred: np.ndarray, poc: int, qp: int, min_size: 
         p_pred.close()
 
 
+def run_trees(m, org: np.ndarray, pred: np.ndarray, poc: int, qp: int, min_size: int = 16) -> list:
+    """org / pred: [frames, height, width]; m: an MltCnn with tree_sizes(min_size) loaded -> one {"nodes", "leaf_map", "first_node"} per frame, all from ONE
+    call (MltCnn.predict_trees); frame f takes poc + f."""
+    assert org.shape == pred.shape and org.ndim == 3
+    frames, height, width = org.shape
+    pics = [(m.picture(width, height).upload(org[f]), m.picture(width, height).upload(pred[f])) for f in range(frames)]
+    try:
+        return m.predict_trees(pics, [poc + f for f in range(frames)], qp, top=128, min_size=min_size, want=("leaf_map",))
+    finally:
+        for a, b in pics:
+            a.close()
+            b.close()
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("org")
@@ -134,12 +178,15 @@ def parse_args(argv=None):
     ap.add_argument("--out", required=True, help="prefix of the .npy maps")
     ap.add_argument("--tree", action="store_true", help="the partition tree (quadtree descent on the device) instead of the per-size maps")
     ap.add_argument("--min-size", type=int, default=None, help="with --tree: the smallest CU size of the descent (default 16)")
+    ap.add_argument("--frames", type=int, default=None, help="with --tree: the inputs hold this many frames; all trees from one call, --poc is the first frame's")
     args = ap.parse_args(argv)
     sizes = tuple(int(s) for s in args.sizes.split(",") if s)
     if not sizes or any(s not in SIZES for s in sizes) or (args.weights_dir is None) == (args.synthetic is None):
         ap.error("--sizes from 128,64,32,16 and exactly one of --weights-dir / --synthetic")
     if args.min_size is not None and not args.tree:
         ap.error("--min-size goes with --tree")
+    if args.frames is not None and (not args.tree or not 1 <= args.frames <= 256):
+        ap.error("--frames goes with --tree, 1 .. 256")
     if args.tree:
         if args.min_size is None:
             args.min_size = 16
@@ -153,8 +200,12 @@ def parse_args(argv=None):
 def main(argv=None):
     args = parse_args(argv)
     sizes = args.size_list
-    org = read_picture(args.org, args.width, args.height)
-    pred = read_picture(args.pred, org.shape[1], org.shape[0])
+    if args.frames is not None:
+        org = read_frames(args.org, args.frames, args.width, args.height)
+        pred = read_frames(args.pred, args.frames, org.shape[2], org.shape[1])
+    else:
+        org = read_picture(args.org, args.width, args.height)
+        pred = read_picture(args.pred, org.shape[1], org.shape[0])
     import mltcnn_pkg
     pkg = mltcnn_pkg.load()
     blobs = None
@@ -167,6 +218,14 @@ def main(argv=None):
         if args.coverage > 0 or args.max_modes > 0:
             m.set_candidate_policy(s, args.coverage, args.max_modes)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    if args.tree and args.frames is not None:
+        for f, t in enumerate(run_trees(m, org, pred, args.poc, args.qp, args.min_size)):
+            np.save(f"{args.out}_f{f}_tree_nodes.npy", t["nodes"])
+            np.save(f"{args.out}_f{f}_leafmap.npy", t["leaf_map"])
+            print(f"frame {f} (poc {args.poc + f}): {len(t['nodes'])} nodes from node {t['first_node']}  " +
+                  "  ".join(f"{size}: {count} ({desc} descend)" for size, count, desc in tree_summary(t["nodes"])))
+        m.close()
+        return 0
     if args.tree:
         t = run_tree(m, org, pred, args.poc, args.qp, args.min_size)
         np.save(f"{args.out}_tree_nodes.npy", t["nodes"])
