@@ -501,31 +501,35 @@ class MltCnn:
                                              ptr("split"), ptr("logits"), ptr("decisions"), ptr("candidates")))
         return out
 
-    def predict_tree(self, org_pic: Picture, pred_pic: Picture, poc: int, qp: int, top: int = 128, min_size: int = 16, descend: dict | None = None,
-                     by_candidates: bool = False, want=("leaf_map",)) -> dict:
-        """The partition tree of the picture pair (mlt_predict_tree): quadtree descent on the device from `top` down to `min_size`.
-        descend: {size: mask of the decision head's classes that mean "quad split"} (default 1 << 1 everywhere).
-        -> {"nodes": TREE_NODE_DTYPE [n] in the contract's order} + for the names in `want`: "leaf_map" uint8 [height // 16, width // 16],
-        "logits" float32 [n, 15] (a 128 node fills the first 9 of its row, the rest stays 0), "decisions", "candidates" (one record per node)."""
-        assert set(want) <= {"leaf_map", "logits", "decisions", "candidates"}
+    @staticmethod
+    def _tree_config(top, min_size, descend, by_candidates, poc=0, qp=0) -> MltTreeConfig:
         cfg = MltTreeConfig()
         cfg.struct_size = C.sizeof(MltTreeConfig)
         cfg.top_size, cfg.min_size, cfg.poc, cfg.qp = int(top), int(min_size), int(poc), int(qp)
         cfg.flags = TREE_BY_CANDIDATES if by_candidates else 0
         for i, s in enumerate((128, 64, 32, 16)):
             cfg.descend_mask[i] = int((descend or {}).get(s, 0))
+        return cfg
+
+    @staticmethod
+    def _tree_outputs(want, cap: int, map_shape):
+        """-> the zeroed arrays named in `want` (`cap` rows per node array, one leaf map of map_shape) and the pointer-or-None of a name."""
+        assert set(want) <= {"leaf_map", "logits", "decisions", "candidates"}
+        rows = max(cap, 1)
+        shapes = {"leaf_map": (map_shape, np.uint8), "logits": ((rows, 15), np.float32), "decisions": ((rows,), DECISION_DTYPE), "candidates": ((rows,), CANDIDATES_DTYPE)}
+        out = {k: np.zeros(*shapes[k]) for k in shapes if k in want}
+        return out, lambda k: out[k].ctypes.data if k in out else None
+
+    def predict_tree(self, org_pic: Picture, pred_pic: Picture, poc: int, qp: int, top: int = 128, min_size: int = 16, descend: dict | None = None,
+                     by_candidates: bool = False, want=("leaf_map",)) -> dict:
+        """The partition tree of the picture pair (mlt_predict_tree): quadtree descent on the device from `top` down to `min_size`.
+        descend: {size: mask of the decision head's classes that mean "quad split"} (default 1 << 1 everywhere).
+        -> {"nodes": TREE_NODE_DTYPE [n] in the contract's order} + for the names in `want`: "leaf_map" uint8 [height // 16, width // 16],
+        "logits" float32 [n, 15] (a 128 node fills the first 9 of its row, the rest stays 0), "decisions", "candidates" (one record per node)."""
+        cfg = self._tree_config(top, min_size, descend, by_candidates, poc, qp)
         cap = tree_max_nodes(org_pic.width, org_pic.height, top, min_size)
         nodes = np.zeros((max(cap, 1),), TREE_NODE_DTYPE)
-        out = {}
-        if "leaf_map" in want:
-            out["leaf_map"] = np.zeros((org_pic.height // 16, org_pic.width // 16), np.uint8)
-        if "logits" in want:
-            out["logits"] = np.zeros((max(cap, 1), 15), np.float32)
-        if "decisions" in want:
-            out["decisions"] = np.zeros((max(cap, 1),), DECISION_DTYPE)
-        if "candidates" in want:
-            out["candidates"] = np.zeros((max(cap, 1),), CANDIDATES_DTYPE)
-        ptr = lambda k: out[k].ctypes.data if k in out else None
+        out, ptr = self._tree_outputs(want, cap, (org_pic.height // 16, org_pic.width // 16))
         n = C.c_int(0)
         self._check(self._lib.mlt_predict_tree(self._h, org_pic._h, pred_pic._h, C.byref(cfg), nodes.ctypes.data, cap, C.byref(n), ptr("leaf_map"),
                                                ptr("logits"), 15, ptr("decisions"), ptr("candidates")))
@@ -541,7 +545,6 @@ class MltCnn:
         for all pairs or one per pair; the other arguments as predict_tree.
         -> one dict per pair, shaped like predict_tree's ("logits" rows are zero beyond the size's logit count) + "first_node": the pair's first index in the call's
         node array."""
-        assert set(want) <= {"leaf_map", "logits", "decisions", "candidates"}
         pairs = list(pairs)
         P = len(pairs)
         poc = np.broadcast_to(np.asarray(poc, np.int32), (P,))
@@ -549,26 +552,12 @@ class MltCnn:
         entries = (MltTreePicture * max(P, 1))()
         for i, (o, q) in enumerate(pairs):
             entries[i].org, entries[i].pred, entries[i].poc, entries[i].qp = o._h, q._h, int(poc[i]), int(qp[i])
-        cfg = MltTreeConfig()
-        cfg.struct_size = C.sizeof(MltTreeConfig)
-        cfg.top_size, cfg.min_size = int(top), int(min_size)
-        cfg.flags = TREE_BY_CANDIDATES if by_candidates else 0
-        for i, s in enumerate((128, 64, 32, 16)):
-            cfg.descend_mask[i] = int((descend or {}).get(s, 0))
+        cfg = self._tree_config(top, min_size, descend, by_candidates)
         w, h = (pairs[0][0].width, pairs[0][0].height) if P else (0, 0)
         cap = P * tree_max_nodes(w, h, top, min_size)
         nodes = np.zeros((max(cap, 1),), TREE_NODE_DTYPE)
         first = np.zeros((P + 1,), np.int32)
-        out = {}
-        if "leaf_map" in want:
-            out["leaf_map"] = np.zeros((max(P, 1), h // 16, w // 16), np.uint8)
-        if "logits" in want:
-            out["logits"] = np.zeros((max(cap, 1), 15), np.float32)
-        if "decisions" in want:
-            out["decisions"] = np.zeros((max(cap, 1),), DECISION_DTYPE)
-        if "candidates" in want:
-            out["candidates"] = np.zeros((max(cap, 1),), CANDIDATES_DTYPE)
-        ptr = lambda k: out[k].ctypes.data if k in out else None
+        out, ptr = self._tree_outputs(want, cap, (max(P, 1), h // 16, w // 16))
         self._check(self._lib.mlt_predict_trees(self._h, P, entries, C.byref(cfg), nodes.ctypes.data, cap, first.ctypes.data, ptr("leaf_map"),
                                                 ptr("logits"), 15, ptr("decisions"), ptr("candidates")))
         res = []

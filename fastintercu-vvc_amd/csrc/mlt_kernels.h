@@ -296,7 +296,11 @@ struct PictureGatherArgs {
   int vec_org, vec_pred;       // the plane's extent starts and ends on 16-byte boundaries: aligned 16-byte loads may be used (else 2-byte loads only)
 };
 hipError_t mlt_launch_picture_gather(const PictureGatherArgs &a, hipStream_t st);
-// ---- partition trees (mlt_predict_tree): the quadtree descent between two network levels (mlt_tree_kernels.inc) ----
+// ---- partition trees (mlt_predict_tree, mlt_predict_trees): the quadtree descent between two network levels (mlt_tree_kernels.inc).  The arena is LEVEL-MAJOR
+// over the pictures of the call (mlt_predict_tree: one) -- level l is one node range, picture 0's segment, then picture 1's, ...; a segment in the contract's order
+// (roots, then children in their parents' order) ----
+#define MLT_TREES_LEVELS 4
+#define MLT_TREES_ROW 15      // floats of a node's logits row, in the arena and in the packed output (include/mltcnn.h: MLT_MAX_LOGITS; mlt_runtime.h asserts it)
 // A node of the tree (include/mltcnn.h: mlt_tree_node -- same 32 bytes; mlt_runtime.h asserts the layout).
 struct TreeNodeRec {
   int32_t x, y;
@@ -307,36 +311,7 @@ struct TreeNodeRec {
   float confidence;
   uint32_t cand_mask;
 };
-struct TreeExpandArgs {
-  TreeNodeRec *nodes;          // every node of the tree, in the contract's order; node_cap entries
-  int32_t *xy;                 // [node_cap][2]: the nodes' positions -- a level's slice is the position list its network pass gathers from
-  int node_cap;
-  int lvl_start, lvl_n;        // the level just evaluated: nodes [lvl_start, lvl_start + lvl_n); lvl_n == 0 with size = 2 x top_size, depth = -1 opens the tree
-  int size, depth;             // its CU size and depth; the next level's are size / 2 and depth + 1
-  const DecisionRec *dec;      // [lvl_n] the level's decision records
-  const CandRec *cand;         // [lvl_n] its candidate records, or NULL: cand_mask = 1 << raw_mode, every class when a logit of the decision head is NaN
-  const float *logits;         // [lvl_n][n_logits] (read only when cand == NULL)
-  int n_logits, head_off, head_classes;   // the decision head inside a row of logits
-  uint32_t descend_mask;       // classes of the decision head that mean "quad split"; 0: the level never descends (min_size)
-  int by_candidates;           // descend on cand_mask & descend_mask instead of on split_mode
-  const int32_t *next_roots;   // [n_next_roots][2] the next level's roots, raster order
-  int n_next_roots, root_flags;   // root_flags: their mlt_tree_node.flags (bit 0 below top_size)
-  int32_t *count;              // [1] out: the next level's node count = n_next_roots + 4 x descending parents (NULL: not wanted)
-};
-struct TreeRasterArgs {
-  const TreeNodeRec *nodes;
-  int lvl_start, lvl_n;
-  int blk_l;                   // log2(size / 16): a node covers (1 << blk_l)^2 map bytes
-  uint8_t *map;                // [map_h][map_w], one byte per 16 x 16 block
-  int map_w, map_h;
-};
-hipError_t mlt_launch_tree_expand(const TreeExpandArgs &a, hipStream_t st);
-hipError_t mlt_launch_tree_raster(const TreeRasterArgs &a, hipStream_t st);
-// ---- partition trees of several pictures in one call (mlt_predict_trees): the arena is LEVEL-MAJOR over all pictures -- level l is one node range, picture 0's
-// segment, then picture 1's, ...; a segment in the single tree's order (roots, then children in their parents' order) ----
-#define MLT_TREES_LEVELS 4
-#define MLT_TREES_ROW 15      // floats of a node's logits row, in the arena and in the output (include/mltcnn.h: MLT_MAX_LOGITS; mlt_runtime.h asserts it)
-// One entry of the call (mlt_tree_picture as the device sees it): the gather's per-launch arguments of the one-picture path, per entry.
+// One entry of mlt_predict_trees (mlt_tree_picture as the device sees it): the gather's per-launch arguments of the one-picture path, per entry.
 struct TreesEntry {
   const int16_t *org, *pred;   // sample (0, 0)
   long org_pitch, pred_pitch;  // elements
@@ -346,13 +321,35 @@ struct TreesEntry {
 // The segment table, [MLT_TREES_LEVELS][n_pictures] each: where picture p's nodes of level l start in the arena, how many they are, and where they start in the
 // packed (picture-major) output.  Written by the expand launches (a level's rows by the launch that writes the level's nodes; pack_base by the last one).
 struct TreesSegs { int32_t *start, *n, *pack_base; };
-struct TreesExpandArgs {
-  TreeExpandArgs t;            // the level as one list; t.next_roots / t.n_next_roots: the roots EVERY picture's next segment opens with; t.count: the whole next level
-  int32_t *pic;                // [node_cap] picture index of every node, beside t.xy
+struct TreeExpandArgs {
+  TreeNodeRec *nodes;          // every node of the call, level-major; node_cap entries
+  int32_t *xy;                 // [node_cap][2]: the nodes' positions -- a level's slice is the position list its network pass gathers from
+  int32_t *pic;                // [node_cap] picture index of every node, beside xy
+  int node_cap;
+  int lvl_start, lvl_n;        // the level just evaluated, as one list over all pictures: nodes [lvl_start, lvl_start + lvl_n)
+  int size;                    // its CU size; the next level's is size / 2
+  int lvl, n_levels;           // its depth; lvl = -1 with lvl_n = 0 and size = 2 x top_size opens the trees; lvl == n_levels - 1: the last launch also writes pack_base and first_node
+  const DecisionRec *dec;      // [lvl_n] the level's decision records
+  const CandRec *cand;         // [lvl_n] its candidate records, or NULL: cand_mask = 1 << raw_mode, every class when a logit of the decision head is NaN
+  const float *logits;         // [lvl_n][n_logits] (read only when cand == NULL)
+  int n_logits, head_off, head_classes;   // the decision head inside a row of logits
+  uint32_t descend_mask;       // classes of the decision head that mean "quad split"; 0: the level never descends (min_size)
+  int by_candidates;           // descend on cand_mask & descend_mask instead of on split_mode
+  const int32_t *next_roots;   // [n_next_roots][2] the roots EVERY picture's next segment opens with, raster order
+  int n_next_roots, root_flags;   // root_flags: their mlt_tree_node.flags (bit 0 below top_size)
+  int32_t *count;              // [1] out: the whole next level's node count = n_pictures x n_next_roots + 4 x descending parents (NULL: not wanted)
   TreesSegs segs;
   int n_pictures;
-  int lvl, n_levels;           // t.depth = lvl (-1 opens the tree); lvl == n_levels - 1: the last launch also writes pack_base and first_node
   int32_t *first_node;         // [n_pictures + 1] out (last launch)
+};
+struct TreeRasterArgs {
+  const TreeNodeRec *nodes;
+  const int32_t *pic;
+  int lvl_start, lvl_n;
+  int blk_l;                   // log2(size / 16): a node covers (1 << blk_l)^2 map bytes
+  uint8_t *map;                // [n_pictures][map_h][map_w], one byte per 16 x 16 block: picture p's map starts at map + p * map_bytes
+  size_t map_bytes;
+  int map_w, map_h;
 };
 struct PictureGatherMultiArgs {
   const TreesEntry *entries;   // [n_entries]
@@ -362,11 +359,6 @@ struct PictureGatherMultiArgs {
   int32_t *g_poc, *g_qp;       // [c] out: the CU's entry's poc / qp
   int c, s_l, n_entries;
 };
-struct TreesRasterArgs {
-  TreeRasterArgs t;            // t.map: picture 0's map
-  const int32_t *pic;
-  size_t map_bytes;            // picture p's map starts at t.map + p * map_bytes
-};
 struct TreesPackArgs {
   const TreeNodeRec *nodes; const int32_t *pic; const float *logits; const DecisionRec *dec; const CandRec *cand;   // level-major (logits / dec / cand: NULL = not wanted)
   TreeNodeRec *o_nodes; float *o_logits; DecisionRec *o_dec; CandRec *o_cand;                                       // picture-major; o_logits: MLT_TREES_ROW floats per node
@@ -375,9 +367,9 @@ struct TreesPackArgs {
   int n_pictures, n_levels, total;
   int lvl_start[MLT_TREES_LEVELS], n_logits[MLT_TREES_LEVELS];   // a level's logits are dense [lvl_n][n_logits] from row lvl_start of the MLT_TREES_ROW-float rows
 };
-hipError_t mlt_launch_trees_expand(const TreesExpandArgs &a, hipStream_t st);
+hipError_t mlt_launch_tree_expand(const TreeExpandArgs &a, hipStream_t st);
+hipError_t mlt_launch_tree_raster(const TreeRasterArgs &a, hipStream_t st);
 hipError_t mlt_launch_picture_gather_multi(const PictureGatherMultiArgs &a, hipStream_t st);
-hipError_t mlt_launch_trees_raster(const TreesRasterArgs &a, hipStream_t st);
 hipError_t mlt_launch_trees_pack(const TreesPackArgs &a, hipStream_t st);
 hipError_t mlt_launch_flat_stat(const FlatStatArgs &a, bool aligned8, hipStream_t st);
 hipError_t mlt_launch_guard_select(const GuardSelectArgs &a, hipStream_t st);

@@ -281,7 +281,7 @@ template <int Q, class ACC = float16v> __device__ __forceinline__ half4 act_quad
 #include "mlt_layer1_kernel.inc"  // layer1_stream_kernel
 #include "mlt_tail_kernels.inc"   // heads_kernel, flat_stat / guard kernels
 #include "mlt_picture_kernels.inc"  // picture_gather_kernel, picture_gather_multi_kernel
-#include "mlt_tree_kernels.inc"  // tree_expand_kernel, tree_raster_kernel, trees_expand_kernel, trees_raster_kernel, tree_pack_kernel
+#include "mlt_tree_kernels.inc"  // tree_expand_kernel, tree_raster_kernel, tree_pack_kernel
 
 // ---------------------------------------------------------------------------------------------
 // launchers
@@ -859,6 +859,7 @@ hipError_t mlt_launch_picture_gather(const PictureGatherArgs &a, hipStream_t st)
 
 // ONE workgroup: the ordered compaction carries its running base from tile to tile (mlt_tree_kernels.inc)
 hipError_t mlt_launch_tree_expand(const TreeExpandArgs &a, hipStream_t st) {
+  if (a.n_pictures < 1 || a.n_pictures > MLT_TREES_MAX_PICTURES_K) return hipErrorInvalidValue;   // the per-picture ranks live in LDS arrays of that size
   hipLaunchKernelGGL(tree_expand_kernel, dim3(1), dim3(MLT_TREE_TILE), 0, st, a);
   return hipGetLastError();
 }
@@ -872,26 +873,12 @@ hipError_t mlt_launch_tree_raster(const TreeRasterArgs &a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// ---- trees of several pictures in one call: the same launch shapes as their one-picture forms ----
+// picture_gather_kernel's launch shape
 hipError_t mlt_launch_picture_gather_multi(const PictureGatherMultiArgs &a, hipStream_t st) {
   const size_t items = (size_t)a.c << (2 * a.s_l - 2);
   if (!items) return hipSuccess;
   const size_t want = (items + 255) / 256;
   hipLaunchKernelGGL(picture_gather_multi_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-hipError_t mlt_launch_trees_expand(const TreesExpandArgs &a, hipStream_t st) {
-  if (a.n_pictures < 1 || a.n_pictures > MLT_TREES_MAX_PICTURES_K) return hipErrorInvalidValue;   // the per-picture ranks live in LDS arrays of that size
-  hipLaunchKernelGGL(trees_expand_kernel, dim3(1), dim3(MLT_TREE_TILE), 0, st, a);
-  return hipGetLastError();
-}
-
-hipError_t mlt_launch_trees_raster(const TreesRasterArgs &a, hipStream_t st) {
-  const size_t items = (size_t)a.t.lvl_n << (2 * a.t.blk_l);
-  if (!items) return hipSuccess;
-  const size_t want = (items + 255) / 256;
-  hipLaunchKernelGGL(trees_raster_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

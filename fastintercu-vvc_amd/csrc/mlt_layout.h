@@ -93,23 +93,11 @@ struct ResultSet : CuFields {
     split = put(cap * 4); lg = put(cap * nl * 4); dec = put(cap * sizeof(mlt_decision), 4, records); cand = put(cap * sizeof(mlt_candidates), 4, cands);
   }
 };
-// mlt_predict_tree's device arena, indexed by node: nodes | xy | logits (kRow floats per node) | records [| candidate records] | roots | leaf map | count.
+// The device arena of a tree call (mlt_predict_tree: pics = 1, !packed; mlt_predict_trees: packed) for `pics` pictures of up to n nodes each, indexed by node and
+// LEVEL-major (a level of all pictures is one node range): nodes | xy | logits (kRow floats per node) | records [| candidate records] | roots | one leaf map per
+// picture | count | the per-node picture index | the segment table ([kLevels][pics]: start, count, start in the output) | first_node [pics + 1]; packed: | the entry
+// table (entry_bytes each) | the picture-major output: nodes [| logits] [| records] [| candidate records].
 struct TreeArena : Carved {
-  static const int kRow = MLT_MAX_LOGITS;
-  struct Ptrs { TreeNodeRec *nodes; int32_t *xy; float *logits; DecisionRec *dec; CandRec *cand; int32_t *roots; uint8_t *map; int32_t *count; };
-  Field nodes, xy, logits, dec, cand, roots, map, count;
-  TreeArena(size_t n, size_t n_roots, size_t map_bytes, bool cands) {
-    nodes = put(n * sizeof(mlt_tree_node), 256); xy = put(n * 8, 256); logits = put(n * kRow * 4, 256); dec = put(n * sizeof(mlt_decision), 256);
-    cand = put(n * sizeof(mlt_candidates), 256, cands); roots = put(n_roots * 8, 256); map = put(map_bytes, 256); count = put(4, 256);
-  }
-  Ptrs at(char *b) const {
-    return Ptrs{nodes.in<TreeNodeRec>(b), xy.in<int32_t>(b), logits.in<float>(b), dec.in<DecisionRec>(b), cand.in<CandRec>(b), roots.in<int32_t>(b), map.in<uint8_t>(b), count.in<int32_t>(b)};
-  }
-};
-// mlt_predict_trees' device arena for `pics` pictures of up to n nodes each, on the same buffer of the context: the parts of TreeArena over pics x n nodes, LEVEL-major
-// (a level of all pictures is one node range) and one map per picture | the per-node picture index | the segment table ([4 levels][pics]: start, count, start in the
-// output) | first_node [pics + 1] | the entry table (entry_bytes each) | the picture-major output: nodes [| logits] [| records] [| candidate records].
-struct TreesArena : Carved {
   static const int kRow = MLT_MAX_LOGITS, kLevels = 4;
   struct Ptrs {
     TreeNodeRec *nodes; int32_t *xy; float *logits; DecisionRec *dec; CandRec *cand; int32_t *roots; uint8_t *map; int32_t *count;
@@ -117,14 +105,14 @@ struct TreesArena : Carved {
     TreeNodeRec *o_nodes; float *o_logits; DecisionRec *o_dec; CandRec *o_cand;
   };
   Field nodes, xy, logits, dec, cand, roots, map, count, pic, seg_start, seg_n, pack_base, first_node, entries, o_nodes, o_logits, o_dec, o_cand;
-  TreesArena(size_t pics, size_t n, size_t n_roots, size_t map_bytes, size_t entry_bytes, bool cands, bool out_logits, bool out_dec, bool out_cand) {
+  TreeArena(size_t pics, size_t n, size_t n_roots, size_t map_bytes, size_t entry_bytes, bool cands, bool packed, bool out_logits, bool out_dec, bool out_cand) {
     const size_t N = pics * n;
     nodes = put(N * sizeof(mlt_tree_node), 256); xy = put(N * 8, 256); logits = put(N * kRow * 4, 256); dec = put(N * sizeof(mlt_decision), 256);
     cand = put(N * sizeof(mlt_candidates), 256, cands); roots = put(n_roots * 8, 256); map = put(pics * map_bytes, 256); count = put(4, 256);
     pic = put(N * 4, 256); seg_start = put(kLevels * pics * 4, 256); seg_n = put(kLevels * pics * 4, 256); pack_base = put(kLevels * pics * 4, 256);
-    first_node = put((pics + 1) * 4, 256); entries = put(pics * entry_bytes, 256);
-    o_nodes = put(N * sizeof(mlt_tree_node), 256); o_logits = put(N * kRow * 4, 256, out_logits); o_dec = put(N * sizeof(mlt_decision), 256, out_dec);
-    o_cand = put(N * sizeof(mlt_candidates), 256, out_cand);
+    first_node = put((pics + 1) * 4, 256); entries = put(pics * entry_bytes, 256, packed);
+    o_nodes = put(N * sizeof(mlt_tree_node), 256, packed); o_logits = put(N * kRow * 4, 256, packed && out_logits); o_dec = put(N * sizeof(mlt_decision), 256, packed && out_dec);
+    o_cand = put(N * sizeof(mlt_candidates), 256, packed && out_cand);
   }
   Ptrs at(char *b) const {
     return Ptrs{nodes.in<TreeNodeRec>(b), xy.in<int32_t>(b), logits.in<float>(b), dec.in<DecisionRec>(b), cand.in<CandRec>(b), roots.in<int32_t>(b), map.in<uint8_t>(b),

@@ -3,7 +3,7 @@
 // A picture is a pitched int16 luma plane per device of its context.  mlt_predict_at validates the positions on the host, then per chunk: positions + poc + qp H2D,
 // picture_gather_kernel (mlt_picture_kernels.inc) -> the dense [c][S][S] planes of a staging set, run_checked on those planes -- the launches, guards and exact
 // re-runs of mlt_predict_batch_device, so every result is the dense path's bit for bit -- results D2H.  The network kernels know nothing about pictures.
-// predict_at_chunks is that per-chunk pass; mlt_predict_tree (mlt_tree.cpp) runs it on position lists that already live on the device.
+// predict_at_chunks is that per-chunk pass; the tree descent (mlt_tree.cpp: mlt_predict_tree, mlt_predict_trees) runs it on position lists that already live on the device.
 #include "mlt_runtime.h"
 
 namespace {
@@ -26,8 +26,8 @@ void release(mlt_ctx *ctx, mlt_picture *pic) {
 }  // namespace
 
 // One device: CUs [0, n) of a position list from the planes this device holds (dev: the device's own context), in chunks of the pass size.  Host lists
-// (mlt_predict_at): positions, poc and qp go H2D per chunk and the results D2H.  Device lists (mlt_predict_tree: at.device): the gather reads the positions where
-// they are, every CU takes (poc_all, qp_all) -- or, for a list over several picture pairs (mlt_predict_trees: at.pic), its entry's planes, poc and qp from the
+// (mlt_predict_at): positions, poc and qp go H2D per chunk and the results D2H.  Device lists (the tree descent: at.device): the gather reads the positions where
+// they are, every CU takes (poc_all, qp_all) -- or, for a list over several picture pairs (a descent over more than one picture: at.pic), its entry's planes, poc and qp from the
 // device table, through picture_gather_multi_kernel -- and the network writes logits and records straight into the caller's device arrays (every store to them is a
 // 4-byte or a struct store: no alignment beyond the arrays' own is assumed) -- the launches in between are the same, so are the results.
 int predict_at_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &pl, int n, const AtList &at, const AtOut &out) {

@@ -293,7 +293,7 @@ struct mlt_ctx {
   int guard_phase[2] = {0, 0};    // which counter of a slot's pair the next batch launch counts on (GuardSlot.phase)
   hipEvent_t ev_guard = nullptr;  // "count of flagged CUs has landed" (device-pointer entry)
   GrowBuf gstage;
-  // mlt_predict_tree's / mlt_predict_trees' device arena (Lay::TreeArena / Lay::TreesArena) and its pinned count
+  // mlt_predict_tree's / mlt_predict_trees' device arena (Lay::TreeArena) and its pinned count
   GrowBuf tree_dev;
   int32_t *tree_host = nullptr;
   std::vector<mlt_picture *> pictures;  // every picture created on / wrapped for this context (mlt_pictures.cpp); what is left is released by mlt_shutdown
@@ -319,7 +319,7 @@ static_assert(offsetof(mlt_decision, confidence) == offsetof(DecisionRec, confid
 static_assert(sizeof(mlt_tree_node) == 32 && sizeof(TreeNodeRec) == 32 && offsetof(mlt_tree_node, size) == offsetof(TreeNodeRec, size) && offsetof(mlt_tree_node, parent) == 12 &&
               offsetof(TreeNodeRec, parent) == 12 && offsetof(mlt_tree_node, cand_mask) == offsetof(TreeNodeRec, cand_mask) && offsetof(mlt_tree_node, cand_mask) == 28, "mlt_tree_node layout");
 static_assert(sizeof(mlt_tree_config) == 40, "mlt_tree_config is 40 bytes");
-static_assert(sizeof(mlt_tree_picture) == 24 && MLT_TREES_ROW == MLT_MAX_LOGITS && MLT_TREES_LEVELS == Lay::TreesArena::kLevels && sizeof(TreesEntry) == 48, "mlt_predict_trees layouts");
+static_assert(sizeof(mlt_tree_picture) == 24 && MLT_TREES_ROW == MLT_MAX_LOGITS && MLT_TREES_LEVELS == Lay::TreeArena::kLevels && sizeof(TreesEntry) == 48, "mlt_predict_trees layouts");
 
 static_assert(sizeof(mlt_candidates) == 40 && sizeof(CandRec) == sizeof(mlt_candidates) && offsetof(mlt_candidates, order) == offsetof(CandRec, order) &&
               offsetof(mlt_candidates, prob) == offsetof(CandRec, prob) && offsetof(mlt_candidates, prob) == 16, "mlt_candidates layout");

@@ -1,10 +1,12 @@
 // mlt_tree.cpp -- partition trees of a picture (include/mltcnn.h): mlt_predict_tree, mlt_predict_trees, mlt_tree_roots, mlt_tree_max_nodes.
 //
-// Per level: the network on the level's nodes -- predict_at_chunks (mlt_pictures.cpp) on the slice of the device-resident position list that IS the level, so
-// launches, guards and exact re-runs are mlt_predict_at's and so is every result -- then tree_expand_kernel (mlt_tree_kernels.inc): the level's decisions into its
-// node records, the next level's nodes and positions behind them, the next level's count; tree_raster_kernel paints the level's leaves into the map; one 4-byte
-// count comes back.  Nodes, positions and the per-node logits / records are indexed by NODE in one device arena, so a level's arrays are slices of the tree's and the
-// end of the call is a handful of D2H copies.
+// Both calls run ONE descent (descend below) over the trees of P picture pairs of one geometry; mlt_predict_tree is P = 1.  Per level: the network on the level's
+// nodes -- predict_at_chunks (mlt_pictures.cpp) on the slice of the device-resident position list that IS the level, over all pictures, so launches, guards and
+// exact re-runs are mlt_predict_at's and so is every result -- then tree_expand_kernel (mlt_tree_kernels.inc): the level's decisions into its node records, the next
+// level's nodes and positions behind them, the next level's count; tree_raster_kernel paints the level's leaves into the maps; one 4-byte count comes back.  Nodes,
+// positions and the per-node logits / records are indexed by NODE in one device arena, LEVEL-major (picture 0's segment of a level, picture 1's, ...), so a level's
+// arrays are slices of the arena's.  One picture's arena is already in the contract's order and mlt_predict_tree ends in a handful of D2H copies;
+// mlt_predict_trees lets tree_pack_kernel permute into the picture-major order of its contract first, then one D2H copy per requested array.
 #include "mlt_runtime.h"
 
 namespace {
@@ -66,6 +68,104 @@ void tree_roots_of(int W, int H, int top, int L, TreeRoots &r) {
   }
 }
 
+// which optional outputs a tree call delivers | what a descent leaves behind: the arena, the node count over all pictures and every level's node range
+struct TreeWant { bool map, logits, dec, cand; };
+struct Descent { Lay::TreeArena::Ptrs A; size_t map_bytes; int total, start[4], n[4]; };
+
+// The descent of the trees of pics[0 .. P) (W x H each, checked by the caller) on this context's own device; everything stays in the arena, enqueued or done.
+// packed: the arena also carries the entry table and tree_pack_kernel's picture-major output.
+int descend(mlt_ctx *ctx, const char *who, const TreeLevels &lv, int W, int H, int P, const mlt_tree_picture *pics, bool by_cand, bool packed, const TreeWant &want,
+            Descent &d) {
+  if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
+  const int top = lv.top, L = lv.L, max_nodes = mlt_tree_max_nodes(W, H, top, lv.mn), N = P * max_nodes;
+  int rc;
+  // candidate records come from the heads launch only where cand_mask can differ from 1 << raw_mode (a policy is set) or the caller asks for them
+  bool want_cand[4], any_cand = false;
+  for (int l = 0; l < L; ++l) any_cand = (want_cand[l] = want.cand || by_cand || lv.st[l]->cand_policy()) || any_cand;
+  TreeRoots tr;
+  tree_roots_of(W, H, top, L, tr);
+  const int map_w = W / 16, map_h = H / 16;
+  const size_t map_bytes = d.map_bytes = (size_t)map_w * map_h;
+  const Lay::TreeArena arena((size_t)P, (size_t)max_nodes, tr.xy.size() / 2, map_bytes, sizeof(TreesEntry), any_cand, packed, want.logits, want.dec, want.cand);
+  if ((rc = ctx->tree_dev.reserve(ctx, arena.bytes(), who))) return rc;
+  if (!ctx->tree_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->tree_host, 64, hipHostMallocDefault));
+  const Lay::TreeArena::Ptrs A = d.A = arena.at(ctx->tree_dev.p);
+  // One pair: its planes, poc and qp are launch arguments of the gather (no table lookup per item).  Several: the entry table, looked up through the nodes' pic.
+  const AtPlanes planes = P == 1 ? AtPlanes::of(pics[0].org, pics[0].pred, 0) : AtPlanes{};
+  if (P > 1) {
+    std::vector<TreesEntry> entries((size_t)P);
+    for (int p = 0; p < P; ++p) {
+      const AtPlanes pl = AtPlanes::of(pics[p].org, pics[p].pred, 0);
+      entries[(size_t)p] = TreesEntry{pl.org, pl.pred, pl.org_pitch, pl.pred_pitch, pl.org_vec ? 1 : 0, pl.pred_vec ? 1 : 0, pics[p].poc, pics[p].qp};
+    }
+    // (pageable sources: both copies have read them when they return)
+    HIP_TRY(ctx, hipMemcpyAsync(A.entries, entries.data(), entries.size() * sizeof(TreesEntry), hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (!tr.xy.empty()) HIP_TRY(ctx, hipMemcpyAsync(A.roots, tr.xy.data(), tr.xy.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (want.map) HIP_TRY(ctx, hipMemsetAsync(A.map, 0xFF, (size_t)P * map_bytes, ctx->stream));
+  Launch prof{ctx};
+  auto expand = [&](const TreeExpandArgs &ea) -> int {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int r;
+    // algorithmic bytes the host knows: the level's records and picture indices read and its node fields written, every picture's next roots written, the segment
+    // table's rows (the children's count is the device's)
+    if ((r = prof.prof_begin("tree_expand", 0.0, (double)ea.lvl_n * (sizeof(DecisionRec) + 20) + (double)P * ea.n_next_roots * (sizeof(TreeNodeRec) + 12) + (double)P * 8, e0, e1)))
+      return r;
+    HIP_TRY(ctx, mlt_launch_tree_expand(ea, ctx->stream));
+    return prof.prof_end(e1);
+  };
+  TreeExpandArgs ea{};
+  ea.nodes = A.nodes; ea.xy = A.xy; ea.pic = A.pic; ea.node_cap = N; ea.by_candidates = by_cand ? 1 : 0;
+  ea.segs = TreesSegs{A.seg_start, A.seg_n, A.pack_base}; ea.n_pictures = P; ea.n_levels = L; ea.first_node = A.first_node;
+  // the trees open: no parents, every picture's top-level roots
+  ea.lvl_start = 0; ea.lvl_n = 0; ea.size = 2 * top; ea.lvl = -1;
+  ea.next_roots = A.roots; ea.n_next_roots = tr.n[0]; ea.root_flags = 0; ea.count = nullptr;
+  if ((rc = expand(ea))) return rc;
+  int start = 0, n = P * tr.n[0];
+  for (int l = 0, S = top; l < L; ++l, S >>= 1) {
+    SizeState *s = lv.st[l];
+    const bool last = l == L - 1;
+    d.start[l] = start; d.n[l] = n;
+    float *d_lg = A.logits + (size_t)start * kRowLogits;
+    DecisionRec *d_dec = A.dec + start;
+    CandRec *d_cand = want_cand[l] ? A.cand + start : nullptr;
+    if (n > 0) {
+      const AtOut out{nullptr, d_lg, (mlt_decision *)d_dec, (mlt_candidates *)d_cand};
+      const int32_t *d_xy = A.xy + 2 * (size_t)start;
+      const AtList list = P == 1 ? AtList::on_device(d_xy, pics[0].poc, pics[0].qp) : AtList::of_entries(d_xy, A.pic + start, (const TreesEntry *)A.entries, P);
+      if ((rc = predict_at_chunks(ctx, s, planes, n, list, out))) return rc;
+    }
+    ea.lvl_start = start; ea.lvl_n = n; ea.size = S; ea.lvl = l;
+    ea.dec = d_dec; ea.cand = d_cand; ea.logits = d_lg; ea.n_logits = s->model.n_logits;
+    ea.head_off = s->head_off(); ea.head_classes = s->head_classes();
+    ea.descend_mask = last ? 0u : lv.mask[l];
+    ea.next_roots = last ? nullptr : A.roots + 2 * (size_t)tr.off[l + 1];
+    ea.n_next_roots = last ? 0 : tr.n[l + 1];
+    ea.root_flags = 1;
+    ea.count = last ? nullptr : A.count;
+    if ((rc = expand(ea))) return rc;
+    if (n > 0 && want.map) {
+      TreeRasterArgs ra{};
+      ra.nodes = A.nodes; ra.pic = A.pic; ra.lvl_start = start; ra.lvl_n = n; ra.blk_l = ilog2(S) - 4; ra.map = A.map; ra.map_bytes = map_bytes; ra.map_w = map_w; ra.map_h = map_h;
+      hipEvent_t e0 = nullptr, e1 = nullptr;
+      // algorithmic bytes: every node record and picture index read once, one byte per block of a leaf written (at most the level's whole area)
+      if ((rc = prof.prof_begin("tree_raster", 0.0, (double)n * (sizeof(TreeNodeRec) + 4 + (double)(1 << (2 * ra.blk_l))), e0, e1))) return rc;
+      HIP_TRY(ctx, mlt_launch_tree_raster(ra, ctx->stream));
+      if ((rc = prof.prof_end(e1))) return rc;
+    }
+    start += n;
+    if (last) break;
+    // the one host synchronisation of the level beside the guards': how many nodes the next level has, over all pictures
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->tree_host, A.count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    n = ctx->tree_host[0];
+    const int nr = P * tr.n[l + 1];
+    if (n < nr || ((n - nr) & 3) || (long long)start + n > N) { ctx->err = std::string(who) + ": bad node count from the device"; return MLT_ERR_HIP; }
+  }
+  d.total = start;
+  return MLT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -95,13 +195,10 @@ int mlt_predict_tree(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pr
   TreeLevels lv;
   int rc;
   if ((rc = tree_levels(ctx, "mlt_predict_tree", cfg, lv))) return rc;
-  const int top = lv.top, mn = lv.mn, L = lv.L;
-  SizeState **st = lv.st;
-  const uint32_t *mask = lv.mask;
   if (!owns_picture(ctx, org) || !owns_picture(ctx, pred)) { ctx->err = "mlt_predict_tree: both pictures must belong to this context"; return MLT_ERR_ARG; }
   if (org->width != pred->width || org->height != pred->height) { ctx->err = "mlt_predict_tree: the two pictures differ in width or height"; return MLT_ERR_ARG; }
   const int W = org->width, H = org->height;
-  const int max_nodes = mlt_tree_max_nodes(W, H, top, mn);
+  const int max_nodes = mlt_tree_max_nodes(W, H, lv.top, lv.mn);
   if (node_cap < max_nodes) {
     char msg[160];
     std::snprintf(msg, sizeof msg, "mlt_predict_tree: node_cap %d is below mlt_tree_max_nodes = %d of a %d x %d picture", node_cap, max_nodes, W, H);
@@ -109,100 +206,30 @@ int mlt_predict_tree(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pr
     return MLT_ERR_ARG;
   }
   // ---- arguments are good: the tree runs on this context's own device (devices[0] of a multi-device context) ----
-  if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
-  const bool by_cand = (cfg->flags & MLT_TREE_BY_CANDIDATES) != 0;
-  // candidate records come from the heads launch only where cand_mask can differ from 1 << raw_mode (a policy is set) or the caller asks for them
-  bool want_cand[4], any_cand = false;
-  for (int l = 0; l < L; ++l) any_cand = (want_cand[l] = cand_opt || by_cand || st[l]->cand_policy()) || any_cand;
-  TreeRoots tr;
-  tree_roots_of(W, H, top, L, tr);
-  const std::vector<int32_t> &roots = tr.xy;
-  const int *root_off = tr.off, *n_roots = tr.n;
-  const int map_w = W / 16, map_h = H / 16;
-  const size_t map_bytes = (size_t)map_w * map_h;
-  const Lay::TreeArena arena((size_t)max_nodes, roots.size() / 2, map_bytes, any_cand);
-  if ((rc = ctx->tree_dev.reserve(ctx, arena.bytes(), "mlt_predict_tree"))) return rc;
-  if (!ctx->tree_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->tree_host, 64, hipHostMallocDefault));
-  const Lay::TreeArena::Ptrs A = arena.at(ctx->tree_dev.p);
-  if (!roots.empty()) HIP_TRY(ctx, hipMemcpyAsync(A.roots, roots.data(), roots.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(A.map, 0xFF, map_bytes, ctx->stream));
-  const AtPlanes pl = AtPlanes::of(org, pred, 0);
-  Launch prof{ctx};
-  auto expand = [&](const TreeExpandArgs &ea) -> int {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int r;
-    // algorithmic bytes the host knows: the level's records read and its node fields written, the next level's roots written (the children's count is the device's)
-    if ((r = prof.prof_begin("tree_expand", 0.0, (double)ea.lvl_n * (sizeof(DecisionRec) + 16) + (double)ea.n_next_roots * (sizeof(TreeNodeRec) + 16), e0, e1))) return r;
-    HIP_TRY(ctx, mlt_launch_tree_expand(ea, ctx->stream));
-    return prof.prof_end(e1);
-  };
-  TreeExpandArgs ea{};
-  ea.nodes = A.nodes; ea.xy = A.xy; ea.node_cap = max_nodes; ea.by_candidates = by_cand ? 1 : 0;
-  // the tree opens: no parents, the top level's roots
-  ea.lvl_start = 0; ea.lvl_n = 0; ea.size = 2 * top; ea.depth = -1;
-  ea.next_roots = A.roots; ea.n_next_roots = n_roots[0]; ea.root_flags = 0; ea.count = nullptr;
-  if ((rc = expand(ea))) return rc;
-  int start = 0, n = n_roots[0], lvl_start[4], lvl_n[4];
-  for (int l = 0, S = top; l < L; ++l, S >>= 1) {
-    SizeState *s = st[l];
-    const int nl = s->model.n_logits;
-    const bool last = l == L - 1;
-    lvl_start[l] = start; lvl_n[l] = n;
-    float *d_lg = A.logits + (size_t)start * kRowLogits;
-    DecisionRec *d_dec = A.dec + start;
-    CandRec *d_cand = want_cand[l] ? A.cand + start : nullptr;
-    if (n > 0) {
-      const AtOut out{nullptr, d_lg, (mlt_decision *)d_dec, (mlt_candidates *)d_cand};
-      if ((rc = predict_at_chunks(ctx, s, pl, n, AtList::on_device(A.xy + 2 * (size_t)start, cfg->poc, cfg->qp), out))) return rc;
-    }
-    ea.lvl_start = start; ea.lvl_n = n; ea.size = S; ea.depth = l;
-    ea.dec = d_dec; ea.cand = d_cand; ea.logits = d_lg; ea.n_logits = nl;
-    ea.head_off = s->head_off(); ea.head_classes = s->head_classes();
-    ea.descend_mask = last ? 0u : mask[l];
-    ea.next_roots = last ? nullptr : A.roots + 2 * (size_t)root_off[l + 1];
-    ea.n_next_roots = last ? 0 : n_roots[l + 1];
-    ea.root_flags = 1;
-    ea.count = last ? nullptr : A.count;
-    if ((rc = expand(ea))) return rc;
-    if (n > 0 && leaf_map_opt) {
-      TreeRasterArgs ra{};
-      ra.nodes = A.nodes; ra.lvl_start = start; ra.lvl_n = n; ra.blk_l = ilog2(S) - 4; ra.map = A.map; ra.map_w = map_w; ra.map_h = map_h;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      // algorithmic bytes: every node record read once, one byte per block of a leaf written (at most the level's whole area)
-      if ((rc = prof.prof_begin("tree_raster", 0.0, (double)n * (sizeof(TreeNodeRec) + (double)(1 << (2 * ra.blk_l))), e0, e1))) return rc;
-      HIP_TRY(ctx, mlt_launch_tree_raster(ra, ctx->stream));
-      if ((rc = prof.prof_end(e1))) return rc;
-    }
-    start += n;
-    if (last) break;
-    // the one host synchronisation of the level beside the guards': how many nodes the next level has
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->tree_host, A.count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    n = ctx->tree_host[0];
-    if (n < n_roots[l + 1] || ((n - n_roots[l + 1]) & 3) || (long long)start + n > max_nodes) { ctx->err = "mlt_predict_tree: bad node count from the device"; return MLT_ERR_HIP; }
-  }
-  // ---- results: everything the caller asked for, then one synchronisation ----
-  const int total = start;
-  if (total) HIP_TRY(ctx, hipMemcpyAsync(nodes, A.nodes, (size_t)total * sizeof(TreeNodeRec), hipMemcpyDeviceToHost, ctx->stream));
-  if (leaf_map_opt && map_bytes) HIP_TRY(ctx, hipMemcpyAsync(leaf_map_opt, A.map, map_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  for (int l = 0; l < L; ++l) {
-    if (!lvl_n[l]) continue;
-    const int nl = st[l]->model.n_logits;
-    const size_t s0 = (size_t)lvl_start[l], c = (size_t)lvl_n[l];
-    if (logits_opt)
+  const mlt_tree_picture one{org, pred, cfg->poc, cfg->qp};
+  Descent d;
+  if ((rc = descend(ctx, "mlt_predict_tree", lv, W, H, 1, &one, (cfg->flags & MLT_TREE_BY_CANDIDATES) != 0, false,
+                    TreeWant{leaf_map_opt != nullptr, logits_opt != nullptr, dec_opt != nullptr, cand_opt != nullptr}, d)))
+    return rc;
+  // ---- results: one picture's arena is in the contract's order; everything the caller asked for, then one synchronisation ----
+  const Lay::TreeArena::Ptrs &A = d.A;
+  if (d.total) HIP_TRY(ctx, hipMemcpyAsync(nodes, A.nodes, (size_t)d.total * sizeof(TreeNodeRec), hipMemcpyDeviceToHost, ctx->stream));
+  if (leaf_map_opt) HIP_TRY(ctx, hipMemcpyAsync(leaf_map_opt, A.map, d.map_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  for (int l = 0; l < lv.L; ++l) {
+    if (!d.n[l]) continue;
+    const int nl = lv.st[l]->model.n_logits;
+    const size_t s0 = (size_t)d.start[l], c = (size_t)d.n[l];
+    if (logits_opt)   // the level's n_logits floats per row; the rest of the caller's row is left alone
       HIP_TRY(ctx, hipMemcpy2DAsync(logits_opt + s0 * (size_t)logit_stride, (size_t)logit_stride * 4, A.logits + s0 * kRowLogits, (size_t)nl * 4, (size_t)nl * 4, c,
                                     hipMemcpyDeviceToHost, ctx->stream));
     if (dec_opt) HIP_TRY(ctx, hipMemcpyAsync(dec_opt + s0, A.dec + s0, c * sizeof(DecisionRec), hipMemcpyDeviceToHost, ctx->stream));
     if (cand_opt) HIP_TRY(ctx, hipMemcpyAsync(cand_opt + s0, A.cand + s0, c * sizeof(CandRec), hipMemcpyDeviceToHost, ctx->stream));
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  *n_nodes = total;
+  *n_nodes = d.total;
   return MLT_OK;
 }
 
-// The trees of several picture pairs of one geometry in one descent: per level ONE position list over all pictures (the arena is level-major: picture 0's segment,
-// picture 1's, ...), one network pass through predict_at_chunks -- picture_gather_multi_kernel looks every CU's entry up -- one guard re-run, one 4-byte count; then
-// tree_pack_kernel permutes into the picture-major order of the contract and the call ends in one D2H copy per requested array.
 int mlt_predict_trees(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture *pics, const mlt_tree_config *cfg, mlt_tree_node *nodes, int node_cap, int32_t *first_node,
                       uint8_t *leaf_maps_opt, float *logits_opt, int logit_stride, mlt_decision *dec_opt, mlt_candidates *cand_opt) {
   if (!ctx) return MLT_ERR_ARG;
@@ -214,8 +241,7 @@ int mlt_predict_trees(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture *pics
   TreeLevels lv;
   int rc;
   if ((rc = tree_levels(ctx, "mlt_predict_trees", cfg, lv))) return rc;
-  const int top = lv.top, mn = lv.mn, L = lv.L, P = n_pictures;
-  SizeState **st = lv.st;
+  const int P = n_pictures;
   for (int p = 0; p < P; ++p) {
     const mlt_picture *o = pics[p].org, *q = pics[p].pred;
     char msg[192];
@@ -232,7 +258,7 @@ int mlt_predict_trees(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture *pics
     }
   }
   const int W = pics[0].org->width, H = pics[0].org->height;
-  const int max_nodes = mlt_tree_max_nodes(W, H, top, mn);
+  const int max_nodes = mlt_tree_max_nodes(W, H, lv.top, lv.mn);
   const long long cap_all = (long long)P * max_nodes;
   if (node_cap < cap_all || cap_all > 0x7fffffff) {
     char msg[192];
@@ -241,110 +267,34 @@ int mlt_predict_trees(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture *pics
     return MLT_ERR_ARG;
   }
   // ---- arguments are good: the trees run on this context's own device (devices[0] of a multi-device context) ----
-  if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
-  const bool by_cand = (cfg->flags & MLT_TREE_BY_CANDIDATES) != 0;
-  bool want_cand[4], any_cand = false;
-  for (int l = 0; l < L; ++l) any_cand = (want_cand[l] = cand_opt || by_cand || st[l]->cand_policy()) || any_cand;
-  TreeRoots tr;
-  tree_roots_of(W, H, top, L, tr);
-  const int map_w = W / 16, map_h = H / 16, N = (int)cap_all;
-  const size_t map_bytes = (size_t)map_w * map_h;
-  const Lay::TreesArena arena((size_t)P, (size_t)max_nodes, tr.xy.size() / 2, map_bytes, sizeof(TreesEntry), any_cand, logits_opt != nullptr, dec_opt != nullptr,
-                              cand_opt != nullptr);
-  if ((rc = ctx->tree_dev.reserve(ctx, arena.bytes(), "mlt_predict_trees"))) return rc;
-  if (!ctx->tree_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->tree_host, 64, hipHostMallocDefault));
-  const Lay::TreesArena::Ptrs A = arena.at(ctx->tree_dev.p);
-  std::vector<TreesEntry> entries((size_t)P);
-  for (int p = 0; p < P; ++p) {
-    const AtPlanes pl = AtPlanes::of(pics[p].org, pics[p].pred, 0);
-    entries[(size_t)p] = TreesEntry{pl.org, pl.pred, pl.org_pitch, pl.pred_pitch, pl.org_vec ? 1 : 0, pl.pred_vec ? 1 : 0, pics[p].poc, pics[p].qp};
-  }
-  // (pageable sources: both copies have read them when they return)
-  HIP_TRY(ctx, hipMemcpyAsync(A.entries, entries.data(), entries.size() * sizeof(TreesEntry), hipMemcpyHostToDevice, ctx->stream));
-  if (!tr.xy.empty()) HIP_TRY(ctx, hipMemcpyAsync(A.roots, tr.xy.data(), tr.xy.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (leaf_maps_opt && map_bytes) HIP_TRY(ctx, hipMemsetAsync(A.map, 0xFF, (size_t)P * map_bytes, ctx->stream));
-  Launch prof{ctx};
-  auto expand = [&](const TreesExpandArgs &xa) -> int {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int r;
-    // algorithmic bytes the host knows, as for tree_expand: + the picture index per node, the segment table's rows
-    if ((r = prof.prof_begin("trees_expand", 0.0, (double)xa.t.lvl_n * (sizeof(DecisionRec) + 20) + (double)P * xa.t.n_next_roots * (sizeof(TreeNodeRec) + 12) + (double)P * 8, e0, e1)))
-      return r;
-    HIP_TRY(ctx, mlt_launch_trees_expand(xa, ctx->stream));
-    return prof.prof_end(e1);
-  };
-  TreesExpandArgs xa{};
-  TreeExpandArgs &ea = xa.t;
-  xa.pic = A.pic; xa.segs = TreesSegs{A.seg_start, A.seg_n, A.pack_base}; xa.n_pictures = P; xa.n_levels = L; xa.first_node = A.first_node;
-  ea.nodes = A.nodes; ea.xy = A.xy; ea.node_cap = N; ea.by_candidates = by_cand ? 1 : 0;
-  // the trees open: no parents, every picture's top-level roots
-  xa.lvl = -1;
-  ea.lvl_start = 0; ea.lvl_n = 0; ea.size = 2 * top; ea.depth = -1;
-  ea.next_roots = A.roots; ea.n_next_roots = tr.n[0]; ea.root_flags = 0; ea.count = nullptr;
-  if ((rc = expand(xa))) return rc;
-  int start = 0, n = P * tr.n[0];
-  TreesPackArgs pa{};
-  for (int l = 0, S = top; l < L; ++l, S >>= 1) {
-    SizeState *s = st[l];
-    const int nl = s->model.n_logits;
-    const bool last = l == L - 1;
-    pa.lvl_start[l] = start; pa.n_logits[l] = nl;
-    float *d_lg = A.logits + (size_t)start * kRowLogits;
-    DecisionRec *d_dec = A.dec + start;
-    CandRec *d_cand = want_cand[l] ? A.cand + start : nullptr;
-    if (n > 0) {
-      const AtOut out{nullptr, d_lg, (mlt_decision *)d_dec, (mlt_candidates *)d_cand};
-      const AtPlanes none{};
-      if ((rc = predict_at_chunks(ctx, s, none, n, AtList::of_entries(A.xy + 2 * (size_t)start, A.pic + start, (const TreesEntry *)A.entries, P), out))) return rc;
-    }
-    xa.lvl = l;
-    ea.lvl_start = start; ea.lvl_n = n; ea.size = S; ea.depth = l;
-    ea.dec = d_dec; ea.cand = d_cand; ea.logits = d_lg; ea.n_logits = nl;
-    ea.head_off = s->head_off(); ea.head_classes = s->head_classes();
-    ea.descend_mask = last ? 0u : lv.mask[l];
-    ea.next_roots = last ? nullptr : A.roots + 2 * (size_t)tr.off[l + 1];
-    ea.n_next_roots = last ? 0 : tr.n[l + 1];
-    ea.root_flags = 1;
-    ea.count = last ? nullptr : A.count;
-    if ((rc = expand(xa))) return rc;
-    if (n > 0 && leaf_maps_opt) {
-      TreesRasterArgs ra{};
-      ra.t.nodes = A.nodes; ra.t.lvl_start = start; ra.t.lvl_n = n; ra.t.blk_l = ilog2(S) - 4; ra.t.map = A.map; ra.t.map_w = map_w; ra.t.map_h = map_h;
-      ra.pic = A.pic; ra.map_bytes = map_bytes;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if ((rc = prof.prof_begin("trees_raster", 0.0, (double)n * (sizeof(TreeNodeRec) + 4 + (double)(1 << (2 * ra.t.blk_l))), e0, e1))) return rc;
-      HIP_TRY(ctx, mlt_launch_trees_raster(ra, ctx->stream));
-      if ((rc = prof.prof_end(e1))) return rc;
-    }
-    start += n;
-    if (last) break;
-    // the one host synchronisation of the level beside the guards': how many nodes the next level has, over all pictures
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->tree_host, A.count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    n = ctx->tree_host[0];
-    const int nr = P * tr.n[l + 1];
-    if (n < nr || ((n - nr) & 3) || (long long)start + n > N) { ctx->err = "mlt_predict_trees: bad node count from the device"; return MLT_ERR_HIP; }
-  }
+  Descent d;
+  if ((rc = descend(ctx, "mlt_predict_trees", lv, W, H, P, pics, (cfg->flags & MLT_TREE_BY_CANDIDATES) != 0, true,
+                    TreeWant{leaf_maps_opt != nullptr, logits_opt != nullptr, dec_opt != nullptr, cand_opt != nullptr}, d)))
+    return rc;
   // ---- level-major -> picture-major, then everything the caller asked for and one synchronisation ----
-  const int total = start;
-  pa.nodes = A.nodes; pa.pic = A.pic; pa.logits = A.logits; pa.dec = A.dec; pa.cand = A.cand;
-  pa.o_nodes = A.o_nodes; pa.o_logits = A.o_logits; pa.o_dec = A.o_dec; pa.o_cand = A.o_cand;
-  pa.segs = xa.segs; pa.first_node = A.first_node; pa.n_pictures = P; pa.n_levels = L; pa.total = total;
+  const Lay::TreeArena::Ptrs &A = d.A;
+  const int total = d.total;
   if (total) {
+    TreesPackArgs pa{};
+    pa.nodes = A.nodes; pa.pic = A.pic; pa.logits = A.logits; pa.dec = A.dec; pa.cand = A.cand;
+    pa.o_nodes = A.o_nodes; pa.o_logits = A.o_logits; pa.o_dec = A.o_dec; pa.o_cand = A.o_cand;
+    pa.segs = TreesSegs{A.seg_start, A.seg_n, A.pack_base}; pa.first_node = A.first_node; pa.n_pictures = P; pa.n_levels = lv.L; pa.total = total;
+    for (int l = 0; l < lv.L; ++l) { pa.lvl_start[l] = d.start[l]; pa.n_logits[l] = lv.st[l]->model.n_logits; }
+    Launch prof{ctx};
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const double per_node = 2.0 * sizeof(TreeNodeRec) + 4 + (logits_opt ? 2.0 * kRowLogits * 4 : 0) + (dec_opt ? 2.0 * sizeof(DecisionRec) : 0) + (cand_opt ? 2.0 * sizeof(CandRec) : 0);
     if ((rc = prof.prof_begin("tree_pack", 0.0, (double)total * per_node, e0, e1))) return rc;
     HIP_TRY(ctx, mlt_launch_trees_pack(pa, ctx->stream));
     if ((rc = prof.prof_end(e1))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(nodes, A.o_nodes, (size_t)total * sizeof(TreeNodeRec), hipMemcpyDeviceToHost, ctx->stream));
-    if (logits_opt) {
+    if (logits_opt) {   // whole zero-padded rows
       if (logit_stride == kRowLogits) HIP_TRY(ctx, hipMemcpyAsync(logits_opt, A.o_logits, (size_t)total * kRowLogits * 4, hipMemcpyDeviceToHost, ctx->stream));
       else HIP_TRY(ctx, hipMemcpy2DAsync(logits_opt, (size_t)logit_stride * 4, A.o_logits, (size_t)kRowLogits * 4, (size_t)kRowLogits * 4, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
     }
     if (dec_opt) HIP_TRY(ctx, hipMemcpyAsync(dec_opt, A.o_dec, (size_t)total * sizeof(DecisionRec), hipMemcpyDeviceToHost, ctx->stream));
     if (cand_opt) HIP_TRY(ctx, hipMemcpyAsync(cand_opt, A.o_cand, (size_t)total * sizeof(CandRec), hipMemcpyDeviceToHost, ctx->stream));
   }
-  if (leaf_maps_opt && map_bytes) HIP_TRY(ctx, hipMemcpyAsync(leaf_maps_opt, A.map, (size_t)P * map_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (leaf_maps_opt) HIP_TRY(ctx, hipMemcpyAsync(leaf_maps_opt, A.map, (size_t)P * d.map_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(first_node, A.first_node, ((size_t)P + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (first_node[P] != total) { ctx->err = "mlt_predict_trees: bad node count from the device"; return MLT_ERR_HIP; }

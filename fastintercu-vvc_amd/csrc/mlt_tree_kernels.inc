@@ -1,34 +1,50 @@
-// mlt_tree_kernels.inc -- partition trees of a picture (include/mltcnn.h: mlt_predict_tree): the quadtree descent between two network levels, on the device.
-// Included by mlt_kernels.hip.
+// mlt_tree_kernels.inc -- partition trees of pictures (include/mltcnn.h: mlt_predict_tree, mlt_predict_trees): the quadtree descent between two network levels, on
+// the device.  Included by mlt_kernels.hip.
 //
-// tree_expand_kernel   one level's evaluated nodes -> their split_mode / confidence / cand_mask / first_child, the next level's nodes (its border roots, then
-//                      four children per descending parent, in the parents' order) with their positions, and the next level's node count.
-// tree_raster_kernel   one level's leaves -> the per-16x16-block leaf map.
+// tree_expand_kernel   one level's evaluated nodes -> their split_mode / confidence / cand_mask / first_child, the next level's nodes (per picture its border roots,
+//                      then four children per descending parent, in the parents' order) with their positions and picture indices, the next level's node count
+//                      and its row of the segment table.
+// tree_raster_kernel   one level's leaves -> the per-16x16-block leaf map of every node's picture.
+// tree_pack_kernel     after the last level of mlt_predict_trees: level-major arena -> picture-major output, parent / first_child rewritten to indices inside the
+//                      picture's slice.
 //
-// The node order is part of the ABI, so the compaction is an ORDERED one: a tiled exclusive prefix scan of the "descends" predicate -- wave ballot + popcount for
-// the 64 nodes of a wave, the 16 wave totals of a 1024-node tile through LDS, a running base carried from tile to tile -- not an atomic append.  One workgroup
-// walks the tiles: a level holds at most (16384 / 16)^2 ~ 1 M nodes = 1024 tiles of two barriers and one 32-byte node record each, and the launch sits between
-// two network passes of milliseconds.  Everything is written with ordinary stores; no atomics are needed (every output word has exactly one writer).
+// The arena is LEVEL-major over the n_pictures pictures of the call (mlt_predict_tree: one): a level is one node range -- picture 0's segment, picture 1's, ... --
+// and one list for the network pass.  The node order is part of the ABI, so the compaction is an ORDERED one: a tiled exclusive prefix scan of the "descends"
+// predicate over the WHOLE level -- wave ballot + popcount for the 64 nodes of a wave, the 16 wave totals of a 1024-node tile through LDS, a running base carried
+// from tile to tile -- not an atomic append.  One workgroup walks the tiles: a level holds at most (16384 / 16)^2 ~ 1 M nodes per picture = 1024 tiles of two
+// barriers and one 32-byte node record each, and the launch sits between two network passes of milliseconds.
+//
+// The next level, with nr = n_next_roots roots per picture (all pictures share the geometry), R_i the exclusive rank of descending parent i over the whole level,
+// p_i its picture and D_p the rank at the start of picture p's segment (the descending parents of the pictures before p):
+//   picture p's segment   starts at next_start + p nr + 4 D_p and holds nr + 4 (D_{p+1} - D_p) nodes: its roots, then its children
+//   parent i's children   start at next_start + (p_i + 1) nr + 4 R_i   (= its segment's start + nr + 4 (R_i - D_{p_i}))
+// D_p is known once the scan has passed the segment's first node, so the scan comes first and the roots after it.  The first node of a non-empty segment publishes
+// its rank as D_p; an EMPTY segment (no roots at that level and nothing descended into it) has no node to do so and takes the rank of the first non-empty segment
+// behind it, or the level's total.  With one picture D_0 = 0: the roots sit at next_start, the children behind them.  Everything is written with ordinary vector
+// stores; no atomics are needed (the order is the scan's and every output word has exactly one writer).
 
 #define MLT_TREE_TILE 1024
+#define MLT_TREES_MAX_PICTURES_K 256   // include/mltcnn.h: MLT_TREES_MAX_PICTURES (the per-picture ranks live in LDS)
 
-__device__ __forceinline__ void tree_write_node(const TreeExpandArgs &a, int idx, int x, int y, int size, int depth, int flags, int parent) {
-  if (idx < 0 || idx >= a.node_cap) return;   // (the host sizes the arena for a tree that descends everywhere: never taken)
+__device__ __forceinline__ void tree_write_node(const TreeExpandArgs &a, int idx, int pic, int x, int y, int size, int depth, int flags, int parent) {
+  if (idx < 0 || idx >= a.node_cap) return;   // (the host sizes the arena for trees that descend everywhere: never taken)
   TreeNodeRec r;
   r.x = x; r.y = y; r.size = (int16_t)size; r.depth = (int8_t)depth; r.flags = (uint8_t)flags;
   r.parent = parent; r.first_child = -1; r.split_mode = -1; r.confidence = 0.f; r.cand_mask = 0u;
   a.nodes[idx] = r;
   a.xy[2 * (size_t)idx] = x;
   a.xy[2 * (size_t)idx + 1] = y;
+  a.pic[idx] = pic;
 }
 
 __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_kernel(const TreeExpandArgs a) {
   __shared__ int wave_total[MLT_TREE_TILE / 64];
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int next_start = a.lvl_start + a.lvl_n, child_size = a.size >> 1, child_start = next_start + a.n_next_roots;
-  // the next level opens with its border roots (host-known, raster order)
-  for (int i = tid; i < a.n_next_roots; i += MLT_TREE_TILE)
-    tree_write_node(a, next_start + i, a.next_roots[2 * i], a.next_roots[2 * i + 1], child_size, a.depth + 1, a.root_flags, -1);
+  __shared__ int seg_rank[MLT_TREES_MAX_PICTURES_K];       // D_p as published by the first node of a non-empty segment
+  __shared__ int seg_first[MLT_TREES_MAX_PICTURES_K + 1];  // D_p of every picture; [n_pictures] = the level's total
+  __shared__ int pic_total[MLT_TREES_MAX_PICTURES_K];      // last launch: nodes of picture p over all levels
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, P = a.n_pictures, nr = a.n_next_roots;
+  const int next_start = a.lvl_start + a.lvl_n, child_size = a.size >> 1;
+  const int32_t *cur_start = a.segs.start + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P, *cur_n = a.segs.n + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P;
   int base = 0;   // descending parents of the tiles before this one (the same value in every thread)
   for (int t0 = 0; t0 < a.lvl_n; t0 += MLT_TREE_TILE) {
     const int i = t0 + tid;
@@ -38,7 +54,9 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_kernel(const TreeEx
     int32_t split = -1;
     float conf = 0.f;
     uint32_t cmask = 0u;
+    int p = 0;
     if (in) {
+      p = a.pic[node];
       const DecisionRec &d = a.dec[i];
       split = d.split_mode;
       conf = d.confidence;
@@ -64,115 +82,18 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_kernel(const TreeEx
     }
     __syncthreads();   // (the next tile overwrites wave_total)
     if (in) {
-      int first_child = -1;
-      if (desc) {
-        const int fc = child_start + 4 * (base + woff + before);
-        if (fc + 3 < a.node_cap) {
-          first_child = fc;
-          const int x = a.xy[2 * (size_t)node], y = a.xy[2 * (size_t)node + 1];
-          for (int j = 0; j < 4; ++j) tree_write_node(a, fc + j, x + (j & 1) * child_size, y + (j >> 1) * child_size, child_size, a.depth + 1, 0, node);
-        }
-      }
-      TreeNodeRec &r = a.nodes[node];
-      r.first_child = first_child; r.split_mode = split; r.confidence = conf; r.cand_mask = cmask;
-    }
-    base += total;
-  }
-  if (tid == 0 && a.count) a.count[0] = a.n_next_roots + 4 * base;
-}
-
-// One work item per 16 x 16 block of every node of the level; the items of a node that has children leave.  Leaves are disjoint, so plain byte stores suffice (the
-// map was filled with 0xFF before the first level).
-__global__ __launch_bounds__(256) void tree_raster_kernel(const TreeRasterArgs a) {
-  const size_t total = (size_t)a.lvl_n << (2 * a.blk_l), step = (size_t)gridDim.x * 256;
-  for (size_t it = (size_t)blockIdx.x * 256 + threadIdx.x; it < total; it += step) {
-    const int i = (int)(it >> (2 * a.blk_l)), b = (int)(it & ((1u << (2 * a.blk_l)) - 1u));
-    const TreeNodeRec &r = a.nodes[a.lvl_start + i];
-    if (r.first_child >= 0) continue;
-    const int mx = (r.x >> 4) + (b & ((1 << a.blk_l) - 1)), my = (r.y >> 4) + (b >> a.blk_l);
-    if (mx < 0 || my < 0 || mx >= a.map_w || my >= a.map_h) continue;   // (a node is a complete CU of the picture: never taken)
-    a.map[(size_t)my * a.map_w + mx] = (uint8_t)(a.blk_l | ((r.split_mode + 1) << 4));
-  }
-}
-
-// ---- trees of several pictures in one call (include/mltcnn.h: mlt_predict_trees) ----
-// trees_expand_kernel   tree_expand_kernel over a level that holds the segments of n_pictures pictures: the same tiled scan over the WHOLE level, segmented output.
-// trees_raster_kernel   tree_raster_kernel with the map chosen by the node's picture.
-// tree_pack_kernel      after the last level: level-major arena -> picture-major output, parent / first_child rewritten to indices inside the picture's slice.
-//
-// The next level, with nr = n_next_roots roots per picture (all pictures share the geometry), R_i the exclusive rank of descending parent i over the whole level,
-// p_i its picture and D_p the rank at the start of picture p's segment (the descending parents of the pictures before p):
-//   picture p's segment   starts at next_start + p nr + 4 D_p and holds nr + 4 (D_{p+1} - D_p) nodes: its roots, then its children
-//   parent i's children   start at next_start + (p_i + 1) nr + 4 R_i   (= its segment's start + nr + 4 (R_i - D_{p_i}))
-// D_p is known once the scan has passed the segment's first node, so the scan comes first and the roots after it.  The first node of a non-empty segment publishes
-// its rank as D_p; an EMPTY segment (no roots at that level and nothing descended into it) has no node to do so and takes the rank of the first non-empty segment
-// behind it, or the level's total.  Still no atomics: the order is the scan's, every output word has one writer, all stores are ordinary vector stores.
-
-#define MLT_TREES_MAX_PICTURES_K 256   // include/mltcnn.h: MLT_TREES_MAX_PICTURES (the per-picture ranks live in LDS)
-
-__device__ __forceinline__ void trees_write_node(const TreesExpandArgs &a, int idx, int pic, int x, int y, int size, int depth, int flags, int parent) {
-  if (idx < 0 || idx >= a.t.node_cap) return;   // (never taken, as in tree_write_node)
-  tree_write_node(a.t, idx, x, y, size, depth, flags, parent);
-  a.pic[idx] = pic;
-}
-
-__global__ __launch_bounds__(MLT_TREE_TILE) void trees_expand_kernel(const TreesExpandArgs a) {
-  __shared__ int wave_total[MLT_TREE_TILE / 64];
-  __shared__ int seg_rank[MLT_TREES_MAX_PICTURES_K];       // D_p as published by the first node of a non-empty segment
-  __shared__ int seg_first[MLT_TREES_MAX_PICTURES_K + 1];  // D_p of every picture; [n_pictures] = the level's total
-  __shared__ int pic_total[MLT_TREES_MAX_PICTURES_K];      // last launch: nodes of picture p over all levels
-  const TreeExpandArgs &t = a.t;
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, P = a.n_pictures, nr = t.n_next_roots;
-  const int next_start = t.lvl_start + t.lvl_n, child_size = t.size >> 1;
-  const int32_t *cur_start = a.segs.start + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P, *cur_n = a.segs.n + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P;
-  int base = 0;
-  for (int t0 = 0; t0 < t.lvl_n; t0 += MLT_TREE_TILE) {
-    const int i = t0 + tid;
-    const bool in = i < t.lvl_n;
-    const int node = t.lvl_start + (in ? i : 0);
-    bool desc = false;
-    int32_t split = -1;
-    float conf = 0.f;
-    uint32_t cmask = 0u;
-    int p = 0;
-    if (in) {
-      p = a.pic[node];
-      const DecisionRec &d = t.dec[i];
-      split = d.split_mode;
-      conf = d.confidence;
-      if (t.cand) cmask = t.cand[i].mask;
-      else {
-        const float *l = t.logits + (size_t)i * t.n_logits + t.head_off;
-        bool nan = false;
-        for (int k = 0; k < t.head_classes; ++k) nan = nan || (l[k] != l[k]);
-        cmask = nan ? (1u << t.head_classes) - 1u : 1u << d.raw_mode;
-      }
-      desc = t.by_candidates ? (cmask & t.descend_mask) != 0u : (split >= 0 && ((t.descend_mask >> split) & 1u) != 0u);
-    }
-    const unsigned long long b = __ballot(desc);
-    const int before = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_total[wave] = __popcll(b);
-    __syncthreads();
-    int woff = 0, total = 0;
-    for (int w = 0; w < MLT_TREE_TILE / 64; ++w) {
-      const int s = wave_total[w];
-      woff += w < wave ? s : 0;
-      total += s;
-    }
-    __syncthreads();   // (the next tile overwrites wave_total)
-    if (in) {
       const int rank = base + woff + before;
       if ((unsigned)p < (unsigned)P && node == cur_start[p]) seg_rank[p] = rank;   // the segment's first node: one writer per picture
       int first_child = -1;
       if (desc) {
         const int fc = next_start + (p + 1) * nr + 4 * rank;
-        if (fc + 3 < t.node_cap) {
+        if (fc + 3 < a.node_cap) {
           first_child = fc;
-          const int x = t.xy[2 * (size_t)node], y = t.xy[2 * (size_t)node + 1];
-          for (int j = 0; j < 4; ++j) trees_write_node(a, fc + j, p, x + (j & 1) * child_size, y + (j >> 1) * child_size, child_size, t.depth + 1, 0, node);
+          const int x = a.xy[2 * (size_t)node], y = a.xy[2 * (size_t)node + 1];
+          for (int j = 0; j < 4; ++j) tree_write_node(a, fc + j, p, x + (j & 1) * child_size, y + (j >> 1) * child_size, child_size, a.lvl + 1, 0, node);
         }
       }
-      TreeNodeRec &r = t.nodes[node];
+      TreeNodeRec &r = a.nodes[node];
       r.first_child = first_child; r.split_mode = split; r.confidence = conf; r.cand_mask = cmask;
     }
     base += total;
@@ -195,9 +116,9 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void trees_expand_kernel(const Trees
     // every picture's next segment opens with the border roots (host-known, raster order, the same for all pictures)
     for (int i = tid; i < P * nr; i += MLT_TREE_TILE) {
       const int p = i / nr, r = i - p * nr;
-      trees_write_node(a, next_start + p * nr + 4 * seg_first[p] + r, p, t.next_roots[2 * r], t.next_roots[2 * r + 1], child_size, t.depth + 1, t.root_flags, -1);
+      tree_write_node(a, next_start + p * nr + 4 * seg_first[p] + r, p, a.next_roots[2 * r], a.next_roots[2 * r + 1], child_size, a.lvl + 1, a.root_flags, -1);
     }
-    if (tid == 0 && t.count) t.count[0] = P * nr + 4 * base;
+    if (tid == 0 && a.count) a.count[0] = P * nr + 4 * base;
     return;
   }
   // the last level: where every (level, picture) segment starts in the picture-major output, and first_node[]
@@ -219,16 +140,17 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void trees_expand_kernel(const Trees
   }
 }
 
-__global__ __launch_bounds__(256) void trees_raster_kernel(const TreesRasterArgs a) {
-  const TreeRasterArgs &t = a.t;
-  const size_t total = (size_t)t.lvl_n << (2 * t.blk_l), step = (size_t)gridDim.x * 256;
+// One work item per 16 x 16 block of every node of the level; the items of a node that has children leave.  Leaves are disjoint, so plain byte stores suffice (the
+// maps were filled with 0xFF before the first level).
+__global__ __launch_bounds__(256) void tree_raster_kernel(const TreeRasterArgs a) {
+  const size_t total = (size_t)a.lvl_n << (2 * a.blk_l), step = (size_t)gridDim.x * 256;
   for (size_t it = (size_t)blockIdx.x * 256 + threadIdx.x; it < total; it += step) {
-    const int i = (int)(it >> (2 * t.blk_l)), b = (int)(it & ((1u << (2 * t.blk_l)) - 1u));
-    const TreeNodeRec &r = t.nodes[t.lvl_start + i];
+    const int i = (int)(it >> (2 * a.blk_l)), b = (int)(it & ((1u << (2 * a.blk_l)) - 1u));
+    const TreeNodeRec &r = a.nodes[a.lvl_start + i];
     if (r.first_child >= 0) continue;
-    const int mx = (r.x >> 4) + (b & ((1 << t.blk_l) - 1)), my = (r.y >> 4) + (b >> t.blk_l);
-    if (mx < 0 || my < 0 || mx >= t.map_w || my >= t.map_h) continue;   // (never taken)
-    t.map[(size_t)a.pic[t.lvl_start + i] * a.map_bytes + (size_t)my * t.map_w + mx] = (uint8_t)(t.blk_l | ((r.split_mode + 1) << 4));
+    const int mx = (r.x >> 4) + (b & ((1 << a.blk_l) - 1)), my = (r.y >> 4) + (b >> a.blk_l);
+    if (mx < 0 || my < 0 || mx >= a.map_w || my >= a.map_h) continue;   // (a node is a complete CU of the picture: never taken)
+    a.map[(size_t)a.pic[a.lvl_start + i] * a.map_bytes + (size_t)my * a.map_w + mx] = (uint8_t)(a.blk_l | ((r.split_mode + 1) << 4));
   }
 }
 

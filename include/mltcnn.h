@@ -430,7 +430,8 @@ int mlt_predict_tree(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pr
 /* ---- Partition trees of SEVERAL picture pairs in one call (new exports; MLT_ABI_VERSION stays 4) ----
  * What a caller with a GOP, or with one original and several candidate predictions, in device memory wants: per level ONE network pass over the nodes of all
  * pictures, one guard re-run and one 4-byte count, instead of those per picture.  On the device a level of all pictures is one position list (picture 0's nodes,
- * then picture 1's, ...), gathered from the entries' planes by one launch; after the last level tree_pack_kernel permutes into the order below.
+ * then picture 1's, ...), gathered from the entries' planes by one launch; after the last level tree_pack_kernel permutes into the order below.  The descent, its
+ * kernels (tree_expand, tree_raster) and its device arena are mlt_predict_tree's: that call is the same descent over one picture.
  *
  * ENTRIES   pics[0 .. n_pictures): an (org, pred) pair of ctx and the pair's poc / qp.  ALL pictures of a call have ONE width x height.  The same picture may
  *           appear in several entries (one original against several predictions) and entries may repeat.  cfg->poc / cfg->qp are NOT read.

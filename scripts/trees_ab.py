@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""What the partition trees of P frames cost in one call against P calls (kernel table: `trees_expand_kernel`, `tree_pack_kernel`).
+"""What the partition trees of P frames cost in one call against P calls (kernel table: `tree_expand_kernel`, `tree_pack_kernel`).
 
 One process, one context (seeded weights, head 0 at every size), P frames of natural patches (synth.natural_patches tiled and cropped, frame f from picture seed
 --picture-seed + f, poc = f, qp = 0) resident as picture pairs:
   leg A  ONE mlt_predict_trees call over the P frames: per level one network pass over the nodes of all frames
-  leg B  P mlt_predict_tree calls, one per frame -- code the batched call does not touch, hence the baseline
+  leg B  P mlt_predict_tree calls, one per frame: the same descent over one picture at a time, the baseline
 Both legs ask for the nodes and the leaf maps.  Legs alternate pair by pair after the warm-up; medians with min / max and the spread of B; the trees of the two
 legs are compared byte for byte.  From separate profiled runs of each leg (HIP events around every launch, mlt_profile_read): launches per call, and the time inside
 the expand, raster, gather and pack launches and inside all launches.  Run it for the full descent and for the single-pass tier at the 128 level alone:
@@ -22,16 +22,10 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-SIZES = (128, 64, 32, 16)
-NEW = ("trees_expand", "trees_raster", "picture_gather_multi", "tree_pack")
-OLD = ("tree_expand", "tree_raster", "picture_gather")
+from tree_ab import SIZES, frame  # noqa: E402  (scripts/tree_ab.py: the frame tiler)
 
-
-def frame(pkg, width, height, seed):
-    cols, rows = (width + 127) // 128, (height + 127) // 128
-    org, pred = pkg.synth.natural_patches(128, cols * rows, seed)
-    tile = lambda p: np.ascontiguousarray(p.reshape(rows, cols, 128, 128).transpose(0, 2, 1, 3).reshape(rows * 128, cols * 128)[:height, :width])
-    return tile(org), tile(pred)
+OWN_A = ("tree_expand", "tree_raster", "picture_gather_multi", "tree_pack")   # the launches of a call beside the network's: batched | single
+OWN_B = ("tree_expand", "tree_raster", "picture_gather")
 
 
 def profiled(m, leg, steps):
@@ -117,14 +111,14 @@ def main():
     print(f"  leg B  {P} mlt_predict_tree calls            median {med['B']:.3f} ms  (min {rng['B'][0]:.3f}, max {rng['B'][1]:.3f})   {launches_b:.0f} launches; "
           f"spread max - min {spread_b['min_max']:.3f} ms, interquartile {spread_b['interquartile']:.3f} ms")
     print(f"  A / B = {med['A'] / med['B']:.3f}   (A - B = {med['A'] - med['B']:+.3f} ms)")
-    for k in NEW:
+    for k in OWN_A:
         if k in prof_a:
             print(f"  leg A  {k}: {prof_a[k]['launches_per_call']:.0f} launches per call, {prof_a[k]['us_per_call']:.1f} us per call in all")
-    for k in OLD:
+    for k in OWN_B:
         if k in prof_b:
             print(f"  leg B  {k}: {prof_b[k]['launches_per_call']:.0f} launches per {P} calls, {prof_b[k]['us_per_call']:.1f} us in all")
     net = lambda prof, own: sorted(((k, v) for k, v in prof.items() if k not in own), key=lambda kv: -kv[1]["us_per_call"])
-    for name, prof, own in (("A", prof_a, NEW), ("B", prof_b, OLD)):
+    for name, prof, own in (("A", prof_a, OWN_A), ("B", prof_b, OWN_B)):
         print(f"  leg {name}  network launches (profiled run): " + "; ".join(f"{k} x{v['launches_per_call']:.0f} {v['us_per_call']:.0f} us" for k, v in net(prof, own)))
     print(f"  all launches, profiled runs (events around every launch): A {ms_a:.3f} ms, B {ms_b:.3f} ms")
     print(json.dumps({"source_sig": pkg.build.source_signature(), "result": row}))

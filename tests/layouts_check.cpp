@@ -176,13 +176,20 @@ int main() {
     for (int cnd = 0; cnd < 2; ++cnd) {
       std::snprintf(tag, sizeof tag, "TreeArena nodes=%zu roots=%zu map=%zu cand=%d", t[0], t[1], t[2], cnd);
       g_what = tag;
-      const Lay::TreeArena A(t[0], t[1], t[2], cnd != 0);
+      // the single call's shape: one picture, not packed (whatever outputs the caller wants: they come straight from the level-major parts)
+      const Lay::TreeArena A(1, t[0], t[1], t[2], 48, cnd != 0, false, cnd != 0, true, cnd == 0);
       Buffer buf(A.bytes());
       const Lay::TreeArena::Ptrs P = buf.p ? A.at(buf.p) : Lay::TreeArena::Ptrs{};
       if (A.cand.on != (cnd != 0)) fail("candidate records not as asked");
+      const std::vector<Part> absent = {{"entries", A.entries, 0, 256, P.entries}, {"o_nodes", A.o_nodes, 0, 256, P.o_nodes}, {"o_logits", A.o_logits, 0, 256, P.o_logits},
+                                        {"o_dec", A.o_dec, 0, 256, P.o_dec}, {"o_cand", A.o_cand, 0, 256, P.o_cand}};
+      for (const Part &p : absent)
+        if (p.f.on || p.f.bytes || p.ptr) fail(std::string(p.name) + ": present in the single call's arena");
       check_parts({{"nodes", A.nodes, t[0] * NODE, 256, P.nodes}, {"xy", A.xy, t[0] * 8, 256, P.xy}, {"logits", A.logits, t[0] * MLT_MAX_LOGITS * 4, 256, P.logits},
                    {"dec", A.dec, t[0] * DEC, 256, P.dec}, {"cand", A.cand, t[0] * CAND, 256, P.cand}, {"roots", A.roots, t[1] * 8, 256, P.roots}, {"map", A.map, t[2], 256, P.map},
-                   {"count", A.count, 4, 256, P.count}}, A.bytes(), buf.p);
+                   {"count", A.count, 4, 256, P.count}, {"pic", A.pic, t[0] * 4, 256, P.pic}, {"seg_start", A.seg_start, 4 * 4, 256, P.seg_start},
+                   {"seg_n", A.seg_n, 4 * 4, 256, P.seg_n}, {"pack_base", A.pack_base, 4 * 4, 256, P.pack_base}, {"first_node", A.first_node, 2 * 4, 256, P.first_node},
+                   absent[0], absent[1], absent[2], absent[3], absent[4]}, A.bytes(), buf.p);
     }
   std::printf("OK %ld layouts\n", g_checked);
   return 0;

@@ -17,12 +17,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tree_host import SIZES, host_tree, reruns as _reruns, same as _same   # the host descent (build_tree over predict_at)
+
 pytestmark = pytest.mark.gpu
 LOGIT_TOL, UNDECIDABLE, CONF_TOL = 1e-3, 4e-5, 5e-4
-SIZES = (128, 64, 32, 16)
 W, H = 424, 280
 MLT_ERR_ARG, MLT_ERR_SIZE_DISABLED = 1, 4
-ALL = ("split", "logits", "decisions", "candidates")
 TREE_ALL = ("leaf_map", "logits", "decisions", "candidates")
 #        pic seed, weight seed
 CASES = {"A": (8, 13), "B": (7, 12), "C": (7, 13)}
@@ -66,35 +66,6 @@ def natural_picture(pkg, pic_seed):
 
 def cut(pic, xy, S):
     return np.stack([pic[y:y + S, x:x + S] for x, y in xy])
-
-
-def _same(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def _reruns(m, sizes=SIZES):
-    return sum(m.arithmetic(s)["guard_reruns"] for s in sizes)
-
-
-def host_tree(pkg, m, p_org, p_pred, width, height, top=128, min_size=16, descend=None, by_candidates=False):
-    """The descent driven from the host: build_tree over m.predict_at -> (nodes, leaf_map, per-node logits [n, 15] / decisions / candidates, guard re-runs)."""
-    rec = {"logits": [], "decisions": [], "candidates": []}
-
-    def decide(size, xy):
-        z = np.zeros(len(xy), np.int32)
-        r = m.predict_at(size, p_org, p_pred, xy, z, z, want=ALL)
-        assert np.array_equal(r["split"], r["decisions"]["split_mode"])
-        row = np.zeros((len(xy), 15), np.float32)
-        row[:, :r["logits"].shape[1]] = r["logits"]
-        rec["logits"].append(row)
-        rec["decisions"].append(r["decisions"])
-        rec["candidates"].append(r["candidates"])
-        return r["decisions"]["split_mode"], r["decisions"]["confidence"], r["candidates"]["mask"]
-
-    sizes = [s for s in SIZES if min_size <= s <= top]
-    r0 = _reruns(m, sizes)
-    nodes, leaf_map = pkg.decisions.build_tree(width, height, top, min_size, descend, decide, by_candidates)
-    return nodes, leaf_map, {k: np.concatenate(v) for k, v in rec.items()}, _reruns(m, sizes) - r0
 
 
 def device_tree(m, p_org, p_pred, want=TREE_ALL, sizes=SIZES, **kw):

@@ -10,6 +10,8 @@ import itertools
 import numpy as np
 import pytest
 
+from tree_host import host_tree   # the descent driven from the host (build_tree over predict_at)
+
 pytestmark = pytest.mark.gpu
 SIZES = (128, 64, 32, 16)
 W, H = 424, 280
@@ -182,7 +184,7 @@ def test_the_streaming_threshold_on_the_single_pass_tier(gpu, contexts, naturals
         print("batched:", batched, "\nsingle:", single)
         assert any(k.startswith("layer0_stream") for k in batched), batched
         assert not any(k.startswith("layer0_stream") for k in single), single
-        assert batched.get("picture_gather_multi") == 1 and batched.get("trees_expand") == 2 and batched.get("tree_pack") == 1 and batched.get("trees_raster") == 1, batched
+        assert batched.get("picture_gather_multi") == 1 and batched.get("tree_expand") == 2 and batched.get("tree_pack") == 1 and batched.get("tree_raster") == 1, batched
         assert "picture_gather_multi" not in single and "tree_pack" not in single and single.get("tree_expand") == 6 and single.get("picture_gather") == 3, single
     finally:
         m.profile_enable(False)
@@ -227,6 +229,17 @@ def test_tile_and_chunk_boundaries_inside_segments(gpu, contexts):
         desc = [int((g["nodes"]["first_child"] >= 0).sum()) for g in got]
         print("device: descending 32 nodes per picture", desc)
         assert 0 in desc and max(desc) >= 1
+        # the batched and the single call share the descent and its kernels, so (b) is also held against the descent driven from the HOST through predict_at:
+        # picture 0, picture 28 (the end of the 4096-CU pass) and picture 34 (the end of the scan's 1024-node tile), byte for byte
+        for p in (0, 28, 34):
+            nodes, leaf_map, rec, host_reruns = host_tree(pkg, m, pairs[p][0], pairs[p][1], w, h, top=32, min_size=16, poc=int(poc[p]), qp=int(qp[p]))
+            assert _same(got[p]["nodes"], nodes) and _same(got[p]["leaf_map"], leaf_map), p
+            for k in ("logits", "decisions", "candidates"):
+                assert _same(got[p][k], rec[k]), (p, k)
+            # guard re-runs: the batched call's are the sum of the single calls' (check_batched_is_singles); a single call's are the host descent's
+            r0 = _reruns(m, (32, 16))
+            m.predict_tree(pairs[p][0], pairs[p][1], int(poc[p]), int(qp[p]), top=32, min_size=16, want=("leaf_map",))
+            assert _reruns(m, (32, 16)) - r0 == host_reruns, (p, host_reruns)
     finally:
         close_all(pairs)
 

@@ -1,4 +1,4 @@
-// Stand-alone check of mlt_predict_trees' device arena (fastintercu-vvc_amd/csrc/mlt_layout.h: Lay::TreesArena), built and run by tests/test_trees_cpu.py with
+// Stand-alone check of the tree arena in mlt_predict_trees' packed shape (fastintercu-vvc_amd/csrc/mlt_layout.h: Lay::TreeArena), built and run by tests/test_trees_cpu.py with
 // g++ -fsanitize=address,undefined, in the manner of tests/layouts_check.cpp.  For 1, 2 and 256 pictures, with and without candidate records in the arena and with
 // every combination of requested outputs: every part lies inside bytes(), parts are pairwise disjoint, every part starts on 256 bytes, has the size written HERE,
 // at(base) is base + offset, the first and last byte of every part can be written, and an absent part has no bytes and a NULL pointer.
@@ -22,7 +22,7 @@ struct Part { const char *name; Field f; size_t want_bytes; bool want_on; const 
 
 int main() {
   const size_t NODE = sizeof(mlt_tree_node), DEC = sizeof(mlt_decision), CAND = sizeof(mlt_candidates), ENTRY = 48;
-  if (NODE != 32 || DEC != 48 || CAND != 40 || sizeof(mlt_tree_picture) != 24 || Lay::TreesArena::kRow != 15 || Lay::TreesArena::kLevels != 4) fail("record sizes");
+  if (NODE != 32 || DEC != 48 || CAND != 40 || sizeof(mlt_tree_picture) != 24 || Lay::TreeArena::kRow != 15 || Lay::TreeArena::kLevels != 4) fail("record sizes");
   // nodes per picture / roots / map bytes: 424 x 280 (576, 40, 442), a 16 x 16 picture (1, 1, 1), 208 x 176 at 32..16 (173, 53, 143)
   const size_t geo[][3] = {{576, 40, 442}, {1, 1, 1}, {173, 53, 143}};
   const size_t pics[] = {1, 2, 256};
@@ -34,12 +34,12 @@ int main() {
         char tag[128];
         std::snprintf(tag, sizeof tag, "pictures %zu nodes %zu cands %d out %d%d%d", P, g[0], cands, o_lg, o_dec, o_cand);
         g_what = tag;
-        const Lay::TreesArena a(P, g[0], g[1], g[2], ENTRY, cands, o_lg, o_dec, o_cand);
+        const Lay::TreeArena a(P, g[0], g[1], g[2], ENTRY, cands, true, o_lg, o_dec, o_cand);
         const size_t N = P * g[0], bytes = a.bytes();
         if (bytes % 256) fail("size is no multiple of 256");
         char *base = (char *)std::aligned_alloc(256, bytes);
         if (!base) fail("allocation");
-        const Lay::TreesArena::Ptrs p = a.at(base);
+        const Lay::TreeArena::Ptrs p = a.at(base);
         const std::vector<Part> parts = {
             {"nodes", a.nodes, N * NODE, true, p.nodes}, {"xy", a.xy, N * 8, true, p.xy}, {"logits", a.logits, N * 15 * 4, true, p.logits}, {"dec", a.dec, N * DEC, true, p.dec},
             {"cand", a.cand, N * CAND, cands, p.cand}, {"roots", a.roots, g[1] * 8, true, p.roots}, {"map", a.map, P * g[2], true, p.map}, {"count", a.count, 4, true, p.count},

@@ -19,6 +19,7 @@ children, down to S (default 16); loads every size 128 .. S, writes `<out>_tree_
 
 File reading and grid logic (read_picture, grid, to_map, histogram) need neither a device nor the library; run_maps needs the MI355X."""
 import argparse
+import contextlib
 import os
 import sys
 
@@ -134,30 +135,38 @@ def tree_summary(nodes: np.ndarray) -> list:
     return [(int(s), int((nodes["size"] == s).sum()), int(((nodes["size"] == s) & (nodes["first_child"] >= 0)).sum())) for s in SIZES if (nodes["size"] == s).any()]
 
 
+@contextlib.contextmanager
+def uploaded(m, org: np.ndarray, pred: np.ndarray):
+    """The frames of org / pred ([height, width] or [frames, height, width]) as resident picture pairs [(org_pic, pred_pic), ...], closed on exit."""
+    assert org.shape == pred.shape
+    height, width = org.shape[-2:]
+    pics = [(m.picture(width, height).upload(o), m.picture(width, height).upload(p)) for o, p in zip(org.reshape(-1, height, width), pred.reshape(-1, height, width))]
+    try:
+        yield pics
+    finally:
+        for a, b in pics:
+            a.close()
+            b.close()
+
+
 def run_tree(m, org: np.ndarray, pred: np.ndarray, poc: int, qp: int, min_size: int = 16) -> dict:
     """m: an MltCnn with tree_sizes(min_size) loaded -> {"nodes", "leaf_map"} (MltCnn.predict_tree)."""
-    assert org.shape == pred.shape
-    height, width = org.shape
-    p_org, p_pred = m.picture(width, height).upload(org), m.picture(width, height).upload(pred)
-    try:
-        return m.predict_tree(p_org, p_pred, poc, qp, top=128, min_size=min_size, want=("leaf_map",))
-    finally:
-        p_org.close()
-        p_pred.close()
+    assert org.ndim == 2
+    with uploaded(m, org, pred) as pics:
+        return m.predict_tree(pics[0][0], pics[0][1], poc, qp, top=128, min_size=min_size, want=("leaf_map",))
 
 
 def run_trees(m, org: np.ndarray, pred: np.ndarray, poc: int, qp: int, min_size: int = 16) -> list:
     """org / pred: [frames, height, width]; m: an MltCnn with tree_sizes(min_size) loaded -> one {"nodes", "leaf_map", "first_node"} per frame, all from ONE
     call (MltCnn.predict_trees); frame f takes poc + f."""
-    assert org.shape == pred.shape and org.ndim == 3
-    frames, height, width = org.shape
-    pics = [(m.picture(width, height).upload(org[f]), m.picture(width, height).upload(pred[f])) for f in range(frames)]
-    try:
-        return m.predict_trees(pics, [poc + f for f in range(frames)], qp, top=128, min_size=min_size, want=("leaf_map",))
-    finally:
-        for a, b in pics:
-            a.close()
-            b.close()
+    assert org.ndim == 3
+    with uploaded(m, org, pred) as pics:
+        return m.predict_trees(pics, [poc + f for f in range(len(pics))], qp, top=128, min_size=min_size, want=("leaf_map",))
+
+
+def save_tree(prefix: str, t: dict) -> None:
+    np.save(f"{prefix}_tree_nodes.npy", t["nodes"])
+    np.save(f"{prefix}_leafmap.npy", t["leaf_map"])
 
 
 def parse_args(argv=None):
@@ -220,16 +229,14 @@ def main(argv=None):
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     if args.tree and args.frames is not None:
         for f, t in enumerate(run_trees(m, org, pred, args.poc, args.qp, args.min_size)):
-            np.save(f"{args.out}_f{f}_tree_nodes.npy", t["nodes"])
-            np.save(f"{args.out}_f{f}_leafmap.npy", t["leaf_map"])
+            save_tree(f"{args.out}_f{f}", t)
             print(f"frame {f} (poc {args.poc + f}): {len(t['nodes'])} nodes from node {t['first_node']}  " +
                   "  ".join(f"{size}: {count} ({desc} descend)" for size, count, desc in tree_summary(t["nodes"])))
         m.close()
         return 0
     if args.tree:
         t = run_tree(m, org, pred, args.poc, args.qp, args.min_size)
-        np.save(f"{args.out}_tree_nodes.npy", t["nodes"])
-        np.save(f"{args.out}_leafmap.npy", t["leaf_map"])
+        save_tree(args.out, t)
         for size, count, desc in tree_summary(t["nodes"]):
             print(f"size {size}: {count} nodes, {desc} descend")
         print(f"tree: {len(t['nodes'])} nodes of at most {pkg.capi.tree_max_nodes(org.shape[1], org.shape[0], 128, args.min_size)}, "
