@@ -33,7 +33,9 @@ EXPORTS = ["mlt_abi_version", "mlt_build_signature", "mlt_init", "mlt_num_device
            "mlt_set_candidate_policy", "mlt_get_candidate_policy", "mlt_predict_candidates", "mlt_predict_batch_candidates",
            "mlt_predict_batch_device_candidates", "mlt_wait_candidates",
            "mlt_picture_create", "mlt_picture_upload", "mlt_picture_wrap_device", "mlt_picture_destroy", "mlt_predict_at", "mlt_grid_positions",
-           "mlt_tree_max_nodes", "mlt_tree_roots", "mlt_predict_tree", "mlt_predict_trees"]
+           "mlt_tree_max_nodes", "mlt_tree_roots", "mlt_predict_tree", "mlt_predict_trees",
+           "mlt_predict_batch_device_sweep", "mlt_predict_at_sweep"]
+SWEEP_MAX_QPS = 32  # MLT_SWEEP_MAX_QPS
 TREES_MAX_PICTURES = 256  # MLT_TREES_MAX_PICTURES
 TREE_BY_CANDIDATES = 0x1  # mlt_tree_config.flags: descend on cand_mask & descend_mask instead of on split_mode
 
@@ -158,6 +160,8 @@ def load_library():
     lib.mlt_picture_wrap_device.argtypes = [vp, vp, i32, i32, i32, C.POINTER(vp)]
     lib.mlt_picture_destroy.argtypes = [vp, vp]
     lib.mlt_predict_at.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.mlt_predict_batch_device_sweep.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.mlt_predict_at_sweep.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.mlt_grid_positions.argtypes = [i32, i32, i32, vp, i32]
     lib.mlt_tree_max_nodes.argtypes = [i32, i32, i32, i32]
     lib.mlt_tree_roots.argtypes = [i32, i32, i32, i32, vp, i32]
@@ -366,6 +370,13 @@ class MltCnn:
             return
         self._check(self._lib.mlt_predict_batch_device(self._h, n, size, d_org, d_pred, d_poc, d_qp, d_split, d_logits))
 
+    def predict_batch_device_sweep(self, n: int, size: int, d_org: int, d_pred: int, d_poc: int, qps, d_split: int | None = None, d_logits: int | None = None,
+                                   d_decisions: int | None = None, d_candidates: int | None = None):
+        """QP sweep on raw device pointers (mlt_predict_batch_device_sweep): one trunk pass, the heads under every value of the HOST sequence `qps`.  Every output is
+        device memory for len(qps) slabs of n CUs (element (q, i) at q * n + i); at least one of them; asynchronous on the context's stream like its twin."""
+        qps = np.ascontiguousarray(qps, np.int32).reshape(-1)
+        self._check(self._lib.mlt_predict_batch_device_sweep(self._h, n, size, d_org, d_pred, d_poc, qps.ctypes.data, qps.shape[0], d_split, d_logits, d_decisions, d_candidates))
+
     # -- per-level decisions with confidence, and the confidence gate ------------------------------
     def set_confidence_gate(self, size: int, min_confidence: float):
         """split = -1 unless the decision head's softmax probability reaches min_confidence (0 = off); every entry point, every device."""
@@ -499,6 +510,30 @@ class MltCnn:
         ptr = lambda k: out[k].ctypes.data if k in out else None
         self._check(self._lib.mlt_predict_at(self._h, int(size), org_pic._h, pred_pic._h, n, xy.ctypes.data, poc.ctypes.data, qp.ctypes.data,
                                              ptr("split"), ptr("logits"), ptr("decisions"), ptr("candidates")))
+        return out
+
+    def predict_at_sweep(self, size: int, org_pic: Picture, pred_pic: Picture, xy, poc, qps, want=("split", "logits", "decisions", "candidates")) -> dict:
+        """predict_at under every value of `qps` from ONE network pass (mlt_predict_at_sweep) -> {name: array with a leading [len(qps)] axis} for the names in
+        `want`; slab q is predict_at's result with every qp = qps[q], byte for byte."""
+        xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        n = xy.shape[0]
+        poc = np.ascontiguousarray(poc, np.int32)
+        qps = np.ascontiguousarray(qps, np.int32).reshape(-1)
+        Q = qps.shape[0]
+        assert poc.shape == (n,) and set(want) <= {"split", "logits", "decisions", "candidates"}
+        out = {}
+        if "split" in want:
+            out["split"] = np.full((Q, n), -1, np.int32)
+        if "logits" in want:
+            out["logits"] = np.zeros((Q, n, self.num_logits(size) or 1), np.float32)
+        if "decisions" in want:
+            out["decisions"] = np.zeros((Q, n), DECISION_DTYPE)
+            out["decisions"]["split_mode"] = -1
+        if "candidates" in want:
+            out["candidates"] = np.zeros((Q, n), CANDIDATES_DTYPE)
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        self._check(self._lib.mlt_predict_at_sweep(self._h, int(size), org_pic._h, pred_pic._h, n, xy.ctypes.data, poc.ctypes.data, qps.ctypes.data, Q,
+                                                   ptr("split"), ptr("logits"), ptr("decisions"), ptr("candidates")))
         return out
 
     @staticmethod

@@ -197,7 +197,7 @@ void mlt_shutdown(mlt_ctx *ctx) {
   if (ctx->zero_page) (void)hipFree(ctx->zero_page);
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   for (int b = 0; b < 2; ++b) { if (ctx->ev_h2d[b]) (void)hipEventDestroy(ctx->ev_h2d[b]); if (ctx->ev_done[b]) (void)hipEventDestroy(ctx->ev_done[b]); }
-  for (GrowBuf *buf : {&ctx->stage, &ctx->guard_dev, &ctx->gstage, &ctx->tree_dev, &ctx->h_res}) buf->release();
+  for (GrowBuf *buf : {&ctx->stage, &ctx->guard_dev, &ctx->gstage, &ctx->sweep_guard_dev, &ctx->tree_dev, &ctx->h_res}) buf->release();
   if (ctx->tree_host) (void)hipHostFree(ctx->tree_host);
   if (ctx->guard_host) (void)hipHostFree(ctx->guard_host);
   if (ctx->ev_guard) (void)hipEventDestroy(ctx->ev_guard);
@@ -272,6 +272,34 @@ int mlt_predict_batch_device_candidates(mlt_ctx *ctx, int n, int size, const voi
                                         void *d_candidates, void *d_decisions_opt, void *d_logits) {
   if (ctx && !d_candidates) { ctx->err = "bad argument"; return MLT_ERR_ARG; }
   return predict_batch_device_impl(ctx, n, size, d_org, d_pred, d_poc, d_qp, nullptr, d_logits, (DecisionRec *)d_decisions_opt, (CandRec *)d_candidates);
+}
+
+// One trunk pass per chunk, the heads under every point of qps[]: slab q of each output is the device-pointer twin's result with every qp[i] = qps[q].
+int mlt_predict_batch_device_sweep(mlt_ctx *ctx, int n, int size, const void *d_org, const void *d_pred, const void *d_poc, const int32_t *qps, int n_qps,
+                                   void *d_split_opt, void *d_logits_opt, void *d_decisions_opt, void *d_candidates_opt) {
+  if (!ctx) return MLT_ERR_ARG;
+  if (n < 0 || !qps || n_qps < 1 || n_qps > MLT_SWEEP_MAX_QPS || (!d_split_opt && !d_logits_opt && !d_decisions_opt && !d_candidates_opt) || (n > 0 && (!d_org || !d_pred || !d_poc))) {
+    ctx->err = "mlt_predict_batch_device_sweep: bad argument (qps, 1 <= n_qps <= 32, at least one output)";
+    return MLT_ERR_ARG;
+  }
+  SizeState *st;
+  int rc = check_size(ctx, size, &st);
+  if (rc) return rc;
+  if (n == 0) return MLT_OK;
+  if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
+  const int nl = st->model.n_logits;
+  const size_t cs = (size_t)size * size;
+  SweepPart sw;
+  sw.n_qps = n_qps; sw.slab = n;
+  std::memcpy(sw.qps, qps, (size_t)n_qps * 4);
+  for (int i0 = 0; i0 < n; i0 += ctx->chunk) {
+    const int c = n - i0 < ctx->chunk ? n - i0 : ctx->chunk;
+    const PassIO io{Planes::dense((const int16_t *)d_org + i0 * cs, (const int16_t *)d_pred + i0 * cs, size), (const int32_t *)d_poc + i0, nullptr,
+                    d_split_opt ? (int32_t *)d_split_opt + i0 : nullptr, d_logits_opt ? (float *)d_logits_opt + (size_t)i0 * nl : nullptr,
+                    d_decisions_opt ? (DecisionRec *)d_decisions_opt + i0 : nullptr, d_candidates_opt ? (CandRec *)d_candidates_opt + i0 : nullptr, sw};
+    if ((rc = run_checked_sweep(ctx, *st, c, io))) return rc;
+  }
+  return MLT_OK;
 }
 
 static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *org, const int16_t *pred, const int32_t *poc, const int32_t *qp,

@@ -654,6 +654,16 @@ int run_network(mlt_ctx *ctx, SizeState &st, const NetCfg &c, int n, const PassI
         ha.g_mag_thr = tail->mag_thr;
       }
       hipEvent_t e0 = nullptr, e1 = nullptr;
+      if (io.sweep.n_qps > 0) {   // QP sweep: the same arguments, the heads under every point (fix-up mode: io.sweep.idx)
+        HeadSweepArgs sa{};
+        sa.h = ha; sa.h.qp = nullptr; sa.h.mag = nullptr;
+        sa.n_qps = io.sweep.n_qps; sa.slab = io.sweep.slab; sa.fix_idx = io.sweep.idx; sa.mask = io.sweep.mask;
+        std::memcpy(sa.qps, io.sweep.qps, sizeof sa.qps);
+        if ((rc = L.prof_begin("heads_sweep", 0.0, 0.0, e0, e1))) return rc;
+        LAUNCH_TRY(ctx, mlt_launch_heads_sweep(sa, n, ctx->stream));
+        rc = L.prof_end(e1);
+        break;
+      }
       if ((rc = L.prof_begin("heads", 0.0, 0.0, e0, e1))) return rc;
       plan_note(ctx, {{"gap0", ha.gap[0]}, {"gap1", ha.gap[1]}, {"gap2", ha.gap[2]}, {"gap3", ha.gap[3]}},
                 {{"slots0", ha.slots[0]}, {"slots1", ha.slots[1]}, {"slots2", ha.slots[2]}, {"slots3", ha.slots[3]}, {"c0", ha.c[0]}, {"c1", ha.c[1]}, {"c2", ha.c[2]}, {"c3", ha.c[3]},

@@ -114,13 +114,10 @@ int guard_fixup_async(mlt_ctx *ctx, SizeState &st, int k, const PassIO &io, cons
   return MLT_OK;
 }
 
-// network for n CUs with whatever guards the size has; synchronises once when guards are on (see mlt_predict_batch_device).
-int run_checked(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io) {
-  const bool guards = st.guards();
-  GuardSlot g;
-  int rc;
-  if (guards && (rc = guard_slot(ctx, 0, n, st.model.n_logits, &g))) return rc;
-  if ((rc = run_fast_async(ctx, st, n, io, g)) || !guards) return rc;
+namespace {
+
+// Blocks until the 4-byte count of a guarded pass on n CUs, whose copy is the last thing enqueued on ctx->stream, has landed (run_checked, run_checked_sweep).
+int wait_count(mlt_ctx *ctx, SizeState &st, int n) {
   // Wait for the 4-byte count.  Default: SLEEP for most of the time the batch is expected to take (a running estimate per CU of this
   // size, learnt from the previous calls), then poll the event for the rest: the host core is idle for all but the last ~0.2 ms of a
   // 5 ms batch -- in the encoder host cores are the scarce resource -- and the caller's next batch is still enqueued the moment this one
@@ -159,8 +156,71 @@ int run_checked(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io) {
       st.guard_n[b] = n;
     }
   }
+  return MLT_OK;
+}
+
+}  // namespace
+
+// network for n CUs with whatever guards the size has; synchronises once when guards are on (see mlt_predict_batch_device).
+int run_checked(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io) {
+  const bool guards = st.guards();
+  GuardSlot g;
+  int rc;
+  if (guards && (rc = guard_slot(ctx, 0, n, st.model.n_logits, &g))) return rc;
+  if ((rc = run_fast_async(ctx, st, n, io, g)) || !guards) return rc;
+  if ((rc = wait_count(ctx, st, n))) return rc;
   const int k = *g.h_count;
   if (k < 0 || k > n) { ctx->err = "guard: bad flagged-CU count"; return MLT_ERR_HIP; }
   return k ? guard_fixup_async(ctx, st, k, io, g) : MLT_OK;
 }
 
+
+// QP sweep (io.sweep: qps, n_qps, slab): ONE pass of the size's main arithmetic whose heads step evaluates every point, the selection as that kernel's tail (per CU
+// a mask of the points it is flagged under; MLT_GUARD_SELECT_KERNEL does not apply), the 4-byte count of the CUs flagged under ANY point, then -- for k > 0 -- the
+// gather of that union and ONE exact pass on its k CUs, whose heads step writes each CU's exact results into the slabs of its mask only: no scatter launch.
+// Sizes without guards run the sweep heads and nothing else.  guard_reruns counts the union: what ran.
+int run_checked_sweep(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io) {
+  if (!st.guards()) return run_network(ctx, st, st.main_cfg(), n, io);
+  Lay::SweepGuardLay &lay = ctx->sweep_guard_lay;
+  if ((size_t)n > lay.n) lay = Lay::SweepGuardLay((size_t)n);
+  int rc;
+  if ((rc = ctx->sweep_guard_dev.reserve(ctx, lay.bytes(), "sweep guard slot", true))) return rc;   // (the counters must start at zero)
+  if (!ctx->guard_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->guard_host, 64, hipHostMallocDefault));
+  const Lay::GuardFields::Ptrs d = lay.at(ctx->sweep_guard_dev.p);
+  uint32_t *d_mask = lay.mask.in<uint32_t>(ctx->sweep_guard_dev.p);
+  int32_t *h_count = ctx->guard_host + 2;
+  GuardTail tail = guard_thresholds(ctx, st);
+  GuardOut go;
+  go.d_flat = st.flat_guard ? d.flat : nullptr;
+  tail.idx = d.idx; tail.flat = go.d_flat;
+  tail.count = d.count + ctx->sweep_phase; tail.next = d.count + (ctx->sweep_phase ^ 1);
+  go.tail = &tail;
+  PassIO fast = io;
+  fast.sweep.idx = nullptr; fast.sweep.mask = d_mask;
+  if ((rc = run_network(ctx, st, st.main_cfg(), n, fast, go))) {
+    (void)hipMemsetAsync(d.count, 0, 8, ctx->stream);   // (run_fast_async: the pass may or may not have run its heads kernel)
+    return rc;
+  }
+  ctx->sweep_phase ^= 1;
+  HIP_TRY(ctx, hipMemcpyAsync(h_count, tail.count, 4, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = wait_count(ctx, st, n))) return rc;
+  const int k = *h_count;
+  if (k < 0 || k > n) { ctx->err = "guard: bad flagged-CU count"; return MLT_ERR_HIP; }
+  if (!k) return MLT_OK;
+  const int S = st.size;
+  const StageSet gl(S, k, st.model.n_logits, false, false);
+  if ((rc = ctx->gstage.reserve(ctx, gl.bytes(), "guard staging"))) return rc;
+  const StageSet::Ptrs gs = gl.at(ctx->gstage.p);
+  GuardGatherArgs ga{};
+  io.pl.fill(ga);
+  ga.poc = io.poc; ga.qp = io.poc;   // (no per-CU qp in a sweep: the gather's qp column is a copy of poc and is not read)
+  ga.idx = d.idx; ga.k = k; ga.s_l = ilog2(S);
+  ga.g_org = gs.d_org; ga.g_pred = gs.d_pred; ga.g_poc = gs.d_poc; ga.g_qp = gs.d_qp;
+  HIP_TRY(ctx, mlt_launch_guard_gather(ga, ctx->stream));
+  PassIO exact = io;   // the caller's outputs: the heads step writes row idx[j] of the slabs in mask[idx[j]]
+  exact.pl = Planes::dense(gs.d_org, gs.d_pred, S); exact.poc = gs.d_poc; exact.qp = nullptr;
+  exact.sweep.idx = d.idx; exact.sweep.mask = d_mask;
+  if ((rc = run_network(ctx, st, st.exact_cfg(), k, exact))) return rc;
+  st.reruns += (uint64_t)k;
+  return MLT_OK;
+}

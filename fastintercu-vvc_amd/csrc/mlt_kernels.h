@@ -245,6 +245,21 @@ struct HeadArgs {
   int32_t *g_next;
 };
 
+// QP sweep (sweep_heads_kernel, mlt_tail_kernels.inc): the heads of one pass under n_qps values of qp.  `h` is read as by heads_kernel except h.qp (unused: point
+// q takes qps[q] for every CU) and h.mag (unused); the outputs of point q start `slab` CUs behind those of point q - 1 (h.logits: slab x sum-classes floats).
+// Fast pass (fix_idx == NULL): workgroup i is CU i and row i, every point is written; with the selection (h.g_next != NULL) mask[i] <- bit q set when CU i is
+// flagged under qps[q] (heads_kernel's rule), and a CU with a non-zero mask is appended to h.g_idx.  Fix-up (fix_idx != NULL, no selection): workgroup j is CU j of
+// the exact re-run, its row is fix_idx[j], and only the points whose bit is set in mask[fix_idx[j]] are written.
+#define MLT_SWEEP_MAX_QPS_K 32
+struct HeadSweepArgs {
+  HeadArgs h;
+  int32_t qps[MLT_SWEEP_MAX_QPS_K];
+  int n_qps;
+  long slab;
+  const int32_t *fix_idx;
+  uint32_t *mask;   // [rows]
+};
+
 // ---- parity guard (fast arithmetic): device-side selection of the CUs that are re-evaluated with the exact arithmetic ----
 struct FlatStatArgs {
   const int16_t *org, *pred;   // Pel planes
@@ -386,3 +401,4 @@ hipError_t mlt_launch_stem_block(const StemBlockArgs &a, bool w2, int grid_x, hi
 hipError_t mlt_launch_layer0_stream(const Layer0Args &a, bool fuse5, bool mfma32, int grid_x, hipStream_t st);
 hipError_t mlt_launch_layer1_stream(const Layer1Args &a, bool mfma32, int grid_x, hipStream_t st);
 hipError_t mlt_launch_heads(const HeadArgs &a, int n, hipStream_t st);
+hipError_t mlt_launch_heads_sweep(const HeadSweepArgs &a, int n, hipStream_t st);

@@ -826,6 +826,13 @@ hipError_t mlt_launch_heads(const HeadArgs &a, int n, hipStream_t st) {
   return hipGetLastError();
 }
 
+// n workgroups: the CUs of the pass (fix-up launches: of the exact re-run)
+hipError_t mlt_launch_heads_sweep(const HeadSweepArgs &a, int n, hipStream_t st) {
+  if (a.n_qps < 1 || a.n_qps > MLT_SWEEP_MAX_QPS_K || ((a.fix_idx || a.h.g_next) && !a.mask)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sweep_heads_kernel, dim3(n), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 hipError_t mlt_launch_flat_stat(const FlatStatArgs &a, bool aligned8, hipStream_t st) {
   if (aligned8) hipLaunchKernelGGL(flat_stat_kernel<true>, dim3(a.n), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(flat_stat_kernel<false>, dim3(a.n), dim3(256), 0, st, a);

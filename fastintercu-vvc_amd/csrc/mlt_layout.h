@@ -57,6 +57,22 @@ struct GuardLay : GuardFields, Carved {
   size_t n, nl;
   GuardLay(size_t n_ = 0, size_t nl_ = 0) : n(n_), nl(nl_) { flat = put(n * 4, 256); idx = put(n * 4, 256); count = put(8, 256); lg = put(n * nl * 4, 256); mag = put(n * 4, 256); }
 };
+// QP sweeps (mlt_predict_at_sweep): a staging set whose result parts hold n_qps slabs of `cap` CUs each -- org | pred | poc | split | logits [| records]
+// [| candidate records]; element (q, i) of a result part is entry q * cap + i (slab stride: cap).  No qp part: the points' values travel in the launch.
+struct SweepStageSet : CuFields {
+  size_t cap, n_qps;
+  SweepStageSet(int S, size_t cap_, size_t nl, size_t n_qps_, bool records, bool cands) : cap(cap_), n_qps(n_qps_) {
+    org = put(cap * S * S * 2, 256); pred = put(cap * S * S * 2, 256); poc = put(cap * 4, 256); split = put(n_qps * cap * 4, 256); lg = put(n_qps * cap * nl * 4, 256);
+    dec = put(n_qps * cap * sizeof(mlt_decision), 256, records); cand = put(n_qps * cap * sizeof(mlt_candidates), 256, cands);
+  }
+};
+// The guard slot of a sweep pass for up to n CUs: flat | idx | count (a pair of counters) | mask (per CU: bit q set = flagged under point q).  The selection is
+// always the sweep heads kernel's tail: no logits or magnitudes are kept for a selection launch.
+struct SweepGuardLay : GuardFields, Carved {
+  size_t n;
+  Field mask;
+  SweepGuardLay(size_t n_ = 0) : n(n_) { flat = put(n * 4, 256); idx = put(n * 4, 256); count = put(8, 256); mask = put(n * 4, 256); }
+};
 // mlt_predict's staging (device buffer and its pinned mirror): org | pred | poc qp | split count logits record candidate-record | flat idx mag.  One H2D brings planes,
 // poc and qp (h2d_bytes); one D2H takes the host-visible prefix from `split` on back, as far as the call's kind needs (fetch).  The guards select on g.
 struct SingleLay : CuFields {

@@ -86,6 +86,67 @@ int predict_at_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &pl, int n, co
   return MLT_OK;
 }
 
+// predict_at_chunks for a QP sweep (host lists only): per chunk the same position upload and gather, ONE sweep pass (run_checked_sweep) into a staging set of
+// n_qps slabs, then the chunk's part of every slab D2H -- element (q, i) of the caller's arrays is entry q * n_all + i; this device's CUs start at entry `first`.
+static int predict_at_sweep_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &pl, int n, const int32_t *xy, const int32_t *poc, const int32_t *qps, int n_qps,
+                                   const AtOut &out, size_t n_all, size_t first) {
+  if (hipSetDevice(dev->device) != hipSuccess) { dev->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
+  const int size = st->size, nl = st->model.n_logits;
+  const int cap = n < dev->chunk ? n : dev->chunk;
+  const Lay::SweepStageSet lay(size, (size_t)cap, (size_t)nl, (size_t)n_qps, out.dec != nullptr, out.cand != nullptr);
+  int rc;
+  if ((rc = dev->stage.reserve(dev, lay.bytes() + Lay::up256((size_t)cap * 8), "staging"))) return rc;   // the set, then the chunk's positions
+  const Lay::SweepStageSet::Ptrs S = lay.at(dev->stage.p);
+  int32_t *d_xy = (int32_t *)(dev->stage.p + lay.bytes());
+  SweepPart sw;
+  sw.n_qps = n_qps; sw.slab = cap;
+  std::memcpy(sw.qps, qps, (size_t)n_qps * 4);
+  for (int i0 = 0; i0 < n; i0 += cap) {
+    const int c = n - i0 < cap ? n - i0 : cap;
+    HIP_TRY(dev, hipMemcpyAsync(d_xy, xy + 2 * (size_t)i0, (size_t)c * 8, hipMemcpyHostToDevice, dev->stream));
+    HIP_TRY(dev, hipMemcpyAsync(S.d_poc, poc + i0, (size_t)c * 4, hipMemcpyHostToDevice, dev->stream));
+    Launch L{dev};
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    PictureGatherArgs ga{};
+    ga.org = pl.org; ga.pred = pl.pred; ga.org_pitch = pl.org_pitch; ga.pred_pitch = pl.pred_pitch; ga.vec_org = pl.org_vec; ga.vec_pred = pl.pred_vec;
+    ga.xy = d_xy; ga.g_org = S.d_org; ga.g_pred = S.d_pred; ga.c = c; ga.s_l = ilog2(size);
+    if ((rc = L.prof_begin("picture_gather", 0.0, (double)c * size * size * 2 * 2 * 2, e0, e1))) return rc;
+    LAUNCH_TRY(dev, mlt_launch_picture_gather(ga, dev->stream));
+    if ((rc = L.prof_end(e1))) return rc;
+    const PassIO io{Planes::dense(S.d_org, S.d_pred, size), S.d_poc, nullptr, S.d_split, out.logits ? S.d_lg : nullptr, S.d_dec, S.d_cand, sw};
+    if ((rc = run_checked_sweep(dev, *st, c, io))) return rc;
+    for (int q = 0; q < n_qps; ++q) {
+      const size_t src = (size_t)q * cap, dst = (size_t)q * n_all + first + (size_t)i0;
+      if (out.split) HIP_TRY(dev, hipMemcpyAsync(out.split + dst, S.d_split + src, (size_t)c * 4, hipMemcpyDeviceToHost, dev->stream));
+      if (out.logits) HIP_TRY(dev, hipMemcpyAsync(out.logits + dst * nl, S.d_lg + src * nl, (size_t)c * nl * 4, hipMemcpyDeviceToHost, dev->stream));
+      if (out.dec) HIP_TRY(dev, hipMemcpyAsync(out.dec + dst, (const mlt_decision *)S.d_dec + src, (size_t)c * sizeof(mlt_decision), hipMemcpyDeviceToHost, dev->stream));
+      if (out.cand) HIP_TRY(dev, hipMemcpyAsync(out.cand + dst, (const mlt_candidates *)S.d_cand + src, (size_t)c * sizeof(mlt_candidates), hipMemcpyDeviceToHost, dev->stream));
+    }
+    HIP_TRY(dev, hipStreamSynchronize(dev->stream));   // the set is reused by the next chunk, the arrays are the caller's
+  }
+  return MLT_OK;
+}
+
+// What mlt_predict_at and its sweep form check of the picture pair and the positions before anything is enqueued (`who` opens the message); n > 0.
+static int check_at_pair(mlt_ctx *ctx, const char *who, const mlt_picture *org, const mlt_picture *pred) {
+  if (!owns(ctx, org) || !owns(ctx, pred)) { ctx->err = std::string(who) + ": both pictures must belong to this context"; return MLT_ERR_ARG; }
+  if (org->width != pred->width || org->height != pred->height) { ctx->err = std::string(who) + ": the two pictures differ in width or height"; return MLT_ERR_ARG; }
+  return MLT_OK;
+}
+static int check_at_positions(mlt_ctx *ctx, const char *who, int size, const mlt_picture *org, int n, const int32_t *xy) {
+  // every position, before anything is enqueued: the gather kernel trusts them
+  for (int i = 0; i < n; ++i) {
+    const long x = xy[2 * (size_t)i], y = xy[2 * (size_t)i + 1];
+    if (x < 0 || y < 0 || x + size > org->width || y + size > org->height) {
+      char msg[224];
+      std::snprintf(msg, sizeof msg, "%s: position %d (x = %ld, y = %ld) puts a %d x %d CU outside the %d x %d picture", who, i, x, y, size, size, org->width, org->height);
+      ctx->err = msg;
+      return MLT_ERR_ARG;
+    }
+  }
+  return MLT_OK;
+}
+
 bool owns_picture(const mlt_ctx *ctx, const mlt_picture *pic) { return owns(ctx, pic); }
 
 void free_pictures(mlt_ctx *ctx) {
@@ -174,19 +235,9 @@ int mlt_predict_at(mlt_ctx *ctx, int size, const mlt_picture *org, const mlt_pic
   SizeState *st;
   int rc = check_size(ctx, size, &st);
   if (rc) return rc;
-  if (!owns(ctx, org) || !owns(ctx, pred)) { ctx->err = "mlt_predict_at: both pictures must belong to this context"; return MLT_ERR_ARG; }
-  if (org->width != pred->width || org->height != pred->height) { ctx->err = "mlt_predict_at: the two pictures differ in width or height"; return MLT_ERR_ARG; }
+  if ((rc = check_at_pair(ctx, "mlt_predict_at", org, pred))) return rc;
   if (n == 0) return MLT_OK;
-  // every position, before anything is enqueued: the gather kernel trusts them
-  for (int i = 0; i < n; ++i) {
-    const long x = xy[2 * (size_t)i], y = xy[2 * (size_t)i + 1];
-    if (x < 0 || y < 0 || x + size > org->width || y + size > org->height) {
-      char msg[192];
-      std::snprintf(msg, sizeof msg, "mlt_predict_at: position %d (x = %ld, y = %ld) puts a %d x %d CU outside the %d x %d picture", i, x, y, size, size, org->width, org->height);
-      ctx->err = msg;
-      return MLT_ERR_ARG;
-    }
-  }
+  if ((rc = check_at_positions(ctx, "mlt_predict_at", size, org, n, xy))) return rc;
   const AtOut out{split_mode_opt, logits_opt, dec_opt, cand_opt};
   if (!ctx->peers.empty() && n > 1)   // every device gathers from its own copy of the planes (both pictures belong to ctx: a plane per device of it)
     return run_sharded(ctx, n, [&](int g, int lo, int hi) -> int {
@@ -197,6 +248,30 @@ int mlt_predict_at(mlt_ctx *ctx, int size, const mlt_picture *org, const mlt_pic
       return predict_at_chunks(dev, sg, AtPlanes::of(org, pred, g), hi - lo, AtList::host(xy + 2 * (size_t)lo, poc + lo, qp + lo), o);
     });
   return predict_at_chunks(ctx, st, AtPlanes::of(org, pred, 0), n, AtList::host(xy, poc, qp), out);
+}
+
+int mlt_predict_at_sweep(mlt_ctx *ctx, int size, const mlt_picture *org, const mlt_picture *pred, int n, const int32_t *xy, const int32_t *poc,
+                         const int32_t *qps, int n_qps, int32_t *split_opt, float *logits_opt, mlt_decision *dec_opt, mlt_candidates *cand_opt) {
+  if (!ctx) return MLT_ERR_ARG;
+  if (n < 0 || !org || !pred || !qps || n_qps < 1 || n_qps > MLT_SWEEP_MAX_QPS || (!split_opt && !logits_opt && !dec_opt && !cand_opt) || (n > 0 && (!xy || !poc))) {
+    ctx->err = "mlt_predict_at_sweep: bad argument (qps, 1 <= n_qps <= 32, at least one output)";
+    return MLT_ERR_ARG;
+  }
+  SizeState *st;
+  int rc = check_size(ctx, size, &st);
+  if (rc) return rc;
+  if ((rc = check_at_pair(ctx, "mlt_predict_at_sweep", org, pred))) return rc;
+  if (n == 0) return MLT_OK;
+  if ((rc = check_at_positions(ctx, "mlt_predict_at_sweep", size, org, n, xy))) return rc;
+  const AtOut out{split_opt, logits_opt, dec_opt, cand_opt};
+  if (!ctx->peers.empty() && n > 1)   // every device writes its [lo, hi) range of every slab
+    return run_sharded(ctx, n, [&](int g, int lo, int hi) -> int {
+      mlt_ctx *dev = device_of(ctx, g);
+      SizeState *sg = &dev->sz[size_index(size)];
+      if (!sg->enabled || !sg->loaded) { dev->err = "CU size not enabled or weights not loaded"; return MLT_ERR_SIZE_DISABLED; }
+      return predict_at_sweep_chunks(dev, sg, AtPlanes::of(org, pred, g), hi - lo, xy + 2 * (size_t)lo, poc + lo, qps, n_qps, out, (size_t)n, (size_t)lo);
+    });
+  return predict_at_sweep_chunks(ctx, st, AtPlanes::of(org, pred, 0), n, xy, poc, qps, n_qps, out, (size_t)n, 0);
 }
 
 int mlt_grid_positions(int width, int height, int size, int32_t *xy, int cap) {

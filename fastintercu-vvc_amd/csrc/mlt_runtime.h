@@ -293,6 +293,9 @@ struct mlt_ctx {
   int guard_phase[2] = {0, 0};    // which counter of a slot's pair the next batch launch counts on (GuardSlot.phase)
   hipEvent_t ev_guard = nullptr;  // "count of flagged CUs has landed" (device-pointer entry)
   GrowBuf gstage;
+  GrowBuf sweep_guard_dev;              // QP sweeps: one slot of sweep_guard_lay (zero when allocated), its counter phase; the count lands in guard_host[2]
+  Lay::SweepGuardLay sweep_guard_lay;
+  int sweep_phase = 0;
   // mlt_predict_tree's / mlt_predict_trees' device arena (Lay::TreeArena) and its pinned count
   GrowBuf tree_dev;
   int32_t *tree_host = nullptr;
@@ -321,6 +324,7 @@ static_assert(sizeof(mlt_tree_node) == 32 && sizeof(TreeNodeRec) == 32 && offset
 static_assert(sizeof(mlt_tree_config) == 40, "mlt_tree_config is 40 bytes");
 static_assert(sizeof(mlt_tree_picture) == 24 && MLT_TREES_ROW == MLT_MAX_LOGITS && MLT_TREES_LEVELS == Lay::TreeArena::kLevels && sizeof(TreesEntry) == 48, "mlt_predict_trees layouts");
 
+static_assert(MLT_SWEEP_MAX_QPS == MLT_SWEEP_MAX_QPS_K, "the sweep kernel's point array holds the ABI's maximum");
 static_assert(sizeof(mlt_candidates) == 40 && sizeof(CandRec) == sizeof(mlt_candidates) && offsetof(mlt_candidates, order) == offsetof(CandRec, order) &&
               offsetof(mlt_candidates, prob) == offsetof(CandRec, prob) && offsetof(mlt_candidates, prob) == 16, "mlt_candidates layout");
 
@@ -358,6 +362,17 @@ struct Planes {
   }
 };
 
+// QP sweep part of a pass (off unless n_qps > 0): the heads step evaluates every CU under qps[0 .. n_qps) -- sweep_heads_kernel instead of the heads kernel --
+// and output (q, i) of split / logits / dec / cand lies `slab` CUs x q behind output (0, i); PassIO.qp is not read.  idx + mask: the pass is the exact re-run of
+// a sweep's flagged CUs -- CU j writes row idx[j] of the points in mask[idx[j]]; mask alone (with the guards' tail): where the fast pass leaves the CUs' masks.
+struct SweepPart {
+  int n_qps = 0;
+  int32_t qps[MLT_SWEEP_MAX_QPS] = {0};
+  long slab = 0;
+  const int32_t *idx = nullptr;
+  uint32_t *mask = nullptr;
+};
+
 // what a pass reads and writes per CU (device memory; any of the outputs may be NULL)
 struct PassIO {
   Planes pl;
@@ -366,6 +381,7 @@ struct PassIO {
   float *logits;
   DecisionRec *dec;
   CandRec *cand = nullptr;
+  SweepPart sweep;
 };
 
 // what a pass produces for the guards besides (all unset: a plain pass)
@@ -432,6 +448,7 @@ int guard_slot(mlt_ctx *ctx, int which, int n, int nl, GuardSlot *g);
 int run_fast_async(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io, const GuardSlot &g);
 int guard_fixup_async(mlt_ctx *ctx, SizeState &st, int k, const PassIO &io, const GuardSlot &g);
 int run_checked(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io);
+int run_checked_sweep(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io);   // io.sweep: qps, n_qps, slab
 // mlt_calibrate.cpp
 void free_model(mlt::Model &m);
 void drop_graphs(mlt_ctx *ctx, int si);

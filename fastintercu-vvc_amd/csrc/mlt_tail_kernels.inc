@@ -225,6 +225,145 @@ __global__ __launch_bounds__(256) void heads_kernel(const HeadArgs a) { heads_bo
 // Records, gate and candidate sets: launched only when a candidate buffer or a candidate policy is present (mlt_launch_heads).
 __global__ __launch_bounds__(256) void heads_cand_kernel(const HeadArgs a) { heads_body<true, true>(a); }
 
+// QP sweep (HeadSweepArgs): the heads of ONE pass under n_qps values of qp -- slab q holds what heads_kernel / heads_cand_kernel give with every qp[i] = qps[q],
+// bit for bit.  qp enters a logit as the LAST element of one lane's fmaf chain (index C + 1 of [feat, poc, qp]: lane (C + 1) & 63), so the per-lane partial sums
+// over [feat, poc] are computed once per (head, class) with heads_body's chain; a point adds its one fmaf in that lane and repeats the shuffle tree and the bias.
+// The magnitude statistic does not see qp: once.  The tails run on one thread per (point, head) -- head_decision -- and one per point -- split under the gate,
+// records, the guards' rule (heads_body's, same comparisons): the points of wave 0 vote the CU's mask.  Fix-up launches (sa.fix_idx) write only the masked points.
+__global__ __launch_bounds__(256) void sweep_heads_kernel(const HeadSweepArgs sa) {
+  const HeadArgs &a = sa.h;
+  __shared__ float feat[MLT_MAX_HEADS_K][256 + 2];
+  __shared__ float lg[MLT_SWEEP_MAX_QPS_K][MLT_MAX_LOGITS_K];
+  __shared__ int hmode[MLT_SWEEP_MAX_QPS_K][MLT_MAX_HEADS_K];
+  __shared__ float hconf[MLT_SWEEP_MAX_QPS_K][MLT_MAX_HEADS_K], hmarg[MLT_SWEEP_MAX_QPS_K][MLT_MAX_HEADS_K];
+  __shared__ float lgm[MLT_MAX_LOGITS_K];
+  __shared__ int sflat;
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, Q = sa.n_qps;
+  const int row = sa.fix_idx ? sa.fix_idx[n] : n;
+  const uint32_t all = Q >= 32 ? 0xFFFFFFFFu : (1u << Q) - 1u;
+  const uint32_t wr = sa.fix_idx ? sa.mask[row] & all : all;   // the points this workgroup writes
+  const bool select = !sa.fix_idx && a.g_count && a.g_next;
+  const float fpoc = (float)a.poc[n];
+  for (int hd = 0; hd < a.n_heads; ++hd) {   // heads_body's features: slot-order sums, / (float)hw
+    const int C = a.c[hd], slots = a.slots[hd];
+    if (tid < C) {
+      const float *g = a.gap[hd] + (size_t)n * slots * C + tid;
+      float s = 0.f;
+      for (int i = 0; i < slots; i += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = i + u < slots ? g[(size_t)(i + u) * C] : 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (i + u < slots) s += v[u];
+      }
+      feat[hd][tid] = s / (float)a.hw[hd];
+    }
+    if (tid == 0) feat[hd][C] = fpoc;
+  }
+  if (tid == 0 && select && a.g_flat) { sflat = a.g_flat[n]; a.g_flat[n] = 0; }   // consume-and-clear, once for all points
+  __syncthreads();
+  int lo = 0;
+  for (int hd = 0; hd < a.n_heads; ++hd) {
+    const int C = a.c[hd], K = a.classes[hd];
+    for (int k = wave; k < K; k += 4) {
+      const float *w = a.w[hd] + (size_t)k * (C + 2);
+      float s = 0.f, m = 0.f;
+      for (int i = lane; i < C + 1; i += 64) {
+        s = __builtin_fmaf(w[i], feat[hd][i], s);
+        if (i < C) m += fabsf(w[i] * feat[hd][i]);
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) m += __shfl_down(m, off, 64);
+      const bool mine = lane == ((C + 1) & 63);
+      const float wq = w[C + 1], bk = a.b[hd][k];
+      for (int q = 0; q < Q; ++q) {
+        float sq = mine ? __builtin_fmaf(wq, (float)sa.qps[q], s) : s;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) sq += __shfl_down(sq, off, 64);
+        if (lane == 0) lg[q][lo + k] = sq + bk;
+      }
+      if (lane == 0) lgm[lo + k] = m;
+    }
+    lo += K;
+  }
+  __syncthreads();
+  if (a.logits)
+    for (int t = tid; t < Q * lo; t += 256) {
+      const int q = t / lo, e = t - q * lo;
+      if ((wr >> q) & 1u) a.logits[((size_t)q * sa.slab + row) * lo + e] = lg[q][e];
+    }
+  const bool cand_on = a.cand || a.cand_cov > 0.f || a.cand_max > 0;   // mlt_launch_heads' choice of heads_cand_kernel ...
+  const bool dec_on = cand_on || a.dec || a.min_conf > 0.f;           // ... and of heads_kernel<true>
+  if (dec_on) {   // one thread per (point, head)
+    if (tid < Q * a.n_heads) {
+      const int q = tid / a.n_heads, hd = tid - q * a.n_heads;
+      int o = 0;
+      for (int h = 0; h < hd; ++h) o += a.classes[h];
+      int bm; float cf, mg;
+      head_decision(lg[q] + o, a.classes[hd], bm, cf, mg);
+      hmode[q][hd] = bm; hconf[q][hd] = cf; hmarg[q][hd] = mg;
+    }
+    __syncthreads();
+  }
+  if (wave == 0) {   // one thread per point
+    bool s = false;
+    if (tid < Q) {
+      const int q = tid;
+      const bool wq_on = (wr >> q) & 1u;
+      const size_t dst = (size_t)q * sa.slab + row;
+      const float *l = lg[q];
+      int off = 0;
+      for (int hd = 0; hd < a.decision_head; ++hd) off += a.classes[hd];
+      int best = 0;
+      for (int k = 1; k < a.classes[a.decision_head]; ++k)
+        if (l[off + k] > l[off + best]) best = k;
+      int out = best;
+      float conf = 0.f;
+      if (dec_on) {
+        conf = hconf[q][a.decision_head];
+        if (a.min_conf > 0.f) out = conf >= a.min_conf ? best : -1;   // (a NaN confidence gates)
+        if (a.dec && wq_on) {
+          DecisionRec r;
+          r.split_mode = out; r.raw_mode = best; r.confidence = conf; r.margin = hmarg[q][a.decision_head];
+#pragma unroll
+          for (int hd = 0; hd < MLT_MAX_HEADS_K; ++hd) {
+            r.level_mode[hd] = hd < a.n_heads ? hmode[q][hd] : -1;
+            r.level_conf[hd] = hd < a.n_heads ? hconf[q][hd] : 0.f;
+          }
+          a.dec[dst] = r;
+        }
+      }
+      bool cflag = false;
+      if (cand_on) {
+        CandRec cr;
+        head_candidates(l + off, a.classes[a.decision_head], a.cand_cov, a.cand_max, a.g_cand_band, a.g_margin, cr, cflag);
+        if (a.cand && wq_on) a.cand[dst] = cr;
+      }
+      if (a.split && wq_on) a.split[dst] = out;
+      if (select) {   // heads_body's rule for this CU under qps[q]
+        if (a.g_flat) s = (sflat >> MLT_FLAT_EXACT_SHIFT) >= a.g_flat_thr || (sflat & 0xFFFF) >= a.g_near_thr;
+        if (a.g_margin > 0.f) {
+          s = s || margin_guard(l + off, a.classes[a.decision_head], a.g_margin);
+          if (dec_on && a.g_conf_band > 0.f) s = s || !(fabsf(conf - a.min_conf) >= a.g_conf_band);
+          if (cand_on) s = s || cflag;
+        }
+        if (a.g_mag_thr > 0.f) {
+          float mag = 0.f;
+          for (int k = 0; k < lo; ++k) mag = !(lgm[k] <= mag) ? lgm[k] : mag;   // (a NaN sticks)
+          s = s || !(mag <= a.g_mag_thr);
+        }
+      }
+    }
+    const uint32_t mask = (uint32_t)__ballot(s) & all;
+    if (tid == 0 && select) {
+      sa.mask[n] = mask;
+      if (n == 0) a.g_next[0] = 0;   // re-arm the slot's other counter
+      if (mask) a.g_idx[atomicAdd(a.g_count, 1)] = n;
+    }
+  }
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // Parity guard of the fast arithmetic.  fp16 rounding noise is averaged away by the global pooling only where

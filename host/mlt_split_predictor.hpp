@@ -242,6 +242,30 @@ class SplitPredictor {
     return true;
   }
 
+  // predictAt() under nQps values of the CU QP from ONE network pass (include/mltcnn.h: mlt_predict_at_sweep; 1 <= nQps <= MLT_SWEEP_MAX_QPS): the outputs hold
+  // nQps slabs of n entries, element (q, i) at q * n + i, slab q being what predictAt() gives with every cuQP[i] = qps[q].  false on failure: every split mode of
+  // every slab -1, every candidate record keeps all classes (full RDO), no prediction in the decision records.
+  bool predictAtSweep(const mlt_picture *org, const mlt_picture *pred, int cuw, int n, const int32_t *xy, const int32_t *poc, const int32_t *qps, int nQps,
+                      int32_t *splitModes, mlt_candidates *candOpt = nullptr, mlt_decision *decOpt = nullptr, float *logitsOpt = nullptr) {
+    Timer tm(this, 0, cuw);
+    const long total = (nQps > 0 && nQps <= MLT_SWEEP_MAX_QPS && n > 0) ? (long)nQps * n : 0;
+    if (!m_ctx || !splitModes || mlt_predict_at_sweep(m_ctx, cuw, org, pred, n, xy, poc, qps, nQps, splitModes, logitsOpt, decOpt, candOpt) != MLT_OK) {
+      std::fprintf(stderr, "error\n");  // EncCu.cpp:925
+      for (long i = 0; i < total; ++i) {
+        if (splitModes) splitModes[i] = -1;
+        if (candOpt) failCandidates(cuw, candOpt + i, decOpt ? decOpt + i : nullptr);
+        else if (decOpt) { decOpt[i] = mlt_decision{}; decOpt[i].split_mode = decOpt[i].raw_mode = -1; }
+      }
+      ++m_failed;
+      return false;
+    }
+    for (long i = 0; i < total; ++i) {
+      if (splitModes[i] < 0) ++m_gated;
+      if (candOpt) m_keptModes += (unsigned long long)candOpt[i].count;
+    }
+    return true;
+  }
+
   // The partition tree of a picture pair (include/mltcnn.h: mlt_predict_tree): the quadtree descent from topSize down to minSize on the device, one (poc, qp) pair
   // for the picture.  nodes: level by level in the contract's order; leafMap: one byte per complete 16 x 16 block, [mapH][mapW], (log2(leaf size) - 4) |
   // ((split_mode + 1) << 4), 0xFF where no node covers the block.  On failure the tree is EMPTY (no nodes, no map): the caller visits every CU, as with -1.

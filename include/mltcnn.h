@@ -351,6 +351,30 @@ int mlt_picture_destroy(mlt_ctx *ctx, mlt_picture *pic);
 int mlt_predict_at(mlt_ctx *ctx, int size, const mlt_picture *org, const mlt_picture *pred, int n, const int32_t *xy, const int32_t *poc, const int32_t *qp,
                    int32_t *split_mode_opt, float *logits_opt, mlt_decision *dec_opt, mlt_candidates *cand_opt);
 
+/* ---- QP sweeps: one network pass, the heads under up to 32 QPs per CU (new exports; MLT_ABI_VERSION stays 4) ----
+ * "What would this frame's split prior be at QP 27, 32, 37?"  poc and qp enter the network in the heads only, so a sweep runs the conv trunk ONCE per CU and the
+ * heads once per point of qps[] -- not n_qps full calls.  poc stays per CU (the CUs of a call may come from different frames); qps[0 .. n_qps) is a HOST array that
+ * applies to every CU: 1 <= n_qps <= MLT_SWEEP_MAX_QPS, any values in any order, duplicates and negative values included.
+ * OUTPUTS are slab-major: element (q, i) of the split modes, decision records and candidate records lives at index q * n + i, the logits of (q, i) start at
+ * (q * n + i) * mlt_num_logits(size); every array holds n_qps * n elements.  At least one output must be non-NULL.
+ * CONTRACT: slab q is byte for byte what the twin without a sweep returns on the same CUs with every qp[i] = qps[q], under the same gate, candidate policy, flags and
+ * tier -- the twin of the device entry is mlt_predict_batch_device and its decision / candidate forms, the twin of the picture entry is mlt_predict_at.  The guards
+ * see the logits, so whether a CU is re-evaluated exactly depends on the point: the exact re-run covers the CUs flagged under ANY point, and its results replace
+ * the fast ones only in the slabs where that CU was flagged.
+ * guard_reruns (mlt_arith_info) grows by the number of DISTINCT CUs re-evaluated -- the size of that union, which is what ran: at most the sum and at least the
+ * maximum of what the n_qps twin calls would add.
+ * ERRORS: everything is checked before anything is enqueued, and on an error the outputs stay untouched.  MLT_ERR_ARG: NULL ctx, NULL qps, n_qps out of range, no
+ * output at all and, on the picture entry, everything its twin checks (the offending position's index is named through mlt_last_error); MLT_ERR_SIZE_DISABLED: a
+ * size that is not loaded.  n == 0 returns MLT_OK.
+ * Chunked by the context's pass size like the twins; the device entry blocks once per chunk for the guards' 4-byte count, the picture entry is synchronous and, on a
+ * multi-device context, sharded (every device writes its range of every slab).  A sweep call with candidate records does NOT make deferred batches carry candidate
+ * records.  Not there: a tree sweep, host-dense, single-CU and deferred forms, a sweep over poc. */
+#define MLT_SWEEP_MAX_QPS 32
+int mlt_predict_batch_device_sweep(mlt_ctx *ctx, int n, int size, const void *d_org, const void *d_pred, const void *d_poc, const int32_t *qps /* HOST */, int n_qps,
+                                   void *d_split_opt, void *d_logits_opt, void *d_decisions_opt, void *d_candidates_opt);
+int mlt_predict_at_sweep(mlt_ctx *ctx, int size, const mlt_picture *org, const mlt_picture *pred, int n, const int32_t *xy, const int32_t *poc,
+                         const int32_t *qps, int n_qps, int32_t *split_opt, float *logits_opt, mlt_decision *dec_opt, mlt_candidates *cand_opt);
+
 /* Pure host, no context: the COMPLETE CUs of the size-aligned grid in raster order -- (width / size) * (height / size) positions; the partial CUs at the right and
  * bottom border are left out (VTM splits them implicitly).  Returns the total count and writes min(count, cap) entries of {x, y} to xy; xy == NULL with cap == 0 is
  * the size query.  0 for an unsupported size or a picture smaller than the size. */

@@ -17,6 +17,9 @@ children, down to S (default 16); loads every size 128 .. S, writes `<out>_tree_
 (MltCnn.predict_trees: one network pass per level over the nodes of all frames); --poc is the first frame's POC, frame f takes --poc + f.  Writes
 `<out>_f<f>_tree_nodes.npy` and `<out>_f<f>_leafmap.npy` per frame.
 
+--qps 22,27,32,37 (without --tree): one map set PER QP from ONE sweep call per size (MltCnn.predict_at_sweep: the network runs once, the heads once per QP),
+written as `<out>_<S>_qp<QP>_split.npy` etc.; --qp is not consulted.  Combined with --tree it is refused: the descents diverge per QP (no tree sweep).
+
 File reading and grid logic (read_picture, grid, to_map, histogram) need neither a device nor the library; run_maps needs the MI355X."""
 import argparse
 import contextlib
@@ -123,6 +126,39 @@ def run_maps(m, org: np.ndarray, pred: np.ndarray, sizes, poc: int, qp: int) -> 
     return out
 
 
+def run_maps_sweep(m, org: np.ndarray, pred: np.ndarray, sizes, poc: int, qps) -> dict:
+    """run_maps under every QP of `qps` from one sweep call per size -> {size: {qp: {"xy", "split", "confidence", "mask"}}} (a duplicate QP keeps one entry)."""
+    from fastintercu_vvc_amd import capi
+    assert org.shape == pred.shape
+    height, width = org.shape
+    p_org, p_pred = m.picture(width, height).upload(org), m.picture(width, height).upload(pred)
+    out = {}
+    try:
+        for size in sizes:
+            xy = capi.grid_positions(width, height, size)
+            if not len(xy):
+                continue
+            r = m.predict_at_sweep(size, p_org, p_pred, xy, np.full(len(xy), poc, np.int32), qps, want=("decisions", "candidates"))
+            out[size] = {int(qp): {"xy": xy, "split": to_map(r["decisions"]["split_mode"][q], width, height, size),
+                                   "confidence": to_map(r["decisions"]["confidence"][q], width, height, size),
+                                   "mask": to_map(r["candidates"]["mask"][q], width, height, size)} for q, qp in enumerate(qps)}
+    finally:
+        p_org.close()
+        p_pred.close()
+    return out
+
+
+def parse_qps(text: str) -> tuple:
+    """"22,27,32,37" -> (22, 27, 32, 37); 1 .. 32 integers (capi.SWEEP_MAX_QPS)."""
+    try:
+        qps = tuple(int(v) for v in text.split(",") if v.strip())
+    except ValueError:
+        raise ValueError(f"--qps {text}: want comma-separated integers") from None
+    if not 1 <= len(qps) <= 32:
+        raise ValueError(f"--qps {text}: want 1 .. 32 values")
+    return qps
+
+
 def tree_sizes(min_size: int) -> tuple:
     """The CU sizes a tree from 128 down to min_size evaluates (what --tree loads instead of --sizes)."""
     if min_size not in SIZES:
@@ -180,6 +216,7 @@ def parse_args(argv=None):
     ap.add_argument("--synthetic", type=int, help="seeded synthetic weights instead of --weights-dir")
     ap.add_argument("--poc", type=int, default=0)
     ap.add_argument("--qp", type=int, default=32)
+    ap.add_argument("--qps", default=None, help="comma-separated QPs: one map set per QP from one sweep call per size (not with --tree)")
     ap.add_argument("--min-conf", type=float, default=0.0, help="confidence gate")
     ap.add_argument("--coverage", type=float, default=0.0, help="candidate policy: coverage")
     ap.add_argument("--max-modes", type=int, default=0, help="candidate policy: cap")
@@ -196,6 +233,14 @@ def parse_args(argv=None):
         ap.error("--min-size goes with --tree")
     if args.frames is not None and (not args.tree or not 1 <= args.frames <= 256):
         ap.error("--frames goes with --tree, 1 .. 256")
+    args.qp_list = None
+    if args.qps is not None:
+        if args.tree:
+            ap.error("--qps does not go with --tree: the descents of a tree diverge per QP and there is no tree sweep; run one --tree call per QP")
+        try:
+            args.qp_list = parse_qps(args.qps)
+        except ValueError as e:
+            ap.error(str(e))
     if args.tree:
         if args.min_size is None:
             args.min_size = 16
@@ -243,13 +288,18 @@ def main(argv=None):
               f"{int((t['leaf_map'] == 0xFF).sum())} of {t['leaf_map'].size} 16x16 blocks uncovered")
         m.close()
         return 0
-    maps = run_maps(m, org, pred, sizes, args.poc, args.qp)
-    for s, r in maps.items():
+    if args.qp_list is not None:
+        sweeps = run_maps_sweep(m, org, pred, sizes, args.poc, args.qp_list)
+        maps = {(s, f"_qp{qp}"): r for s, per_qp in sweeps.items() for qp, r in per_qp.items()}
+    else:
+        maps = {(s, ""): r for s, r in run_maps(m, org, pred, sizes, args.poc, args.qp).items()}
+    for (s, tag), r in maps.items():
         for name in ("split", "confidence", "mask"):
-            np.save(f"{args.out}_{s}_{name}.npy", r[name])
+            np.save(f"{args.out}_{s}{tag}_{name}.npy", r[name])
         classes = pkg.decisions.HEAD_CLASSES[s][pkg.decisions.default_head(s)]
         hist = " ".join(f"{k}:{v}" for k, v in sorted(histogram(r["split"], classes).items()))
-        print(f"size {s}: {r['split'].size} CUs ({r['split'].shape[1]} x {r['split'].shape[0]})  split histogram  {hist}  mean confidence {float(r['confidence'].mean()):.4f}")
+        print(f"size {s}{tag.replace('_qp', ' qp ')}: {r['split'].size} CUs ({r['split'].shape[1]} x {r['split'].shape[0]})  split histogram  {hist}  "
+              f"mean confidence {float(r['confidence'].mean()):.4f}")
     m.close()
     return 0
 
