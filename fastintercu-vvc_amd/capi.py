@@ -34,7 +34,7 @@ EXPORTS = ["mlt_abi_version", "mlt_build_signature", "mlt_init", "mlt_num_device
            "mlt_predict_batch_device_candidates", "mlt_wait_candidates",
            "mlt_picture_create", "mlt_picture_upload", "mlt_picture_wrap_device", "mlt_picture_destroy", "mlt_predict_at", "mlt_grid_positions",
            "mlt_tree_max_nodes", "mlt_tree_roots", "mlt_predict_tree", "mlt_predict_trees",
-           "mlt_predict_batch_device_sweep", "mlt_predict_at_sweep"]
+           "mlt_predict_batch_device_sweep", "mlt_predict_at_sweep", "mlt_predict_tree_sweep"]
 SWEEP_MAX_QPS = 32  # MLT_SWEEP_MAX_QPS
 TREES_MAX_PICTURES = 256  # MLT_TREES_MAX_PICTURES
 TREE_BY_CANDIDATES = 0x1  # mlt_tree_config.flags: descend on cand_mask & descend_mask instead of on split_mode
@@ -167,6 +167,7 @@ def load_library():
     lib.mlt_tree_roots.argtypes = [i32, i32, i32, i32, vp, i32]
     lib.mlt_predict_tree.argtypes = [vp, vp, vp, C.POINTER(MltTreeConfig), vp, i32, C.POINTER(i32), vp, vp, i32, vp, vp]
     lib.mlt_predict_trees.argtypes = [vp, i32, C.POINTER(MltTreePicture), C.POINTER(MltTreeConfig), vp, i32, vp, vp, vp, i32, vp, vp]
+    lib.mlt_predict_tree_sweep.argtypes = [vp, vp, vp, C.POINTER(MltTreeConfig), vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp]
     lib.mlt_synchronize.argtypes = [vp]
     lib.mlt_set_stream.argtypes = [vp, vp]
     lib.mlt_alloc_pinned.restype = vp
@@ -601,6 +602,35 @@ class MltCnn:
             r = {"nodes": nodes[lo:hi].copy(), "first_node": lo}
             if "leaf_map" in out:
                 r["leaf_map"] = out["leaf_map"][p].copy()
+            for k in ("logits", "decisions", "candidates"):
+                if k in out:
+                    r[k] = out[k][lo:hi].copy()
+            res.append(r)
+        return res
+
+    def predict_tree_sweep(self, org_pic: Picture, pred_pic: Picture, poc: int, qps, top: int = 128, min_size: int = 16, descend: dict | None = None,
+                           by_candidates: bool = False, want=("leaf_map",)) -> list:
+        """The partition trees of ONE picture pair under every value of `qps` from one descent over the union of the trees (mlt_predict_tree_sweep); the other
+        arguments as predict_tree.
+        -> one dict per point, shaped like predict_trees' ("nodes", "first_node" and the wanted arrays) + "union_nodes": int32 [4], the nodes the network
+        evaluated per level from `top` down (the same array in every dict)."""
+        qps = np.ascontiguousarray(qps, np.int32).reshape(-1)
+        Q = qps.shape[0]
+        cfg = self._tree_config(top, min_size, descend, by_candidates, poc, 0)
+        w, h = org_pic.width, org_pic.height
+        cap = Q * tree_max_nodes(w, h, top, min_size)
+        nodes = np.zeros((max(cap, 1),), TREE_NODE_DTYPE)
+        first = np.zeros((Q + 1,), np.int32)
+        union = np.zeros((4,), np.int32)
+        out, ptr = self._tree_outputs(want, cap, (max(Q, 1), h // 16, w // 16))
+        self._check(self._lib.mlt_predict_tree_sweep(self._h, org_pic._h, pred_pic._h, C.byref(cfg), qps.ctypes.data, Q, nodes.ctypes.data, cap, first.ctypes.data,
+                                                     union.ctypes.data, ptr("leaf_map"), ptr("logits"), 15, ptr("decisions"), ptr("candidates")))
+        res = []
+        for q in range(Q):
+            lo, hi = int(first[q]), int(first[q + 1])
+            r = {"nodes": nodes[lo:hi].copy(), "first_node": lo, "union_nodes": union.copy()}
+            if "leaf_map" in out:
+                r["leaf_map"] = out["leaf_map"][q].copy()
             for k in ("logits", "decisions", "candidates"):
                 if k in out:
                     r[k] = out[k][lo:hi].copy()

@@ -258,6 +258,7 @@ struct HeadSweepArgs {
   long slab;
   const int32_t *fix_idx;
   uint32_t *mask;   // [rows]
+  const uint32_t *active;   // fast pass with the selection: mask[i] is ANDed with active[i] -- the points CU i takes part in (tree sweeps); NULL: all points
 };
 
 // ---- parity guard (fast arithmetic): device-side selection of the CUs that are re-evaluated with the exact arithmetic ----
@@ -382,6 +383,51 @@ struct TreesPackArgs {
   int n_pictures, n_levels, total;
   int lvl_start[MLT_TREES_LEVELS], n_logits[MLT_TREES_LEVELS];   // a level's logits are dense [lvl_n][n_logits] from row lvl_start of the MLT_TREES_ROW-float rows
 };
+// ---- tree sweeps (mlt_predict_tree_sweep): the UNION descent of one picture pair under n_qps points (mlt_tree_kernels.inc; the arena: mlt_layout.h TreeSweepArena).
+// A union node carries alive (bit q: part of tree q) and desc (bit q: descends under point q); its per-point records / logits / candidate records are slab-major:
+// element (q, i) of a level lies q * slab + i behind the level's element (0, 0).
+struct TreeSweepExpandArgs {
+  TreeNodeRec *nodes;          // the union's nodes (parent / first_child: union indices; split_mode / confidence / cand_mask stay unset), node_cap entries
+  int32_t *xy;                 // [node_cap][2]
+  uint32_t *alive, *desc;      // [node_cap]
+  int node_cap;
+  int lvl_start, lvl_n;        // the level just evaluated
+  int next_start, next_cap;    // where the next level starts and how many nodes it may hold
+  int size, lvl;               // as TreeExpandArgs (lvl = -1, lvl_n = 0: the opening launch)
+  const DecisionRec *dec;      // the level's element (0, 0) of each slab array
+  const CandRec *cand;         // NULL: the default policy's mask from the logits (TreeExpandArgs.cand)
+  const float *logits;
+  long slab;
+  int n_qps, n_logits, head_off, head_classes;
+  uint32_t descend_mask;
+  int by_candidates;
+  const int32_t *next_roots;   // the next level's border roots: alive under every point
+  int n_next_roots, root_flags;
+  int32_t *count;              // [1] out: n_next_roots + 4 x nodes descending under any point (NULL: not wanted)
+};
+struct TreeSweepRasterArgs {
+  const TreeNodeRec *nodes;
+  const uint32_t *alive, *desc;
+  const DecisionRec *dec;      // the level's element (0, 0)
+  long slab;
+  int lvl_start, lvl_n, blk_l, n_qps;
+  uint8_t *map;                // [n_qps][map_h][map_w]
+  size_t map_bytes;
+  int map_w, map_h;
+};
+// after the last level: idx[q][g] <- the index of union node g inside slice q (-1: not part of it), total[q] <- the slice's node count | the slices themselves
+struct TreeSweepPackArgs {
+  const TreeNodeRec *nodes; const uint32_t *alive, *desc; const DecisionRec *dec; const float *logits; const CandRec *cand;   // whole arena arrays
+  int32_t *idx, *total, *first_node, *union_nodes;
+  TreeNodeRec *o_nodes; float *o_logits; DecisionRec *o_dec; CandRec *o_cand;   // [out_cap]; NULL = not wanted
+  int n_qps, n_levels, node_cap, out_cap;
+  int lvl_start[MLT_TREES_LEVELS], lvl_n[MLT_TREES_LEVELS], lvl_cap[MLT_TREES_LEVELS];   // level l: union nodes [lvl_start, lvl_start + lvl_n), slab stride lvl_cap
+  int n_logits[MLT_TREES_LEVELS], head_off[MLT_TREES_LEVELS], head_classes[MLT_TREES_LEVELS], has_cand[MLT_TREES_LEVELS];
+};
+hipError_t mlt_launch_tree_expand_sweep(const TreeSweepExpandArgs &a, hipStream_t st);
+hipError_t mlt_launch_tree_sweep_raster(const TreeSweepRasterArgs &a, hipStream_t st);
+hipError_t mlt_launch_tree_sweep_rank(const TreeSweepPackArgs &a, hipStream_t st);
+hipError_t mlt_launch_tree_sweep_pack(const TreeSweepPackArgs &a, hipStream_t st);
 hipError_t mlt_launch_tree_expand(const TreeExpandArgs &a, hipStream_t st);
 hipError_t mlt_launch_tree_raster(const TreeRasterArgs &a, hipStream_t st);
 hipError_t mlt_launch_picture_gather_multi(const PictureGatherMultiArgs &a, hipStream_t st);

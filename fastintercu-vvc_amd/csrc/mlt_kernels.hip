@@ -281,7 +281,7 @@ template <int Q, class ACC = float16v> __device__ __forceinline__ half4 act_quad
 #include "mlt_layer1_kernel.inc"  // layer1_stream_kernel
 #include "mlt_tail_kernels.inc"   // heads_kernel, flat_stat / guard kernels
 #include "mlt_picture_kernels.inc"  // picture_gather_kernel, picture_gather_multi_kernel
-#include "mlt_tree_kernels.inc"  // tree_expand_kernel, tree_raster_kernel, tree_pack_kernel
+#include "mlt_tree_kernels.inc"  // tree_expand_kernel, tree_raster_kernel, tree_pack_kernel; tree sweeps: tree_expand_sweep_kernel, tree_sweep_raster / _rank / _pack_kernel
 
 // ---------------------------------------------------------------------------------------------
 // launchers
@@ -894,5 +894,37 @@ hipError_t mlt_launch_trees_pack(const TreesPackArgs &a, hipStream_t st) {
   if (a.total <= 0) return hipSuccess;
   const int want = (a.total + 255) / 256;
   hipLaunchKernelGGL(tree_pack_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// tree sweeps -- ONE workgroup, as mlt_launch_tree_expand
+hipError_t mlt_launch_tree_expand_sweep(const TreeSweepExpandArgs &a, hipStream_t st) {
+  if (a.n_qps < 1 || a.n_qps > MLT_SWEEP_MAX_QPS_K) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tree_expand_sweep_kernel, dim3(1), dim3(MLT_TREE_TILE), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t mlt_launch_tree_sweep_raster(const TreeSweepRasterArgs &a, hipStream_t st) {
+  const size_t items = (size_t)a.lvl_n << (2 * a.blk_l);
+  if (!items) return hipSuccess;
+  const size_t want = (items + 255) / 256;
+  hipLaunchKernelGGL(tree_sweep_raster_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// one workgroup per point
+hipError_t mlt_launch_tree_sweep_rank(const TreeSweepPackArgs &a, hipStream_t st) {
+  if (a.n_qps < 1 || a.n_qps > MLT_SWEEP_MAX_QPS_K) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tree_sweep_rank_kernel, dim3((unsigned)a.n_qps), dim3(MLT_TREE_TILE), 0, st, a);
+  return hipGetLastError();
+}
+
+// flat grid-stride launch over (point, union node); at least workgroup 0, which writes first_node[] and union_nodes[]
+hipError_t mlt_launch_tree_sweep_pack(const TreeSweepPackArgs &a, hipStream_t st) {
+  if (a.n_qps < 1 || a.n_qps > MLT_SWEEP_MAX_QPS_K) return hipErrorInvalidValue;
+  size_t items = 0;
+  for (int l = 0; l < a.n_levels; ++l) items += (size_t)a.lvl_n[l];
+  const size_t want = (items * (size_t)a.n_qps + 255) / 256;
+  hipLaunchKernelGGL(tree_sweep_pack_kernel, dim3((unsigned)(want < 1 ? 1 : want < 2048 ? want : 2048)), dim3(256), 0, st, a);
   return hipGetLastError();
 }

@@ -4,7 +4,7 @@
 //   mlt_calibrate.cpp  model upload, calibration sets and session, the loader, mlt_load_weights / mlt_calibrate / mlt_arithmetic
 //   mlt_api.cpp        init / shutdown / stream, the predict entry points, deferred prediction, confidence gate, profile
 //   mlt_pictures.cpp   device-resident pictures: create / upload / wrap / destroy, mlt_predict_at, mlt_grid_positions
-//   mlt_tree.cpp       partition trees of a picture: mlt_predict_tree, mlt_predict_trees, mlt_tree_roots, mlt_tree_max_nodes
+//   mlt_tree.cpp       partition trees of a picture: mlt_predict_tree, mlt_predict_trees, mlt_predict_tree_sweep, mlt_tree_roots, mlt_tree_max_nodes
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -296,7 +296,7 @@ struct mlt_ctx {
   GrowBuf sweep_guard_dev;              // QP sweeps: one slot of sweep_guard_lay (zero when allocated), its counter phase; the count lands in guard_host[2]
   Lay::SweepGuardLay sweep_guard_lay;
   int sweep_phase = 0;
-  // mlt_predict_tree's / mlt_predict_trees' device arena (Lay::TreeArena) and its pinned count
+  // mlt_predict_tree's / mlt_predict_trees' device arena (Lay::TreeArena) or mlt_predict_tree_sweep's (Lay::TreeSweepArena), and the pinned count
   GrowBuf tree_dev;
   int32_t *tree_host = nullptr;
   std::vector<mlt_picture *> pictures;  // every picture created on / wrapped for this context (mlt_pictures.cpp); what is left is released by mlt_shutdown
@@ -371,6 +371,7 @@ struct SweepPart {
   long slab = 0;
   const int32_t *idx = nullptr;
   uint32_t *mask = nullptr;
+  const uint32_t *active = nullptr;   // per CU, the points it takes part in: a CU is flagged only under those (tree sweeps); NULL: all points
 };
 
 // what a pass reads and writes per CU (device memory; any of the outputs may be NULL)

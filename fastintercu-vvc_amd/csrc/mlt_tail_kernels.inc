@@ -355,7 +355,7 @@ __global__ __launch_bounds__(256) void sweep_heads_kernel(const HeadSweepArgs sa
         }
       }
     }
-    const uint32_t mask = (uint32_t)__ballot(s) & all;
+    const uint32_t mask = (uint32_t)__ballot(s) & all & (sa.active ? sa.active[n] : 0xFFFFFFFFu);   // (tree sweeps: only the points whose tree holds this CU)
     if (tid == 0 && select) {
       sa.mask[n] = mask;
       if (n == 0) a.g_next[0] = 0;   // re-arm the slot's other counter

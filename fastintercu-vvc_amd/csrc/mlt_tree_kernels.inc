@@ -1,5 +1,5 @@
 // mlt_tree_kernels.inc -- partition trees of pictures (include/mltcnn.h: mlt_predict_tree, mlt_predict_trees): the quadtree descent between two network levels, on
-// the device.  Included by mlt_kernels.hip.
+// the device.  Included by mlt_kernels.hip.  The union descent of mlt_predict_tree_sweep has kernels of its own at the end of the file.
 //
 // tree_expand_kernel   one level's evaluated nodes -> their split_mode / confidence / cand_mask / first_child, the next level's nodes (per picture its border roots,
 //                      then four children per descending parent, in the parents' order) with their positions and picture indices, the next level's node count
@@ -178,5 +178,196 @@ __global__ __launch_bounds__(256) void tree_pack_kernel(const TreesPackArgs a) {
     }
     if (a.o_dec) a.o_dec[dst] = a.dec[g];
     if (a.o_cand) a.o_cand[dst] = a.cand[g];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Tree sweeps (mlt_predict_tree_sweep): ONE descent over the UNION of the trees of a picture pair under n_qps points.
+//
+// tree_expand_sweep_kernel   one level's union nodes -> desc (bit q: the node descends under point q -- tree_expand_kernel's rule on slab q's records, for the
+//                            points the node is alive under), the next level: its border roots (alive under every point), then four children per node with
+//                            desc != 0 (alive = desc), in the parents' order -- the same ordered tiled scan -- and the next level's count.
+// tree_sweep_raster_kernel   one level's leaves into the map of every point: a leaf under q is alive under q and does not descend under q.
+// tree_sweep_rank_kernel     after the last level, one workgroup per point: an ordered scan of "alive under q" over the levels -> a node's index inside slice q.
+//                            Restricted to the nodes alive under q the union's level order IS the single descent's order (roots first, then children in their
+//                            parents' order, and a parent alive under q keeps its rank among those), so the scan's running count is that index.
+// tree_sweep_pack_kernel     one work item per (point, union node): the node's record of slice q -- parent / first_child through idx, split_mode / confidence /
+//                            cand_mask from slab q -- with its logits row and records; workgroup 0 also writes first_node[] and union_nodes[].
+// Plain vector stores, one writer per output word, no atomics.
+// ---------------------------------------------------------------------------------------------
+
+// (selected, not indexed: a dynamically indexed argument array would be copied to scratch or LDS)
+#define MLT_TREE_SEL(v, l) ((l) == 0 ? (v)[0] : (l) == 1 ? (v)[1] : (l) == 2 ? (v)[2] : (v)[3])
+
+// cand_mask of one evaluated element: the candidate record's, or the default policy's without one -- the argmax alone, every class when a logit of the decision
+// head is NaN (tree_expand_kernel's rule)
+__device__ __forceinline__ uint32_t tree_point_cmask(const DecisionRec &d, const CandRec *cand, const float *logits, size_t e, int n_logits, int head_off, int head_classes) {
+  if (cand) return cand[e].mask;
+  const float *l = logits + e * (size_t)n_logits + head_off;
+  bool nan = false;
+  for (int k = 0; k < head_classes; ++k) nan = nan || (l[k] != l[k]);
+  return nan ? (1u << head_classes) - 1u : 1u << d.raw_mode;
+}
+
+__device__ __forceinline__ void tree_sweep_write_node(const TreeSweepExpandArgs &a, int idx, int x, int y, int size, int depth, int flags, int parent, uint32_t alive) {
+  if (idx < 0 || idx >= a.node_cap) return;   // (the host sizes every level for a union that descends everywhere: never taken)
+  TreeNodeRec r;
+  r.x = x; r.y = y; r.size = (int16_t)size; r.depth = (int8_t)depth; r.flags = (uint8_t)flags;
+  r.parent = parent; r.first_child = -1; r.split_mode = -1; r.confidence = 0.f; r.cand_mask = 0u;
+  a.nodes[idx] = r;
+  a.xy[2 * (size_t)idx] = x;
+  a.xy[2 * (size_t)idx + 1] = y;
+  a.alive[idx] = alive;
+  a.desc[idx] = 0u;
+}
+
+__global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_sweep_kernel(const TreeSweepExpandArgs a) {
+  __shared__ int wave_total[MLT_TREE_TILE / 64];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, Q = a.n_qps, nr = a.n_next_roots, child_size = a.size >> 1;
+  const uint32_t all = Q >= 32 ? 0xFFFFFFFFu : (1u << Q) - 1u;
+  int base = 0;   // descending nodes of the tiles before this one (the same value in every thread)
+  for (int t0 = 0; t0 < a.lvl_n; t0 += MLT_TREE_TILE) {
+    const int i = t0 + tid;
+    const bool in = i < a.lvl_n;
+    const int node = a.lvl_start + (in ? i : 0);
+    uint32_t dm = 0u;
+    if (in && a.descend_mask) {
+      const uint32_t al = a.alive[node] & all;
+      for (int q = 0; q < Q; ++q) {
+        if (!((al >> q) & 1u)) continue;
+        const size_t e = (size_t)q * (size_t)a.slab + (size_t)i;
+        const DecisionRec &d = a.dec[e];
+        const int32_t split = d.split_mode;
+        bool ds;
+        if (a.by_candidates) ds = (tree_point_cmask(d, a.cand, a.logits, e, a.n_logits, a.head_off, a.head_classes) & a.descend_mask) != 0u;
+        else ds = split >= 0 && ((a.descend_mask >> split) & 1u) != 0u;
+        if (ds) dm |= 1u << q;
+      }
+    }
+    const bool desc = dm != 0u;
+    const unsigned long long b = __ballot(desc);
+    const int before = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_total[wave] = __popcll(b);
+    __syncthreads();
+    int woff = 0, total = 0;
+    for (int w = 0; w < MLT_TREE_TILE / 64; ++w) {
+      const int s = wave_total[w];
+      woff += w < wave ? s : 0;
+      total += s;
+    }
+    __syncthreads();   // (the next tile overwrites wave_total)
+    if (in) {
+      int first_child = -1;
+      if (desc) {
+        const int k = nr + 4 * (base + woff + before);
+        if (k + 3 < a.next_cap && a.next_start + k + 3 < a.node_cap) {
+          const int fc = first_child = a.next_start + k;
+          const int x = a.xy[2 * (size_t)node], y = a.xy[2 * (size_t)node + 1];
+          for (int j = 0; j < 4; ++j) tree_sweep_write_node(a, fc + j, x + (j & 1) * child_size, y + (j >> 1) * child_size, child_size, a.lvl + 1, 0, node, dm);
+        }
+      }
+      a.nodes[node].first_child = first_child;
+      a.desc[node] = first_child >= 0 ? dm : 0u;
+    }
+    base += total;
+  }
+  if (!a.next_roots && !a.count) return;   // the last level
+  // the next level opens with the border roots (host-known, raster order): part of every tree
+  for (int r = tid; r < nr && r < a.next_cap; r += MLT_TREE_TILE)
+    tree_sweep_write_node(a, a.next_start + r, a.next_roots[2 * r], a.next_roots[2 * r + 1], child_size, a.lvl + 1, a.root_flags, -1, all);
+  if (tid == 0 && a.count) a.count[0] = nr + 4 * base;
+}
+
+// One work item per 16 x 16 block of every union node of the level; under a point the leaves are disjoint, and every point has a map of its own.
+__global__ __launch_bounds__(256) void tree_sweep_raster_kernel(const TreeSweepRasterArgs a) {
+  const size_t total = (size_t)a.lvl_n << (2 * a.blk_l), step = (size_t)gridDim.x * 256;
+  const uint32_t all = a.n_qps >= 32 ? 0xFFFFFFFFu : (1u << a.n_qps) - 1u;
+  for (size_t it = (size_t)blockIdx.x * 256 + threadIdx.x; it < total; it += step) {
+    const int i = (int)(it >> (2 * a.blk_l)), b = (int)(it & ((1u << (2 * a.blk_l)) - 1u));
+    const int node = a.lvl_start + i;
+    const uint32_t leaf = a.alive[node] & ~a.desc[node] & all;
+    if (!leaf) continue;
+    const TreeNodeRec &r = a.nodes[node];
+    const int mx = (r.x >> 4) + (b & ((1 << a.blk_l) - 1)), my = (r.y >> 4) + (b >> a.blk_l);
+    if (mx < 0 || my < 0 || mx >= a.map_w || my >= a.map_h) continue;   // (a node is a complete CU of the picture: never taken)
+    for (int q = 0; q < a.n_qps; ++q)
+      if ((leaf >> q) & 1u)
+        a.map[(size_t)q * a.map_bytes + (size_t)my * a.map_w + mx] = (uint8_t)(a.blk_l | ((a.dec[(size_t)q * (size_t)a.slab + (size_t)i].split_mode + 1) << 4));
+  }
+}
+
+// Workgroup q: the ordered scan of bit q of alive over every level's nodes, level after level (tree_expand_kernel's tile scan with the base carried on).
+__global__ __launch_bounds__(MLT_TREE_TILE) void tree_sweep_rank_kernel(const TreeSweepPackArgs a) {
+  __shared__ int wave_total[MLT_TREE_TILE / 64];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, q = (int)blockIdx.x;
+  if (q >= a.n_qps) return;
+  int32_t *idx = a.idx + (size_t)q * (size_t)a.node_cap;
+  int base = 0;
+  for (int l = 0; l < a.n_levels && l < MLT_TREES_LEVELS; ++l) {
+    const int start = MLT_TREE_SEL(a.lvl_start, l), n = MLT_TREE_SEL(a.lvl_n, l);
+    for (int t0 = 0; t0 < n; t0 += MLT_TREE_TILE) {
+      const int i = t0 + tid, node = start + i;
+      const bool in = i < n && node < a.node_cap;
+      const bool on = in && ((a.alive[node] >> q) & 1u) != 0u;
+      const unsigned long long b = __ballot(on);
+      const int before = __popcll(b & ((1ull << lane) - 1ull));
+      if (lane == 0) wave_total[wave] = __popcll(b);
+      __syncthreads();
+      int woff = 0, total = 0;
+      for (int w = 0; w < MLT_TREE_TILE / 64; ++w) {
+        const int s = wave_total[w];
+        woff += w < wave ? s : 0;
+        total += s;
+      }
+      __syncthreads();
+      if (in) idx[node] = on ? base + woff + before : -1;
+      base += total;
+    }
+  }
+  if (tid == 0) a.total[q] = base;
+}
+
+__global__ __launch_bounds__(256) void tree_sweep_pack_kernel(const TreeSweepPackArgs a) {
+  __shared__ int first[MLT_SWEEP_MAX_QPS_K + 1];
+  const int tid = (int)threadIdx.x, Q = a.n_qps;
+  if (tid <= Q && tid <= MLT_SWEEP_MAX_QPS_K) {
+    int f = 0;
+    for (int q = 0; q < tid; ++q) f += a.total[q];
+    first[tid] = f;
+    if (blockIdx.x == 0) a.first_node[tid] = f;
+  }
+  if (blockIdx.x == 0 && tid < MLT_TREES_LEVELS) a.union_nodes[tid] = tid < a.n_levels ? MLT_TREE_SEL(a.lvl_n, tid) : 0;
+  __syncthreads();
+  int un = 0;   // union nodes over all levels
+  for (int l = 0; l < a.n_levels && l < MLT_TREES_LEVELS; ++l) un += MLT_TREE_SEL(a.lvl_n, l);
+  const size_t items = (size_t)Q * (size_t)un, step = (size_t)gridDim.x * 256;
+  for (size_t it = (size_t)blockIdx.x * 256 + tid; it < items; it += step) {
+    const int q = (int)(it / (size_t)un);
+    int u = (int)(it - (size_t)q * (size_t)un), l = 0;
+    while (l + 1 < a.n_levels && u >= MLT_TREE_SEL(a.lvl_n, l)) { u -= MLT_TREE_SEL(a.lvl_n, l); ++l; }
+    const int start = MLT_TREE_SEL(a.lvl_start, l), g = start + u;
+    if (g >= a.node_cap || !((a.alive[g] >> q) & 1u)) continue;
+    const int32_t *idx = a.idx + (size_t)q * (size_t)a.node_cap;
+    const int li = idx[g], dst = first[q] + li;
+    if (li < 0 || (unsigned)dst >= (unsigned)a.out_cap) continue;   // (never taken)
+    const int cap = MLT_TREE_SEL(a.lvl_cap, l), nl = MLT_TREE_SEL(a.n_logits, l);
+    const size_t slab0 = (size_t)Q * (size_t)start, e = slab0 + (size_t)q * (size_t)cap + (size_t)u;   // element (l, q, u): level l starts at node off[l] = start
+    TreeNodeRec r = a.nodes[g];
+    r.parent = r.parent >= 0 && r.parent < a.node_cap ? idx[r.parent] : -1;
+    r.first_child = ((a.desc[g] >> q) & 1u) && r.first_child >= 0 && r.first_child < a.node_cap ? idx[r.first_child] : -1;
+    const DecisionRec d = a.dec[e];
+    // a level's logits are dense rows of nl floats from the level's first reserved row; its candidate records are read only where the heads wrote them
+    const float *lg = a.logits ? a.logits + slab0 * MLT_TREES_ROW : nullptr;
+    const size_t le = (size_t)q * (size_t)cap + (size_t)u;
+    r.split_mode = d.split_mode; r.confidence = d.confidence;
+    r.cand_mask = tree_point_cmask(d, MLT_TREE_SEL(a.has_cand, l) ? a.cand + slab0 : nullptr, lg, le, nl, MLT_TREE_SEL(a.head_off, l), MLT_TREE_SEL(a.head_classes, l));
+    a.o_nodes[dst] = r;
+    if (a.o_logits) {
+      const float *src = lg + le * (size_t)nl;
+      float *o = a.o_logits + (size_t)dst * MLT_TREES_ROW;
+      for (int k = 0; k < MLT_TREES_ROW; ++k) o[k] = k < nl ? src[k] : 0.f;
+    }
+    if (a.o_dec) a.o_dec[dst] = d;
+    if (a.o_cand) a.o_cand[dst] = a.cand[e];
   }
 }

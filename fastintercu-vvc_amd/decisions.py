@@ -198,3 +198,82 @@ def build_tree(width: int, height: int, top: int, min_size: int, descend_mask, d
             for dx in range(size // 16):
                 leaf_map[lv["y"] // 16 + dy, lv["x"] // 16 + dx] = val
     return nodes, leaf_map
+
+
+def build_tree_sweep(width: int, height: int, top: int, min_size: int, descend_mask, decide, n_points: int, by_candidates: bool = False):
+    """The union descent of mlt_predict_tree_sweep restated on the host: the trees of one picture under n_points points from ONE descent over their union.
+    decide(size, xy) -> (split_mode, confidence, cand_mask), each [n_points, n]: the records of EVERY point for the [n, 2] position list -- called once per
+    level with at least one union node.  A union node carries `alive` (bit q: part of tree q) and `desc` (bit q: it descends under point q, build_tree's rule on
+    point q's record); it descends in the union iff desc != 0 and its four children are alive under desc; roots are alive under every point.  Tree q is then
+    the ordered compaction of every union level by bit q, parent / first_child renumbered inside the slice.
+    -> ([(nodes TREE_NODE_DTYPE [n_q], leaf_map uint8 [height // 16, width // 16]) per point], union_nodes int32 [4]: union nodes per level from `top` down)."""
+    assert top in TREE_SIZES and min_size in TREE_SIZES and min_size <= top and 1 <= n_points <= 32
+    Q = n_points
+    levels = [s for s in TREE_SIZES if min_size <= s <= top]
+    everyone = np.uint32((1 << Q) - 1)   # (Python integers: no shift by 32)
+    union = []           # per level: x, y, flags, parent (index in the previous level), alive, desc, first (index in the next level of the first child), records
+    prev = None
+    for size in levels:
+        roots = tree_roots(width, height, top, size)
+        x, y = roots[:, 0].astype(np.int32), roots[:, 1].astype(np.int32)
+        parent = np.full(len(roots), -1, np.int64)
+        alive = np.full(len(roots), everyone, np.uint32)
+        flags = np.full(len(roots), 0 if size == top else 1, np.uint8)
+        if prev is not None:
+            par = np.flatnonzero(prev["desc"] != 0)
+            prev["first"][par] = len(roots) + 4 * np.arange(len(par))
+            j = np.tile(np.arange(4), len(par))   # z-order: TL, TR, BL, BR
+            x = np.concatenate([x, np.repeat(prev["x"][par], 4) + (j & 1) * size]).astype(np.int32)
+            y = np.concatenate([y, np.repeat(prev["y"][par], 4) + (j >> 1) * size]).astype(np.int32)
+            parent = np.concatenate([parent, np.repeat(par, 4)])
+            alive = np.concatenate([alive, np.repeat(prev["desc"][par], 4)]).astype(np.uint32)
+            flags = np.concatenate([flags, np.zeros(4 * len(par), np.uint8)])
+        n = len(x)
+        lvl = {"size": size, "x": x, "y": y, "flags": flags, "parent": parent, "alive": alive, "desc": np.zeros(n, np.uint32), "first": np.full(n, -1, np.int64)}
+        if n:
+            split, conf, cmask = (np.asarray(a).reshape(Q, n) for a in decide(size, np.stack([x, y], axis=1).astype(np.int32)))
+            lvl["split"], lvl["conf"], lvl["cmask"] = split.astype(np.int32), conf.astype(np.float32), cmask.astype(np.uint32)
+            if size > min_size:
+                mask = int((descend_mask or {}).get(size, 0)) or 2
+                for q in range(Q):
+                    if by_candidates:
+                        d = (lvl["cmask"][q] & np.uint32(mask)) != 0
+                    else:
+                        sm = lvl["split"][q].astype(np.int64)
+                        d = (sm >= 0) & (((mask >> np.clip(sm, 0, 31)) & 1) != 0)
+                    d &= ((alive >> np.uint32(q)) & np.uint32(1)) != 0
+                    lvl["desc"] |= (d.astype(np.uint32) << np.uint32(q)).astype(np.uint32)
+        union.append(lvl)
+        prev = lvl
+    counts = np.zeros(4, np.int32)
+    counts[:len(union)] = [len(l["x"]) for l in union]
+    trees = []
+    for q in range(Q):
+        bit = lambda m: ((m >> np.uint32(q)) & np.uint32(1)) != 0
+        idx, base = [], 0     # per level: a union node's index inside slice q (-1: not part of it)
+        for lvl in union:
+            on = bit(lvl["alive"])
+            idx.append(np.where(on, base + np.cumsum(on) - 1, -1))
+            base += int(on.sum())
+        nodes = np.zeros(base, TREE_NODE_DTYPE)
+        for l, lvl in enumerate(union):
+            on = np.flatnonzero(bit(lvl["alive"]))
+            if not len(on):
+                continue
+            r = nodes[idx[l][on]]
+            r["x"], r["y"], r["size"], r["depth"], r["flags"] = lvl["x"][on], lvl["y"][on], lvl["size"], l, lvl["flags"][on]
+            p = lvl["parent"][on]
+            r["parent"] = np.where(p >= 0, idx[l - 1][np.maximum(p, 0)], -1) if l else -1
+            down = bit(lvl["desc"][on])
+            r["first_child"] = np.where(down, idx[l + 1][np.maximum(lvl["first"][on], 0)], -1) if l + 1 < len(union) else -1
+            r["split_mode"], r["confidence"], r["cand_mask"] = lvl["split"][q][on], lvl["conf"][q][on], lvl["cmask"][q][on]
+            nodes[idx[l][on]] = r
+        leaf_map = np.full((height // 16, width // 16), 0xFF, np.uint8)
+        for size in levels:
+            lv = nodes[(nodes["first_child"] < 0) & (nodes["size"] == size)]
+            val = ((size.bit_length() - 5) | ((lv["split_mode"] + 1) << 4)).astype(np.uint8)
+            for dy in range(size // 16):
+                for dx in range(size // 16):
+                    leaf_map[lv["y"] // 16 + dy, lv["x"] // 16 + dx] = val
+        trees.append((nodes, leaf_map))
+    return trees, counts

@@ -301,6 +301,43 @@ class SplitPredictor {
     return t;
   }
 
+  // The partition trees of ONE picture pair under several QPs from one call (include/mltcnn.h: mlt_predict_tree_sweep): one descent over the union of the trees,
+  // the conv trunk once per union node, the heads once per QP.  Tree q is what predictTree returns with qp = qps[q].  unionNodesOpt: [4], the nodes the network
+  // evaluated per level from topSize down.  On failure every tree is EMPTY (the vector still has one entry per QP).
+  std::vector<PartitionTree> predictTreeSweep(const mlt_picture *org, const mlt_picture *pred, int width, int height, int poc, const std::vector<int32_t> &qps,
+                                              int topSize = 128, int minSize = 16, bool byCandidates = false, int32_t *unionNodesOpt = nullptr) {
+    Timer tm(this, 0, 0);
+    const int Q = (int)qps.size(), per = mlt_tree_max_nodes(width, height, topSize, minSize);
+    const long long cap = (long long)Q * per;
+    std::vector<PartitionTree> trees((size_t)Q);
+    mlt_tree_config cfg{};
+    cfg.struct_size = (uint32_t)sizeof cfg;
+    cfg.top_size = topSize; cfg.min_size = minSize; cfg.poc = poc;
+    cfg.flags = byCandidates ? MLT_TREE_BY_CANDIDATES : 0u;
+    const int mapW = width / 16, mapH = height / 16;
+    const size_t mapBytes = (size_t)mapW * (size_t)mapH;
+    std::vector<mlt_tree_node> nodes;
+    std::vector<uint8_t> maps;
+    std::vector<int32_t> first((size_t)Q + 1, 0);
+    const bool sized = Q >= 1 && Q <= MLT_SWEEP_MAX_QPS && per > 0 && cap <= 0x7fffffff;
+    if (sized) { nodes.resize((size_t)cap); maps.assign((size_t)Q * mapBytes, (uint8_t)0xFF); }
+    if (!m_ctx || !sized || mlt_predict_tree_sweep(m_ctx, org, pred, &cfg, qps.data(), Q, nodes.data(), (int)cap, first.data(), unionNodesOpt, maps.data(), nullptr, 0,
+                                                   nullptr, nullptr) != MLT_OK) {
+      std::fprintf(stderr, "error\n");  // EncCu.cpp:925
+      ++m_failed;
+      return trees;
+    }
+    for (int q = 0; q < Q; ++q) {
+      PartitionTree &t = trees[(size_t)q];
+      t.nodes.assign(nodes.begin() + first[(size_t)q], nodes.begin() + first[(size_t)q + 1]);
+      t.leafMap.assign(maps.begin() + (long)((size_t)q * mapBytes), maps.begin() + (long)(((size_t)q + 1) * mapBytes));
+      t.mapW = mapW; t.mapH = mapH;
+      for (const mlt_tree_node &nd : t.nodes)
+        if (nd.split_mode < 0) ++m_gated;
+    }
+    return trees;
+  }
+
   // The class indices a candidate record keeps, most probable first (classes[] holds up to 8); returns how many.
   static int keptClasses(const mlt_candidates &c, int classes[8]) {
     int n = 0;

@@ -368,7 +368,7 @@ int mlt_predict_at(mlt_ctx *ctx, int size, const mlt_picture *org, const mlt_pic
  * size that is not loaded.  n == 0 returns MLT_OK.
  * Chunked by the context's pass size like the twins; the device entry blocks once per chunk for the guards' 4-byte count, the picture entry is synchronous and, on a
  * multi-device context, sharded (every device writes its range of every slab).  A sweep call with candidate records does NOT make deferred batches carry candidate
- * records.  Not there: a tree sweep, host-dense, single-CU and deferred forms, a sweep over poc. */
+ * records.  Partition trees under several QPs: mlt_predict_tree_sweep below.  Not there: host-dense, single-CU and deferred forms, a sweep over poc. */
 #define MLT_SWEEP_MAX_QPS 32
 int mlt_predict_batch_device_sweep(mlt_ctx *ctx, int n, int size, const void *d_org, const void *d_pred, const void *d_poc, const int32_t *qps /* HOST */, int n_qps,
                                    void *d_split_opt, void *d_logits_opt, void *d_decisions_opt, void *d_candidates_opt);
@@ -482,6 +482,37 @@ int mlt_predict_trees(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture *pics
                       mlt_tree_node *nodes, int node_cap, int32_t *first_node /* [n_pictures + 1] */,
                       uint8_t *leaf_maps_opt /* [n_pictures][height/16][width/16] */,
                       float *logits_opt, int logit_stride, mlt_decision *dec_opt, mlt_candidates *cand_opt);
+
+/* ---- Partition trees of ONE picture pair under SEVERAL QPs in one call (new export; MLT_ABI_VERSION stays 4) ----
+ * The partition tree of a frame at QP 22 / 27 / 32 / 37: poc and qp enter the network in the heads only, so the conv trunk of a node is the same under every
+ * point -- but the descents diverge per QP, and not as nested sets.  The call runs ONE descent over the UNION of the points' trees: every node that exists under
+ * any point is evaluated once (one gather, one trunk pass, the heads under every point: the QP sweep's kernel), and one tree per point is carved out of the union.
+ *
+ * POINTS    qps[0 .. n_qps) is a HOST array, 1 <= n_qps <= MLT_SWEEP_MAX_QPS, any values in any order, duplicates and negative values included.  cfg->poc is the
+ *           picture's poc; cfg->qp is NOT read.
+ * RESULT    tree q is nodes[first_node[q] .. first_node[q + 1]); first_node[n_qps] is the total node count.  The slice is BYTE FOR BYTE what mlt_predict_tree
+ *           returns for the pair with cfg.qp = qps[q] -- node order, parent / first_child (indices inside the slice), split_mode, confidence, cand_mask -- that is,
+ *           slice q of mlt_predict_trees over n_qps entries {org, pred, cfg->poc, qps[q]}.  Leaf map q (leaf_maps_opt + q * (height / 16) * (width / 16)), the
+ *           decision and the candidate records (one per node, at the node's index) are that call's.  The output format is mlt_predict_trees' throughout.
+ * LOGITS    as mlt_predict_trees: node i at logits_opt + i * logit_stride, the WHOLE 15-float row written, zeros behind mlt_num_logits(size).
+ * UNION     union_nodes_opt[l], l = 0 at top_size: the number of distinct nodes of that level on which the network ran -- the distinct (x, y) among the nodes of
+ *           that size over all slices; 0 for the levels below min_size.
+ * GUARDS    confidence gate, candidate policy, the three guards and MLT_TREE_BY_CANDIDATES act per point exactly as in mlt_predict_tree.  A node is re-evaluated
+ *           with the exact arithmetic iff it is flagged under at least one point whose tree contains it, and the exact results replace the fast ones in those
+ *           slabs only.  guard_reruns (mlt_arithmetic) grows by the number of distinct nodes re-evaluated: at least the maximum and at most the sum of what the
+ *           n_qps single calls add.
+ * ERRORS    everything is checked before anything is enqueued and on any error every output stays untouched.  MLT_ERR_ARG: cfg, qps, nodes or first_node NULL;
+ *           n_qps outside 1 .. MLT_SWEEP_MAX_QPS; everything mlt_predict_tree checks (struct_size, sizes, masks, flags, logit_stride < 15 with logits_opt, a
+ *           picture NULL, of another context or of another geometry); node_cap < n_qps * mlt_tree_max_nodes(width, height, top_size, min_size).
+ *           MLT_ERR_SIZE_DISABLED: a size top..min is not loaded.  MLT_ERR_NOMEM: the device arena cannot be grown.  NULL ctx: MLT_ERR_ARG.
+ * All arrays are HOST memory.  Synchronous.  On a multi-device context the call runs on devices[0] with a one-device context's bytes.
+ * Not there: several pictures times several QPs in one call, a sweep over poc, an asynchronous form. */
+int mlt_predict_tree_sweep(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pred, const mlt_tree_config *cfg,
+                           const int32_t *qps /* HOST */, int n_qps,
+                           mlt_tree_node *nodes, int node_cap, int32_t *first_node /* [n_qps + 1] */,
+                           int32_t *union_nodes_opt /* [4]: nodes the network evaluated per level top.., 0 for levels below min_size */,
+                           uint8_t *leaf_maps_opt /* [n_qps][height/16][width/16] */,
+                           float *logits_opt, int logit_stride, mlt_decision *dec_opt, mlt_candidates *cand_opt);
 
 int mlt_synchronize(mlt_ctx *ctx);
 

@@ -17,8 +17,12 @@ children, down to S (default 16); loads every size 128 .. S, writes `<out>_tree_
 (MltCnn.predict_trees: one network pass per level over the nodes of all frames); --poc is the first frame's POC, frame f takes --poc + f.  Writes
 `<out>_f<f>_tree_nodes.npy` and `<out>_f<f>_leafmap.npy` per frame.
 
+--tree --tree-qps 22,27,32,37: the trees of ONE frame under several QPs from ONE call (MltCnn.predict_tree_sweep: one descent over the union of the trees, the
+network once per union node, the heads once per QP); --qp is not consulted and --frames does not go with it.  Writes `<out>_qp<QP>_tree_nodes.npy` and
+`<out>_qp<QP>_leafmap.npy` per QP and prints the nodes per level per QP and of the union.
+
 --qps 22,27,32,37 (without --tree): one map set PER QP from ONE sweep call per size (MltCnn.predict_at_sweep: the network runs once, the heads once per QP),
-written as `<out>_<S>_qp<QP>_split.npy` etc.; --qp is not consulted.  Combined with --tree it is refused: the descents diverge per QP (no tree sweep).
+written as `<out>_<S>_qp<QP>_split.npy` etc.; --qp is not consulted.  Combined with --tree it is refused: trees under several QPs are --tree-qps.
 
 File reading and grid logic (read_picture, grid, to_map, histogram) need neither a device nor the library; run_maps needs the MI355X."""
 import argparse
@@ -200,6 +204,14 @@ def run_trees(m, org: np.ndarray, pred: np.ndarray, poc: int, qp: int, min_size:
         return m.predict_trees(pics, [poc + f for f in range(len(pics))], qp, top=128, min_size=min_size, want=("leaf_map",))
 
 
+def run_tree_sweep(m, org: np.ndarray, pred: np.ndarray, poc: int, qps, min_size: int = 16) -> list:
+    """m: an MltCnn with tree_sizes(min_size) loaded -> one {"nodes", "leaf_map", "first_node", "union_nodes"} per QP of `qps`, all from ONE call
+    (MltCnn.predict_tree_sweep)."""
+    assert org.ndim == 2
+    with uploaded(m, org, pred) as pics:
+        return m.predict_tree_sweep(pics[0][0], pics[0][1], poc, qps, top=128, min_size=min_size, want=("leaf_map",))
+
+
 def save_tree(prefix: str, t: dict) -> None:
     np.save(f"{prefix}_tree_nodes.npy", t["nodes"])
     np.save(f"{prefix}_leafmap.npy", t["leaf_map"])
@@ -225,6 +237,7 @@ def parse_args(argv=None):
     ap.add_argument("--tree", action="store_true", help="the partition tree (quadtree descent on the device) instead of the per-size maps")
     ap.add_argument("--min-size", type=int, default=None, help="with --tree: the smallest CU size of the descent (default 16)")
     ap.add_argument("--frames", type=int, default=None, help="with --tree: the inputs hold this many frames; all trees from one call, --poc is the first frame's")
+    ap.add_argument("--tree-qps", default=None, help="with --tree: comma-separated QPs, one tree per QP from one call (not with --frames)")
     args = ap.parse_args(argv)
     sizes = tuple(int(s) for s in args.sizes.split(",") if s)
     if not sizes or any(s not in SIZES for s in sizes) or (args.weights_dir is None) == (args.synthetic is None):
@@ -241,6 +254,14 @@ def parse_args(argv=None):
             args.qp_list = parse_qps(args.qps)
         except ValueError as e:
             ap.error(str(e))
+    args.tree_qp_list = None
+    if args.tree_qps is not None:
+        if not args.tree or args.frames is not None:
+            ap.error("--tree-qps goes with --tree and not with --frames")
+        try:
+            args.tree_qp_list = parse_qps(args.tree_qps)
+        except ValueError as e:
+            ap.error(str(e).replace("--qps", "--tree-qps"))
     if args.tree:
         if args.min_size is None:
             args.min_size = 16
@@ -277,6 +298,16 @@ def main(argv=None):
             save_tree(f"{args.out}_f{f}", t)
             print(f"frame {f} (poc {args.poc + f}): {len(t['nodes'])} nodes from node {t['first_node']}  " +
                   "  ".join(f"{size}: {count} ({desc} descend)" for size, count, desc in tree_summary(t["nodes"])))
+        m.close()
+        return 0
+    if args.tree and args.tree_qp_list is not None:
+        trees = run_tree_sweep(m, org, pred, args.poc, args.tree_qp_list, args.min_size)
+        for qp, t in zip(args.tree_qp_list, trees):
+            save_tree(f"{args.out}_qp{qp}", t)
+            print(f"qp {qp}: {len(t['nodes'])} nodes  " + "  ".join(f"{size}: {count} ({desc} descend)" for size, count, desc in tree_summary(t["nodes"])))
+        union = [int(v) for v in trees[0]["union_nodes"]]
+        print(f"union: {sum(union)} nodes evaluated for {sum(len(t['nodes']) for t in trees)} nodes of {len(trees)} trees  " +
+              "  ".join(f"{size}: {count}" for size, count in zip(SIZES, union) if size >= args.min_size))
         m.close()
         return 0
     if args.tree:
