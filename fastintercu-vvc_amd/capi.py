@@ -34,7 +34,7 @@ EXPORTS = ["mlt_abi_version", "mlt_build_signature", "mlt_init", "mlt_num_device
            "mlt_predict_batch_device_candidates", "mlt_wait_candidates",
            "mlt_picture_create", "mlt_picture_upload", "mlt_picture_wrap_device", "mlt_picture_destroy", "mlt_predict_at", "mlt_grid_positions",
            "mlt_tree_max_nodes", "mlt_tree_roots", "mlt_predict_tree", "mlt_predict_trees",
-           "mlt_predict_batch_device_sweep", "mlt_predict_at_sweep", "mlt_predict_tree_sweep"]
+           "mlt_predict_batch_device_sweep", "mlt_predict_at_sweep", "mlt_predict_tree_sweep", "mlt_predict_trees_sweep"]
 SWEEP_MAX_QPS = 32  # MLT_SWEEP_MAX_QPS
 TREES_MAX_PICTURES = 256  # MLT_TREES_MAX_PICTURES
 TREE_BY_CANDIDATES = 0x1  # mlt_tree_config.flags: descend on cand_mask & descend_mask instead of on split_mode
@@ -168,6 +168,7 @@ def load_library():
     lib.mlt_predict_tree.argtypes = [vp, vp, vp, C.POINTER(MltTreeConfig), vp, i32, C.POINTER(i32), vp, vp, i32, vp, vp]
     lib.mlt_predict_trees.argtypes = [vp, i32, C.POINTER(MltTreePicture), C.POINTER(MltTreeConfig), vp, i32, vp, vp, vp, i32, vp, vp]
     lib.mlt_predict_tree_sweep.argtypes = [vp, vp, vp, C.POINTER(MltTreeConfig), vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp]
+    lib.mlt_predict_trees_sweep.argtypes = [vp, i32, C.POINTER(MltTreePicture), C.POINTER(MltTreeConfig), vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp]
     lib.mlt_synchronize.argtypes = [vp]
     lib.mlt_set_stream.argtypes = [vp, vp]
     lib.mlt_alloc_pinned.restype = vp
@@ -635,6 +636,46 @@ class MltCnn:
                 if k in out:
                     r[k] = out[k][lo:hi].copy()
             res.append(r)
+        return res
+
+    def predict_trees_sweep(self, pairs, poc, qp_offset, qps, top: int = 128, min_size: int = 16, descend: dict | None = None, by_candidates: bool = False,
+                            want=("leaf_map",)) -> list:
+        """The partition trees of several picture pairs of one geometry under every value of `qps` each, from ONE descent over the unions of all entries
+        (mlt_predict_trees_sweep).  pairs: [(org_pic, pred_pic), ...]; poc / qp_offset: one int for all pairs or one per pair -- entry p under point q runs at
+        qp_offset[p] + qps[q]; the other arguments as predict_tree.
+        -> result[p][q]: a dict shaped like predict_tree_sweep's; "union_nodes" is entry p's int32 [4]."""
+        pairs = list(pairs)
+        P = len(pairs)
+        poc = np.broadcast_to(np.asarray(poc, np.int32), (P,))
+        off = np.broadcast_to(np.asarray(qp_offset, np.int32), (P,))
+        qps = np.ascontiguousarray(qps, np.int32).reshape(-1)
+        Q = qps.shape[0]
+        entries = (MltTreePicture * max(P, 1))()
+        for i, (o, q) in enumerate(pairs):
+            entries[i].org, entries[i].pred, entries[i].poc, entries[i].qp = o._h, q._h, int(poc[i]), int(off[i])
+        cfg = self._tree_config(top, min_size, descend, by_candidates)
+        w, h = (pairs[0][0].width, pairs[0][0].height) if P else (0, 0)
+        cap = P * Q * tree_max_nodes(w, h, top, min_size)
+        nodes = np.zeros((max(cap, 1),), TREE_NODE_DTYPE)
+        first = np.zeros((P * Q + 1,), np.int32)
+        union = np.zeros((max(P, 1), 4), np.int32)
+        out, ptr = self._tree_outputs(want, cap, (max(P * Q, 1), h // 16, w // 16))
+        self._check(self._lib.mlt_predict_trees_sweep(self._h, P, entries, C.byref(cfg), qps.ctypes.data, Q, nodes.ctypes.data, cap, first.ctypes.data, union.ctypes.data,
+                                                      ptr("leaf_map"), ptr("logits"), 15, ptr("decisions"), ptr("candidates")))
+        res = []
+        for p in range(P):
+            row = []
+            for q in range(Q):
+                s = p * Q + q
+                lo, hi = int(first[s]), int(first[s + 1])
+                r = {"nodes": nodes[lo:hi].copy(), "first_node": lo, "union_nodes": union[p].copy()}
+                if "leaf_map" in out:
+                    r["leaf_map"] = out["leaf_map"][s].copy()
+                for k in ("logits", "decisions", "candidates"):
+                    if k in out:
+                        r[k] = out[k][lo:hi].copy()
+                row.append(r)
+            res.append(row)
         return res
 
     def synchronize(self):

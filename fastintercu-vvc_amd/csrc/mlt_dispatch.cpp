@@ -656,7 +656,7 @@ int run_network(mlt_ctx *ctx, SizeState &st, const NetCfg &c, int n, const PassI
       hipEvent_t e0 = nullptr, e1 = nullptr;
       if (io.sweep.n_qps > 0) {   // QP sweep: the same arguments, the heads under every point (fix-up mode: io.sweep.idx)
         HeadSweepArgs sa{};
-        sa.h = ha; sa.h.qp = nullptr; sa.h.mag = nullptr;
+        sa.h = ha; sa.h.mag = nullptr;   // (ha.qp: NULL, or the CUs' offsets to every point)
         sa.n_qps = io.sweep.n_qps; sa.slab = io.sweep.slab; sa.fix_idx = io.sweep.idx; sa.mask = io.sweep.mask; sa.active = io.sweep.idx ? nullptr : io.sweep.active;
         std::memcpy(sa.qps, io.sweep.qps, sizeof sa.qps);
         if ((rc = L.prof_begin("heads_sweep", 0.0, 0.0, e0, e1))) return rc;

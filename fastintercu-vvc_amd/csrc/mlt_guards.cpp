@@ -213,12 +213,12 @@ int run_checked_sweep(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io) {
   const StageSet::Ptrs gs = gl.at(ctx->gstage.p);
   GuardGatherArgs ga{};
   io.pl.fill(ga);
-  ga.poc = io.poc; ga.qp = io.poc;   // (no per-CU qp in a sweep: the gather's qp column is a copy of poc and is not read)
+  ga.poc = io.poc; ga.qp = io.qp ? io.qp : io.poc;   // the CUs' qp offsets follow them into the re-run; without offsets the column is a copy of poc and is not read
   ga.idx = d.idx; ga.k = k; ga.s_l = ilog2(S);
   ga.g_org = gs.d_org; ga.g_pred = gs.d_pred; ga.g_poc = gs.d_poc; ga.g_qp = gs.d_qp;
   HIP_TRY(ctx, mlt_launch_guard_gather(ga, ctx->stream));
   PassIO exact = io;   // the caller's outputs: the heads step writes row idx[j] of the slabs in mask[idx[j]]
-  exact.pl = Planes::dense(gs.d_org, gs.d_pred, S); exact.poc = gs.d_poc; exact.qp = nullptr;
+  exact.pl = Planes::dense(gs.d_org, gs.d_pred, S); exact.poc = gs.d_poc; exact.qp = io.qp ? gs.d_qp : nullptr;
   exact.sweep.idx = d.idx; exact.sweep.mask = d_mask;
   if ((rc = run_network(ctx, st, st.exact_cfg(), k, exact))) return rc;
   st.reruns += (uint64_t)k;

@@ -245,8 +245,9 @@ struct HeadArgs {
   int32_t *g_next;
 };
 
-// QP sweep (sweep_heads_kernel, mlt_tail_kernels.inc): the heads of one pass under n_qps values of qp.  `h` is read as by heads_kernel except h.qp (unused: point
-// q takes qps[q] for every CU) and h.mag (unused); the outputs of point q start `slab` CUs behind those of point q - 1 (h.logits: slab x sum-classes floats).
+// QP sweep (sweep_heads_kernel, mlt_tail_kernels.inc): the heads of one pass under n_qps values of qp.  `h` is read as by heads_kernel except h.qp (NULL: point
+// q takes qps[q] for every CU; else a per-CU OFFSET: CU n takes qps[q] + h.qp[n], added as integers -- fix-up launches read it per CU of the re-run, like
+// h.poc) and h.mag (unused); the outputs of point q start `slab` CUs behind those of point q - 1 (h.logits: slab x sum-classes floats).
 // Fast pass (fix_idx == NULL): workgroup i is CU i and row i, every point is written; with the selection (h.g_next != NULL) mask[i] <- bit q set when CU i is
 // flagged under qps[q] (heads_kernel's rule), and a CU with a non-zero mask is appended to h.g_idx.  Fix-up (fix_idx != NULL, no selection): workgroup j is CU j of
 // the exact re-run, its row is fix_idx[j], and only the points whose bit is set in mask[fix_idx[j]] are written.
@@ -383,15 +384,20 @@ struct TreesPackArgs {
   int n_pictures, n_levels, total;
   int lvl_start[MLT_TREES_LEVELS], n_logits[MLT_TREES_LEVELS];   // a level's logits are dense [lvl_n][n_logits] from row lvl_start of the MLT_TREES_ROW-float rows
 };
-// ---- tree sweeps (mlt_predict_tree_sweep): the UNION descent of one picture pair under n_qps points (mlt_tree_kernels.inc; the arena: mlt_layout.h TreeSweepArena).
-// A union node carries alive (bit q: part of tree q) and desc (bit q: descends under point q); its per-point records / logits / candidate records are slab-major:
-// element (q, i) of a level lies q * slab + i behind the level's element (0, 0).
+// ---- tree sweeps (mlt_predict_tree_sweep, mlt_predict_trees_sweep): the UNION descent of n_pictures entries (one: mlt_predict_tree_sweep) under n_qps points each
+// (mlt_tree_kernels.inc; the arena: mlt_layout.h TreeSweepArena).  A level is one node range over all entries -- entry 0's union segment, entry 1's, ... (the
+// segment table: [MLT_TREES_LEVELS][n_pictures] start and count).  A union node carries pic (its entry), alive (bit q: part of the entry's tree q) and desc (bit q:
+// descends under point q); its per-point records / logits / candidate records are slab-major: element (q, i) of a level lies q * slab + i behind the level's
+// element (0, 0).
 struct TreeSweepExpandArgs {
   TreeNodeRec *nodes;          // the union's nodes (parent / first_child: union indices; split_mode / confidence / cand_mask stay unset), node_cap entries
   int32_t *xy;                 // [node_cap][2]
   uint32_t *alive, *desc;      // [node_cap]
+  int32_t *pic;                // [node_cap] entry of every node
+  int32_t *seg_start, *seg_n;  // the segment table: this launch reads the level's rows and writes the next level's
+  int n_pictures;
   int node_cap;
-  int lvl_start, lvl_n;        // the level just evaluated
+  int lvl_start, lvl_n;        // the level just evaluated, as one list over all entries
   int next_start, next_cap;    // where the next level starts and how many nodes it may hold
   int size, lvl;               // as TreeExpandArgs (lvl = -1, lvl_n = 0: the opening launch)
   const DecisionRec *dec;      // the level's element (0, 0) of each slab array
@@ -401,23 +407,27 @@ struct TreeSweepExpandArgs {
   int n_qps, n_logits, head_off, head_classes;
   uint32_t descend_mask;
   int by_candidates;
-  const int32_t *next_roots;   // the next level's border roots: alive under every point
+  const int32_t *next_roots;   // the border roots EVERY entry's next segment opens with: alive under every point
   int n_next_roots, root_flags;
-  int32_t *count;              // [1] out: n_next_roots + 4 x nodes descending under any point (NULL: not wanted)
+  int32_t *count;              // [1] out: n_pictures x n_next_roots + 4 x nodes descending under any point (NULL: not wanted)
 };
 struct TreeSweepRasterArgs {
   const TreeNodeRec *nodes;
   const uint32_t *alive, *desc;
+  const int32_t *pic;
   const DecisionRec *dec;      // the level's element (0, 0)
   long slab;
-  int lvl_start, lvl_n, blk_l, n_qps;
-  uint8_t *map;                // [n_qps][map_h][map_w]
+  int lvl_start, lvl_n, blk_l, n_qps, n_pictures;
+  uint8_t *map;                // [n_pictures][n_qps][map_h][map_w]
   size_t map_bytes;
   int map_w, map_h;
 };
-// after the last level: idx[q][g] <- the index of union node g inside slice q (-1: not part of it), total[q] <- the slice's node count | the slices themselves
+// after the last level: idx[q][g] <- the index of union node g inside slice (pic[g], q) (-1: not part of it), total[p * n_qps + q] <- the slice's node count |
+// the slices themselves, first_node [n_pictures * n_qps + 1], union_nodes [n_pictures][MLT_TREES_LEVELS]
 struct TreeSweepPackArgs {
   const TreeNodeRec *nodes; const uint32_t *alive, *desc; const DecisionRec *dec; const float *logits; const CandRec *cand;   // whole arena arrays
+  const int32_t *pic, *seg_start, *seg_n;
+  int n_pictures;
   int32_t *idx, *total, *first_node, *union_nodes;
   TreeNodeRec *o_nodes; float *o_logits; DecisionRec *o_dec; CandRec *o_cand;   // [out_cap]; NULL = not wanted
   int n_qps, n_levels, node_cap, out_cap;

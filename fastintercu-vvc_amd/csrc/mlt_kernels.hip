@@ -899,7 +899,7 @@ hipError_t mlt_launch_trees_pack(const TreesPackArgs &a, hipStream_t st) {
 
 // tree sweeps -- ONE workgroup, as mlt_launch_tree_expand
 hipError_t mlt_launch_tree_expand_sweep(const TreeSweepExpandArgs &a, hipStream_t st) {
-  if (a.n_qps < 1 || a.n_qps > MLT_SWEEP_MAX_QPS_K) return hipErrorInvalidValue;
+  if (a.n_qps < 1 || a.n_qps > MLT_SWEEP_MAX_QPS_K || a.n_pictures < 1 || a.n_pictures > MLT_TREES_MAX_PICTURES_K) return hipErrorInvalidValue;   // (the per-entry ranks live in LDS)
   hipLaunchKernelGGL(tree_expand_sweep_kernel, dim3(1), dim3(MLT_TREE_TILE), 0, st, a);
   return hipGetLastError();
 }
@@ -912,16 +912,16 @@ hipError_t mlt_launch_tree_sweep_raster(const TreeSweepRasterArgs &a, hipStream_
   return hipGetLastError();
 }
 
-// one workgroup per point
+// one workgroup per (entry, point)
 hipError_t mlt_launch_tree_sweep_rank(const TreeSweepPackArgs &a, hipStream_t st) {
-  if (a.n_qps < 1 || a.n_qps > MLT_SWEEP_MAX_QPS_K) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(tree_sweep_rank_kernel, dim3((unsigned)a.n_qps), dim3(MLT_TREE_TILE), 0, st, a);
+  if (a.n_qps < 1 || a.n_qps > MLT_SWEEP_MAX_QPS_K || a.n_pictures < 1 || a.n_pictures > MLT_TREES_MAX_PICTURES_K) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tree_sweep_rank_kernel, dim3((unsigned)(a.n_pictures * a.n_qps)), dim3(MLT_TREE_TILE), 0, st, a);
   return hipGetLastError();
 }
 
 // flat grid-stride launch over (point, union node); at least workgroup 0, which writes first_node[] and union_nodes[]
 hipError_t mlt_launch_tree_sweep_pack(const TreeSweepPackArgs &a, hipStream_t st) {
-  if (a.n_qps < 1 || a.n_qps > MLT_SWEEP_MAX_QPS_K) return hipErrorInvalidValue;
+  if (a.n_qps < 1 || a.n_qps > MLT_SWEEP_MAX_QPS_K || a.n_pictures < 1 || a.n_pictures > MLT_TREES_MAX_PICTURES_K) return hipErrorInvalidValue;   // (the slices' starts live in LDS)
   size_t items = 0;
   for (int l = 0; l < a.n_levels; ++l) items += (size_t)a.lvl_n[l];
   const size_t want = (items * (size_t)a.n_qps + 255) / 256;

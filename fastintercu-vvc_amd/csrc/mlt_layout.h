@@ -136,39 +136,45 @@ struct TreeArena : Carved {
                 entries.in<char>(b), o_nodes.in<TreeNodeRec>(b), o_logits.in<float>(b), o_dec.in<DecisionRec>(b), o_cand.in<CandRec>(b)};
   }
 };
-// The device arena of a tree SWEEP (mlt_predict_tree_sweep): the UNION of the trees of one picture pair under n_qps points, LEVEL-major, every level at its full
-// capacity -- level l holds up to cap[l] = (W / S)(H / S) nodes from node off[l] = cap[0] + .. + cap[l - 1] on (n = off[levels]).  Per union node: nodes | xy |
-// alive (bit q: the node is part of tree q) | desc (bit q: it descends under point q).  The per-node outputs of a level are SLAB-major over the points: element
-// (l, q, i) of records [| logits, kRow floats reserved per element, a level's rows dense] [| candidate records] is entry n_qps * off[l] + q * cap[l] + i -- the
-// sweep pass writes level l with slab stride cap[l].  Then roots | count | idx [n_qps][n] (a node's index inside slice q) | total [n_qps] | first_node
-// [n_qps + 1] | union_nodes [kLevels] [| one leaf map per point] | the packed output: nodes [| logits] [| records] [| candidate records], n_qps * n each.
+// The device arena of a tree SWEEP (mlt_predict_tree_sweep: pics = 1; mlt_predict_trees_sweep): the UNION of the trees of each of `pics` entries of one geometry
+// under n_qps points, LEVEL-major, every level at its full capacity -- level l holds up to cap[l] = pics (W / S)(H / S) nodes from node off[l] = cap[0] + .. +
+// cap[l - 1] on (n = off[levels]); inside a level entry 0's union segment, entry 1's, ... (the segment table).  Per union node: nodes | xy | alive (bit q: the node
+// is part of its entry's tree q) | desc (bit q: it descends under point q).  The per-node outputs of a level are SLAB-major over the points: element (l, q, i) of
+// records [| logits, kRow floats reserved per element, a level's rows dense] [| candidate records] is entry n_qps * off[l] + q * cap[l] + i -- the sweep pass
+// writes level l with slab stride cap[l].  Then roots | count | idx [n_qps][n] (a node's index inside its entry's slice q) | total [pics * n_qps] | first_node
+// [pics * n_qps + 1] | union_nodes [pics][kLevels] [| one leaf map per (entry, point)] | the packed output: nodes [| logits] [| records] [| candidate records],
+// n_qps * n each | pic (a node's entry) | the segment table ([kLevels][pics]: start, count) [| the entry table, entry_bytes each: pics > 1].
 struct TreeSweepArena : Carved {
   static const int kRow = MLT_MAX_LOGITS, kLevels = 4;
   struct Ptrs {
     TreeNodeRec *nodes; int32_t *xy; uint32_t *alive, *desc; DecisionRec *dec; float *logits; CandRec *cand; int32_t *roots, *count, *idx, *total, *first_node, *union_nodes;
     uint8_t *map; TreeNodeRec *o_nodes; float *o_logits; DecisionRec *o_dec; CandRec *o_cand;
+    int32_t *pic, *seg_start, *seg_n; char *entries;
   };
-  size_t n_qps, n, off[kLevels + 1], cap[kLevels];
-  Field nodes, xy, alive, desc, dec, logits, cand, roots, count, idx, total, first_node, union_nodes, map, o_nodes, o_logits, o_dec, o_cand;
+  size_t n_qps, n, off[kLevels + 1], cap[kLevels], pics;
+  Field nodes, xy, alive, desc, dec, logits, cand, roots, count, idx, total, first_node, union_nodes, map, o_nodes, o_logits, o_dec, o_cand, pic, seg_start, seg_n, entries;
+  // lvl_cap: ONE entry's capacity per level
   TreeSweepArena(size_t n_qps_, int levels, const size_t *lvl_cap, size_t n_roots, size_t map_bytes, bool lg, bool cands, bool out_map, bool out_logits, bool out_dec,
-                 bool out_cand) : n_qps(n_qps_) {
+                 bool out_cand, size_t pics_ = 1, size_t entry_bytes = 0) : n_qps(n_qps_), pics(pics_) {
     off[0] = 0;
-    for (int l = 0; l < kLevels; ++l) { cap[l] = l < levels ? lvl_cap[l] : 0; off[l + 1] = off[l] + cap[l]; }
+    for (int l = 0; l < kLevels; ++l) { cap[l] = l < levels ? pics * lvl_cap[l] : 0; off[l + 1] = off[l] + cap[l]; }
     n = off[kLevels];
-    const size_t QN = n_qps * n;
+    const size_t QN = n_qps * n, PQ = pics * n_qps;
     nodes = put(n * sizeof(mlt_tree_node), 256); xy = put(n * 8, 256); alive = put(n * 4, 256); desc = put(n * 4, 256);
     dec = put(QN * sizeof(mlt_decision), 256); logits = put(QN * kRow * 4, 256, lg); cand = put(QN * sizeof(mlt_candidates), 256, cands);
-    roots = put(n_roots * 8, 256); count = put(4, 256); idx = put(QN * 4, 256); total = put(n_qps * 4, 256); first_node = put((n_qps + 1) * 4, 256);
-    union_nodes = put(kLevels * 4, 256); map = put(n_qps * map_bytes, 256, out_map);
+    roots = put(n_roots * 8, 256); count = put(4, 256); idx = put(QN * 4, 256); total = put(PQ * 4, 256); first_node = put((PQ + 1) * 4, 256);
+    union_nodes = put(pics * kLevels * 4, 256); map = put(PQ * map_bytes, 256, out_map);
     o_nodes = put(QN * sizeof(mlt_tree_node), 256); o_logits = put(QN * kRow * 4, 256, out_logits); o_dec = put(QN * sizeof(mlt_decision), 256, out_dec);
     o_cand = put(QN * sizeof(mlt_candidates), 256, out_cand);
+    pic = put(n * 4, 256); seg_start = put(kLevels * pics * 4, 256); seg_n = put(kLevels * pics * 4, 256); entries = put(pics * entry_bytes, 256, pics > 1);
   }
   size_t slab0(int l) const { return n_qps * off[l]; }                                            // element (l, 0, 0)
   size_t element(int l, size_t q, size_t i) const { return slab0(l) + q * cap[l] + i; }   // slab stride of level l: cap[l]
   Ptrs at(char *b) const {
     return Ptrs{nodes.in<TreeNodeRec>(b), xy.in<int32_t>(b), alive.in<uint32_t>(b), desc.in<uint32_t>(b), dec.in<DecisionRec>(b), logits.in<float>(b), cand.in<CandRec>(b),
                 roots.in<int32_t>(b), count.in<int32_t>(b), idx.in<int32_t>(b), total.in<int32_t>(b), first_node.in<int32_t>(b), union_nodes.in<int32_t>(b), map.in<uint8_t>(b),
-                o_nodes.in<TreeNodeRec>(b), o_logits.in<float>(b), o_dec.in<DecisionRec>(b), o_cand.in<CandRec>(b)};
+                o_nodes.in<TreeNodeRec>(b), o_logits.in<float>(b), o_dec.in<DecisionRec>(b), o_cand.in<CandRec>(b),
+                pic.in<int32_t>(b), seg_start.in<int32_t>(b), seg_n.in<int32_t>(b), entries.in<char>(b)};
   }
 };
 

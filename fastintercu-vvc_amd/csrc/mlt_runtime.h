@@ -4,7 +4,7 @@
 //   mlt_calibrate.cpp  model upload, calibration sets and session, the loader, mlt_load_weights / mlt_calibrate / mlt_arithmetic
 //   mlt_api.cpp        init / shutdown / stream, the predict entry points, deferred prediction, confidence gate, profile
 //   mlt_pictures.cpp   device-resident pictures: create / upload / wrap / destroy, mlt_predict_at, mlt_grid_positions
-//   mlt_tree.cpp       partition trees of a picture: mlt_predict_tree, mlt_predict_trees, mlt_predict_tree_sweep, mlt_tree_roots, mlt_tree_max_nodes
+//   mlt_tree.cpp       partition trees of a picture: mlt_predict_tree, mlt_predict_trees, mlt_predict_tree_sweep, mlt_predict_trees_sweep, mlt_tree_roots, mlt_tree_max_nodes
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -296,7 +296,7 @@ struct mlt_ctx {
   GrowBuf sweep_guard_dev;              // QP sweeps: one slot of sweep_guard_lay (zero when allocated), its counter phase; the count lands in guard_host[2]
   Lay::SweepGuardLay sweep_guard_lay;
   int sweep_phase = 0;
-  // mlt_predict_tree's / mlt_predict_trees' device arena (Lay::TreeArena) or mlt_predict_tree_sweep's (Lay::TreeSweepArena), and the pinned count
+  // mlt_predict_tree's / mlt_predict_trees' device arena (Lay::TreeArena) or mlt_predict_tree_sweep's / mlt_predict_trees_sweep's (Lay::TreeSweepArena), and the pinned count
   GrowBuf tree_dev;
   int32_t *tree_host = nullptr;
   std::vector<mlt_picture *> pictures;  // every picture created on / wrapped for this context (mlt_pictures.cpp); what is left is released by mlt_shutdown
@@ -363,7 +363,7 @@ struct Planes {
 };
 
 // QP sweep part of a pass (off unless n_qps > 0): the heads step evaluates every CU under qps[0 .. n_qps) -- sweep_heads_kernel instead of the heads kernel --
-// and output (q, i) of split / logits / dec / cand lies `slab` CUs x q behind output (0, i); PassIO.qp is not read.  idx + mask: the pass is the exact re-run of
+// and output (q, i) of split / logits / dec / cand lies `slab` CUs x q behind output (0, i); PassIO.qp is NULL or the CUs' OFFSETS to every point (CU i under point q: qps[q] + qp[i]; tree sweeps over several entries).  idx + mask: the pass is the exact re-run of
 // a sweep's flagged CUs -- CU j writes row idx[j] of the points in mask[idx[j]]; mask alone (with the guards' tail): where the fast pass leaves the CUs' masks.
 struct SweepPart {
   int n_qps = 0;

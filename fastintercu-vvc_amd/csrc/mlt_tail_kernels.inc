@@ -230,6 +230,7 @@ __global__ __launch_bounds__(256) void heads_cand_kernel(const HeadArgs a) { hea
 // over [feat, poc] are computed once per (head, class) with heads_body's chain; a point adds its one fmaf in that lane and repeats the shuffle tree and the bias.
 // The magnitude statistic does not see qp: once.  The tails run on one thread per (point, head) -- head_decision -- and one per point -- split under the gate,
 // records, the guards' rule (heads_body's, same comparisons): the points of wave 0 vote the CU's mask.  Fix-up launches (sa.fix_idx) write only the masked points.
+// a.qp != NULL: CU n's point q is qps[q] + a.qp[n] -- added as integers before the one conversion, so the slab holds the bytes of a CU whose qp is that sum.
 __global__ __launch_bounds__(256) void sweep_heads_kernel(const HeadSweepArgs sa) {
   const HeadArgs &a = sa.h;
   __shared__ float feat[MLT_MAX_HEADS_K][256 + 2];
@@ -244,6 +245,7 @@ __global__ __launch_bounds__(256) void sweep_heads_kernel(const HeadSweepArgs sa
   const uint32_t wr = sa.fix_idx ? sa.mask[row] & all : all;   // the points this workgroup writes
   const bool select = !sa.fix_idx && a.g_count && a.g_next;
   const float fpoc = (float)a.poc[n];
+  const int qp_off = a.qp ? a.qp[n] : 0;
   for (int hd = 0; hd < a.n_heads; ++hd) {   // heads_body's features: slot-order sums, / (float)hw
     const int C = a.c[hd], slots = a.slots[hd];
     if (tid < C) {
@@ -278,7 +280,7 @@ __global__ __launch_bounds__(256) void sweep_heads_kernel(const HeadSweepArgs sa
       const bool mine = lane == ((C + 1) & 63);
       const float wq = w[C + 1], bk = a.b[hd][k];
       for (int q = 0; q < Q; ++q) {
-        float sq = mine ? __builtin_fmaf(wq, (float)sa.qps[q], s) : s;
+        float sq = mine ? __builtin_fmaf(wq, (float)(sa.qps[q] + qp_off), s) : s;
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) sq += __shfl_down(sq, off, 64);
         if (lane == 0) lg[q][lo + k] = sq + bk;

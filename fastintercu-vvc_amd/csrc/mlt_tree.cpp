@@ -1,4 +1,5 @@
-// mlt_tree.cpp -- partition trees of a picture (include/mltcnn.h): mlt_predict_tree, mlt_predict_trees, mlt_predict_tree_sweep, mlt_tree_roots, mlt_tree_max_nodes.
+// mlt_tree.cpp -- partition trees of a picture (include/mltcnn.h): mlt_predict_tree, mlt_predict_trees, mlt_predict_tree_sweep, mlt_predict_trees_sweep, mlt_tree_roots,
+// mlt_tree_max_nodes.
 //
 // Both calls run ONE descent (descend below) over the trees of P picture pairs of one geometry; mlt_predict_tree is P = 1.  Per level: the network on the level's
 // nodes -- predict_at_chunks (mlt_pictures.cpp) on the slice of the device-resident position list that IS the level, over all pictures, so launches, guards and
@@ -7,7 +8,8 @@
 // positions and the per-node logits / records are indexed by NODE in one device arena, LEVEL-major (picture 0's segment of a level, picture 1's, ...), so a level's
 // arrays are slices of the arena's.  One picture's arena is already in the contract's order and mlt_predict_tree ends in a handful of D2H copies;
 // mlt_predict_trees lets tree_pack_kernel permute into the picture-major order of its contract first, then one D2H copy per requested array.
-// mlt_predict_tree_sweep (one pair, several qp) runs a descent of its own over the UNION of the points' trees: descend_sweep below.
+// mlt_predict_tree_sweep (one pair, several qp) and mlt_predict_trees_sweep (several pairs, several qp each) run ONE descent of their own over the UNION of every
+// entry's trees: descend_sweep below, P = 1 for the former.
 #include "mlt_runtime.h"
 
 namespace {
@@ -174,14 +176,17 @@ int descend(mlt_ctx *ctx, const char *who, const TreeLevels &lv, int W, int H, i
   return MLT_OK;
 }
 
-// The UNION descent of mlt_predict_tree_sweep: the trees of one pair under qps[0 .. Q), every node that exists under any point evaluated once.  Per level: the
-// gather from the level's slice of the device position list, ONE sweep pass per chunk (run_checked_sweep: the heads under every point, slab-major straight into the
-// arena with the level's slab stride; a node is flagged only under the points it is alive under), tree_expand_sweep_kernel, the leaves into the maps, one 4-byte count.
+// The UNION descent of mlt_predict_tree_sweep (P = 1) and mlt_predict_trees_sweep: the trees of pics[0 .. P) (W x H each, checked by the caller) under qps[0 .. Q),
+// every node that exists under any point of its entry evaluated once.  Per level, over ALL entries: the gather from the level's slice of the device position
+// list, ONE sweep pass per chunk (run_checked_sweep: the heads under every point, slab-major straight into the arena with the level's slab stride; a node is
+// flagged only under the points it is alive under), tree_expand_sweep_kernel, the leaves into the maps, one 4-byte count.  One entry: its planes and poc are
+// launch arguments of the gather and qps[] are the points' QPs themselves (the caller has added the entry's offset).  Several: the entry table, looked up through
+// the nodes' pic by picture_gather_multi_kernel, which also writes the chunk's per-CU poc and qp -- the entry's OFFSET, which the sweep heads add to every point.
 struct SweepDescent { Lay::TreeSweepArena::Ptrs A; size_t map_bytes; int n[4], start[4], cap[4]; bool has_cand[4]; };
-int descend_sweep(mlt_ctx *ctx, const char *who, const TreeLevels &lv, const mlt_picture *org, const mlt_picture *pred, int32_t poc, const int32_t *qps, int Q, bool by_cand,
+int descend_sweep(mlt_ctx *ctx, const char *who, const TreeLevels &lv, int W, int H, int P, const mlt_tree_picture *pics, const int32_t *qps, int Q, bool by_cand,
                   const TreeWant &want, SweepDescent &d) {
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
-  const int W = org->width, H = org->height, top = lv.top, L = lv.L;
+  const int top = lv.top, L = lv.L;
   int rc;
   bool any_cand = false, all_cand = true;
   size_t lvl_cap[4] = {0, 0, 0, 0};
@@ -196,21 +201,32 @@ int descend_sweep(mlt_ctx *ctx, const char *who, const TreeLevels &lv, const mlt
   const int map_w = W / 16, map_h = H / 16;
   const size_t map_bytes = d.map_bytes = (size_t)map_w * map_h;
   // logits: the caller's, or what cand_mask is made from on the levels without candidate records
-  const Lay::TreeSweepArena arena((size_t)Q, L, lvl_cap, tr.xy.size() / 2, map_bytes, want.logits || !all_cand, any_cand, want.map, want.logits, want.dec, want.cand);
+  const Lay::TreeSweepArena arena((size_t)Q, L, lvl_cap, tr.xy.size() / 2, map_bytes, want.logits || !all_cand, any_cand, want.map, want.logits, want.dec, want.cand, (size_t)P,
+                                  sizeof(TreesEntry));
   if ((rc = ctx->tree_dev.reserve(ctx, arena.bytes(), who))) return rc;
   if (!ctx->tree_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->tree_host, 64, hipHostMallocDefault));
   const Lay::TreeSweepArena::Ptrs A = d.A = arena.at(ctx->tree_dev.p);
   const int N = (int)arena.n;
-  const AtPlanes pl = AtPlanes::of(org, pred, 0);
+  const AtPlanes pl = AtPlanes::of(pics[0].org, pics[0].pred, 0);
+  if (P > 1) {
+    std::vector<TreesEntry> entries((size_t)P);
+    for (int p = 0; p < P; ++p) {
+      const AtPlanes e = AtPlanes::of(pics[p].org, pics[p].pred, 0);
+      entries[(size_t)p] = TreesEntry{e.org, e.pred, e.org_pitch, e.pred_pitch, e.org_vec ? 1 : 0, e.pred_vec ? 1 : 0, pics[p].poc, pics[p].qp};
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(A.entries, entries.data(), entries.size() * sizeof(TreesEntry), hipMemcpyHostToDevice, ctx->stream));   // (pageable: read when the copy returns)
+  }
   if (!tr.xy.empty()) HIP_TRY(ctx, hipMemcpyAsync(A.roots, tr.xy.data(), tr.xy.size() * 4, hipMemcpyHostToDevice, ctx->stream));   // (pageable: read when the copy returns)
-  if (want.map) HIP_TRY(ctx, hipMemsetAsync(A.map, 0xFF, (size_t)Q * map_bytes, ctx->stream));
+  if (want.map) HIP_TRY(ctx, hipMemsetAsync(A.map, 0xFF, (size_t)P * (size_t)Q * map_bytes, ctx->stream));
   Launch prof{ctx};
   auto expand = [&](const TreeSweepExpandArgs &ea) -> int {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int r;
     // algorithmic bytes the host knows: the level's alive masks and, under every point, its records read, its node fields written, the next roots written
-    if ((r = prof.prof_begin("tree_expand_sweep", 0.0, (double)ea.lvl_n * ((double)Q * sizeof(DecisionRec) + 16) + (double)ea.n_next_roots * (sizeof(TreeNodeRec) + 24), e0, e1)))
-      return r;
+    // (several entries: + a picture index per node and root, the segment table's rows)
+    double bytes = (double)ea.lvl_n * ((double)Q * sizeof(DecisionRec) + 16) + (double)P * ea.n_next_roots * (sizeof(TreeNodeRec) + 24);
+    if (P > 1) bytes += 4.0 * ((double)ea.lvl_n + (double)P * ea.n_next_roots) + (double)P * 8;
+    if ((r = prof.prof_begin("tree_expand_sweep", 0.0, bytes, e0, e1))) return r;
     HIP_TRY(ctx, mlt_launch_tree_expand_sweep(ea, ctx->stream));
     return prof.prof_end(e1);
   };
@@ -218,12 +234,13 @@ int descend_sweep(mlt_ctx *ctx, const char *who, const TreeLevels &lv, const mlt
   sw.n_qps = Q;
   std::memcpy(sw.qps, qps, (size_t)Q * 4);
   TreeSweepExpandArgs ea{};
-  ea.nodes = A.nodes; ea.xy = A.xy; ea.alive = A.alive; ea.desc = A.desc; ea.node_cap = N; ea.n_qps = Q; ea.by_candidates = by_cand ? 1 : 0;
-  // the union opens: no parents, the top-level roots
+  ea.nodes = A.nodes; ea.xy = A.xy; ea.alive = A.alive; ea.desc = A.desc; ea.pic = A.pic; ea.seg_start = A.seg_start; ea.seg_n = A.seg_n; ea.n_pictures = P;
+  ea.node_cap = N; ea.n_qps = Q; ea.by_candidates = by_cand ? 1 : 0;
+  // the unions open: no parents, every entry's top-level roots
   ea.lvl_start = 0; ea.lvl_n = 0; ea.next_start = 0; ea.next_cap = (int)arena.cap[0]; ea.size = 2 * top; ea.lvl = -1;
   ea.next_roots = A.roots; ea.n_next_roots = tr.n[0]; ea.root_flags = 0; ea.count = nullptr;
   if ((rc = expand(ea))) return rc;
-  int n = tr.n[0];
+  int n = P * tr.n[0];
   for (int l = 0, S = top; l < L; ++l, S >>= 1) {
     SizeState *s = lv.st[l];
     const bool last = l == L - 1;
@@ -239,18 +256,27 @@ int descend_sweep(mlt_ctx *ctx, const char *who, const TreeLevels &lv, const mlt
       const StageSet lay(S, cap, nl, false, false);
       if ((rc = ctx->stage.reserve(ctx, lay.bytes(), "staging"))) return rc;
       const StageSet::Ptrs G = lay.at(ctx->stage.p);
-      HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)G.d_poc, poc, (size_t)cap, ctx->stream));   // one poc: every chunk reads its first c entries
+      if (P == 1) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)G.d_poc, pics[0].poc, (size_t)cap, ctx->stream));   // one poc: every chunk reads its first c entries
       for (int i0 = 0; i0 < n; i0 += cap) {
         const int c = n - i0 < cap ? n - i0 : cap;
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        PictureGatherArgs ga{};
-        ga.org = pl.org; ga.pred = pl.pred; ga.org_pitch = pl.org_pitch; ga.pred_pitch = pl.pred_pitch; ga.vec_org = pl.org_vec; ga.vec_pred = pl.pred_vec;
-        ga.xy = A.xy + 2 * ((size_t)start + (size_t)i0); ga.g_org = G.d_org; ga.g_pred = G.d_pred; ga.c = c; ga.s_l = ilog2(S);
-        if ((rc = prof.prof_begin("picture_gather", 0.0, (double)c * S * S * 2 * 2 * 2, e0, e1))) return rc;
-        LAUNCH_TRY(ctx, mlt_launch_picture_gather(ga, ctx->stream));
+        if (P == 1) {
+          PictureGatherArgs ga{};
+          ga.org = pl.org; ga.pred = pl.pred; ga.org_pitch = pl.org_pitch; ga.pred_pitch = pl.pred_pitch; ga.vec_org = pl.org_vec; ga.vec_pred = pl.pred_vec;
+          ga.xy = A.xy + 2 * ((size_t)start + (size_t)i0); ga.g_org = G.d_org; ga.g_pred = G.d_pred; ga.c = c; ga.s_l = ilog2(S);
+          if ((rc = prof.prof_begin("picture_gather", 0.0, (double)c * S * S * 2 * 2 * 2, e0, e1))) return rc;
+          LAUNCH_TRY(ctx, mlt_launch_picture_gather(ga, ctx->stream));
+        } else {   // the chunk's slice of the list and of its entry indices; the launch writes the chunk's poc and qp offsets as well
+          PictureGatherMultiArgs ga{};
+          ga.entries = (const TreesEntry *)A.entries; ga.n_entries = P; ga.pic = A.pic + start + i0; ga.xy = A.xy + 2 * ((size_t)start + (size_t)i0);
+          ga.g_org = G.d_org; ga.g_pred = G.d_pred; ga.g_poc = G.d_poc; ga.g_qp = G.d_qp; ga.c = c; ga.s_l = ilog2(S);
+          if ((rc = prof.prof_begin("picture_gather_multi", 0.0, (double)c * (S * S * 2 * 2 * 2 + 12), e0, e1))) return rc;
+          LAUNCH_TRY(ctx, mlt_launch_picture_gather_multi(ga, ctx->stream));
+        }
         if ((rc = prof.prof_end(e1))) return rc;
         sw.active = A.alive + start + i0;
-        const PassIO io{Planes::dense(G.d_org, G.d_pred, S), G.d_poc, nullptr, nullptr, d_lg ? d_lg + (size_t)i0 * nl : nullptr, d_dec + i0, d_cand ? d_cand + i0 : nullptr, sw};
+        const PassIO io{Planes::dense(G.d_org, G.d_pred, S), G.d_poc, P == 1 ? nullptr : G.d_qp, nullptr, d_lg ? d_lg + (size_t)i0 * nl : nullptr, d_dec + i0,
+                        d_cand ? d_cand + i0 : nullptr, sw};
         if ((rc = run_checked_sweep(ctx, *s, c, io))) return rc;   // (the stream orders this chunk's reads of the staged planes before the next chunk's gather)
       }
     }
@@ -264,23 +290,81 @@ int descend_sweep(mlt_ctx *ctx, const char *who, const TreeLevels &lv, const mlt
     if ((rc = expand(ea))) return rc;
     if (n > 0 && want.map) {
       TreeSweepRasterArgs ra{};
-      ra.nodes = A.nodes; ra.alive = A.alive; ra.desc = A.desc; ra.dec = d_dec; ra.slab = sw.slab; ra.lvl_start = start; ra.lvl_n = n; ra.blk_l = ilog2(S) - 4; ra.n_qps = Q;
-      ra.map = A.map; ra.map_bytes = map_bytes; ra.map_w = map_w; ra.map_h = map_h;
+      ra.nodes = A.nodes; ra.alive = A.alive; ra.desc = A.desc; ra.pic = A.pic; ra.dec = d_dec; ra.slab = sw.slab; ra.lvl_start = start; ra.lvl_n = n; ra.blk_l = ilog2(S) - 4;
+      ra.n_qps = Q; ra.n_pictures = P; ra.map = A.map; ra.map_bytes = map_bytes; ra.map_w = map_w; ra.map_h = map_h;
       hipEvent_t e0 = nullptr, e1 = nullptr;
       // algorithmic bytes: every node record and mask pair read once, one byte per block of a leaf written under every point (at most the level's whole area each)
-      if ((rc = prof.prof_begin("tree_sweep_raster", 0.0, (double)n * (sizeof(TreeNodeRec) + 8 + (double)Q * (1 << (2 * ra.blk_l))), e0, e1))) return rc;
+      if ((rc = prof.prof_begin("tree_sweep_raster", 0.0, (double)n * (sizeof(TreeNodeRec) + 8 + (P > 1 ? 4 : 0) + (double)Q * (1 << (2 * ra.blk_l))), e0, e1))) return rc;
       HIP_TRY(ctx, mlt_launch_tree_sweep_raster(ra, ctx->stream));
       if ((rc = prof.prof_end(e1))) return rc;
     }
     if (last) break;
-    // the one host synchronisation of the level beside the guards': how many nodes the union's next level has
+    // the one host synchronisation of the level beside the guards': how many nodes the unions' next level has, over all entries
     HIP_TRY(ctx, hipMemcpyAsync(ctx->tree_host, A.count, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     n = ctx->tree_host[0];
-    const int nr = tr.n[l + 1];
+    const long long nr = (long long)P * tr.n[l + 1];
     if (n < nr || ((n - nr) & 3) || (size_t)n > arena.cap[l + 1]) { ctx->err = std::string(who) + ": bad node count from the device"; return MLT_ERR_HIP; }
   }
   for (int l = L; l < 4; ++l) { d.start[l] = 0; d.n[l] = 0; d.cap[l] = 0; d.has_cand[l] = false; }
+  return MLT_OK;
+}
+
+// What follows a union descent: rank and pack -- one slice per (entry, point), slice p * Q + q -- then everything the caller asked for and one synchronisation.
+// max_nodes: mlt_tree_max_nodes of one picture.
+int sweep_results(mlt_ctx *ctx, const char *who, const TreeLevels &lv, const SweepDescent &d, int P, int Q, int max_nodes, mlt_tree_node *nodes, int32_t *first_node,
+                  int32_t *union_nodes_opt, uint8_t *leaf_maps_opt, float *logits_opt, int logit_stride, mlt_decision *dec_opt, mlt_candidates *cand_opt) {
+  const Lay::TreeSweepArena::Ptrs &A = d.A;
+  const long long cap_all = (long long)P * Q * max_nodes;
+  const size_t PQ = (size_t)P * (size_t)Q;
+  int rc;
+  TreeSweepPackArgs pa{};
+  pa.nodes = A.nodes; pa.alive = A.alive; pa.desc = A.desc; pa.dec = A.dec; pa.logits = A.logits; pa.cand = A.cand;
+  pa.pic = A.pic; pa.seg_start = A.seg_start; pa.seg_n = A.seg_n; pa.n_pictures = P;
+  pa.idx = A.idx; pa.total = A.total; pa.first_node = A.first_node; pa.union_nodes = A.union_nodes;
+  pa.o_nodes = A.o_nodes; pa.o_logits = A.o_logits; pa.o_dec = A.o_dec; pa.o_cand = A.o_cand;
+  pa.n_qps = Q; pa.n_levels = lv.L; pa.node_cap = P * max_nodes; pa.out_cap = (int)cap_all;
+  long long un = 0;
+  for (int l = 0; l < lv.L; ++l) {
+    pa.lvl_start[l] = d.start[l]; pa.lvl_n[l] = d.n[l]; pa.lvl_cap[l] = d.cap[l]; pa.has_cand[l] = d.has_cand[l] ? 1 : 0;
+    pa.n_logits[l] = lv.st[l]->model.n_logits; pa.head_off[l] = lv.st[l]->head_off(); pa.head_classes[l] = lv.st[l]->head_classes();
+    un += d.n[l];
+  }
+  {
+    Launch prof{ctx};
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    // algorithmic bytes: the alive mask of every union node read and its index written under every point | per (point, node) at most one node record, its slab
+    // record and the requested rows and records, read and written
+    if ((rc = prof.prof_begin("tree_sweep_rank", 0.0, (double)Q * (double)un * 8, e0, e1))) return rc;
+    HIP_TRY(ctx, mlt_launch_tree_sweep_rank(pa, ctx->stream));
+    if ((rc = prof.prof_end(e1))) return rc;
+    const double per = 2.0 * sizeof(TreeNodeRec) + 12 + sizeof(DecisionRec) + (logits_opt ? 2.0 * kRowLogits * 4 : 0) + (dec_opt ? sizeof(DecisionRec) : 0) + (cand_opt ? 2.0 * sizeof(CandRec) : 0);
+    if ((rc = prof.prof_begin("tree_sweep_pack", 0.0, (double)Q * (double)un * per, e0, e1))) return rc;
+    HIP_TRY(ctx, mlt_launch_tree_sweep_pack(pa, ctx->stream));
+    if ((rc = prof.prof_end(e1))) return rc;
+  }
+  // the slices' sizes first: the copies below take exactly the packed nodes (the caller's arrays stay untouched behind them)
+  std::vector<int32_t> first(PQ + 1), un_l((size_t)P * 4);
+  HIP_TRY(ctx, hipMemcpyAsync(first.data(), A.first_node, (PQ + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(un_l.data(), A.union_nodes, (size_t)P * 16, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const int total = first[PQ];
+  bool ok = first[0] == 0 && total >= 0 && total <= cap_all;
+  for (size_t s = 0; s < PQ && ok; ++s) ok = first[s + 1] >= first[s];
+  if (!ok) { ctx->err = std::string(who) + ": bad node count from the device"; return MLT_ERR_HIP; }
+  if (total) {
+    HIP_TRY(ctx, hipMemcpyAsync(nodes, A.o_nodes, (size_t)total * sizeof(TreeNodeRec), hipMemcpyDeviceToHost, ctx->stream));
+    if (logits_opt) {   // whole zero-padded rows
+      if (logit_stride == kRowLogits) HIP_TRY(ctx, hipMemcpyAsync(logits_opt, A.o_logits, (size_t)total * kRowLogits * 4, hipMemcpyDeviceToHost, ctx->stream));
+      else HIP_TRY(ctx, hipMemcpy2DAsync(logits_opt, (size_t)logit_stride * 4, A.o_logits, (size_t)kRowLogits * 4, (size_t)kRowLogits * 4, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (dec_opt) HIP_TRY(ctx, hipMemcpyAsync(dec_opt, A.o_dec, (size_t)total * sizeof(DecisionRec), hipMemcpyDeviceToHost, ctx->stream));
+    if (cand_opt) HIP_TRY(ctx, hipMemcpyAsync(cand_opt, A.o_cand, (size_t)total * sizeof(CandRec), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (leaf_maps_opt) HIP_TRY(ctx, hipMemcpyAsync(leaf_maps_opt, A.map, PQ * d.map_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  std::memcpy(first_node, first.data(), (PQ + 1) * 4);
+  if (union_nodes_opt) std::memcpy(union_nodes_opt, un_l.data(), (size_t)P * 16);
   return MLT_OK;
 }
 
@@ -441,59 +525,69 @@ int mlt_predict_tree_sweep(mlt_ctx *ctx, const mlt_picture *org, const mlt_pictu
     return MLT_ERR_ARG;
   }
   // ---- arguments are good: the union descent runs on this context's own device (devices[0] of a multi-device context) ----
+  const mlt_tree_picture one{org, pred, cfg->poc, 0};
   SweepDescent d;
-  if ((rc = descend_sweep(ctx, "mlt_predict_tree_sweep", lv, org, pred, cfg->poc, qps, Q, (cfg->flags & MLT_TREE_BY_CANDIDATES) != 0,
+  if ((rc = descend_sweep(ctx, "mlt_predict_tree_sweep", lv, W, H, 1, &one, qps, Q, (cfg->flags & MLT_TREE_BY_CANDIDATES) != 0,
                           TreeWant{leaf_maps_opt != nullptr, logits_opt != nullptr, dec_opt != nullptr, cand_opt != nullptr}, d)))
     return rc;
-  // ---- union -> one slice per point: rank, pack, then everything the caller asked for and one synchronisation ----
-  const Lay::TreeSweepArena::Ptrs &A = d.A;
-  TreeSweepPackArgs pa{};
-  pa.nodes = A.nodes; pa.alive = A.alive; pa.desc = A.desc; pa.dec = A.dec; pa.logits = A.logits; pa.cand = A.cand;
-  pa.idx = A.idx; pa.total = A.total; pa.first_node = A.first_node; pa.union_nodes = A.union_nodes;
-  pa.o_nodes = A.o_nodes; pa.o_logits = A.o_logits; pa.o_dec = A.o_dec; pa.o_cand = A.o_cand;
-  pa.n_qps = Q; pa.n_levels = lv.L; pa.node_cap = max_nodes; pa.out_cap = (int)cap_all;
-  long long un = 0;
-  for (int l = 0; l < lv.L; ++l) {
-    pa.lvl_start[l] = d.start[l]; pa.lvl_n[l] = d.n[l]; pa.lvl_cap[l] = d.cap[l]; pa.has_cand[l] = d.has_cand[l] ? 1 : 0;
-    pa.n_logits[l] = lv.st[l]->model.n_logits; pa.head_off[l] = lv.st[l]->head_off(); pa.head_classes[l] = lv.st[l]->head_classes();
-    un += d.n[l];
+  return sweep_results(ctx, "mlt_predict_tree_sweep", lv, d, 1, Q, max_nodes, nodes, first_node, union_nodes_opt, leaf_maps_opt, logits_opt, logit_stride, dec_opt, cand_opt);
+}
+
+int mlt_predict_trees_sweep(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture *pics, const mlt_tree_config *cfg, const int32_t *qps, int n_qps, mlt_tree_node *nodes,
+                            int node_cap, int32_t *first_node, int32_t *union_nodes_opt, uint8_t *leaf_maps_opt, float *logits_opt, int logit_stride, mlt_decision *dec_opt,
+                            mlt_candidates *cand_opt) {
+  if (!ctx) return MLT_ERR_ARG;
+  if (n_pictures < 1 || n_pictures > MLT_TREES_MAX_PICTURES || !pics || !cfg || cfg->struct_size != sizeof(mlt_tree_config) || !qps || n_qps < 1 ||
+      n_qps > MLT_SWEEP_MAX_QPS || !nodes || !first_node || (logits_opt && logit_stride < MLT_MAX_LOGITS) || (cfg->flags & ~MLT_TREE_BY_CANDIDATES)) {
+    ctx->err = "mlt_predict_trees_sweep: bad argument (1 .. 256 pictures, pics, cfg with struct_size = sizeof(mlt_tree_config), qps, 1 <= n_qps <= 32, nodes, first_node; "
+               "logit_stride >= 15)";
+    return MLT_ERR_ARG;
   }
-  {
-    Launch prof{ctx};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    // algorithmic bytes: the alive mask of every union node read and its index written under every point | per (point, node) at most one node record, its slab
-    // record and the requested rows and records, read and written
-    if ((rc = prof.prof_begin("tree_sweep_rank", 0.0, (double)Q * (double)un * 8, e0, e1))) return rc;
-    HIP_TRY(ctx, mlt_launch_tree_sweep_rank(pa, ctx->stream));
-    if ((rc = prof.prof_end(e1))) return rc;
-    const double per = 2.0 * sizeof(TreeNodeRec) + 12 + sizeof(DecisionRec) + (logits_opt ? 2.0 * kRowLogits * 4 : 0) + (dec_opt ? sizeof(DecisionRec) : 0) + (cand_opt ? 2.0 * sizeof(CandRec) : 0);
-    if ((rc = prof.prof_begin("tree_sweep_pack", 0.0, (double)Q * (double)un * per, e0, e1))) return rc;
-    HIP_TRY(ctx, mlt_launch_tree_sweep_pack(pa, ctx->stream));
-    if ((rc = prof.prof_end(e1))) return rc;
-  }
-  // the slices' sizes first: the copies below take exactly the packed nodes (the caller's arrays stay untouched behind them)
-  std::vector<int32_t> first((size_t)Q + 1), un_l(4);
-  HIP_TRY(ctx, hipMemcpyAsync(first.data(), A.first_node, ((size_t)Q + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(un_l.data(), A.union_nodes, 16, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const int total = first[(size_t)Q];
-  if (first[0] != 0 || total < 0 || total > cap_all) { ctx->err = "mlt_predict_tree_sweep: bad node count from the device"; return MLT_ERR_HIP; }
-  for (int q = 0; q < Q; ++q)
-    if (first[(size_t)q + 1] < first[(size_t)q]) { ctx->err = "mlt_predict_tree_sweep: bad node count from the device"; return MLT_ERR_HIP; }
-  if (total) {
-    HIP_TRY(ctx, hipMemcpyAsync(nodes, A.o_nodes, (size_t)total * sizeof(TreeNodeRec), hipMemcpyDeviceToHost, ctx->stream));
-    if (logits_opt) {   // whole zero-padded rows
-      if (logit_stride == kRowLogits) HIP_TRY(ctx, hipMemcpyAsync(logits_opt, A.o_logits, (size_t)total * kRowLogits * 4, hipMemcpyDeviceToHost, ctx->stream));
-      else HIP_TRY(ctx, hipMemcpy2DAsync(logits_opt, (size_t)logit_stride * 4, A.o_logits, (size_t)kRowLogits * 4, (size_t)kRowLogits * 4, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+  TreeLevels lv;
+  int rc;
+  if ((rc = tree_levels(ctx, "mlt_predict_trees_sweep", cfg, lv))) return rc;
+  const int P = n_pictures, Q = n_qps;
+  for (int p = 0; p < P; ++p) {
+    const mlt_picture *o = pics[p].org, *q = pics[p].pred;
+    char msg[192];
+    if (!o || !q || !owns_picture(ctx, o) || !owns_picture(ctx, q)) {
+      std::snprintf(msg, sizeof msg, "mlt_predict_trees_sweep: entry %d: both pictures must be given and belong to this context", p);
+      ctx->err = msg;
+      return MLT_ERR_ARG;
     }
-    if (dec_opt) HIP_TRY(ctx, hipMemcpyAsync(dec_opt, A.o_dec, (size_t)total * sizeof(DecisionRec), hipMemcpyDeviceToHost, ctx->stream));
-    if (cand_opt) HIP_TRY(ctx, hipMemcpyAsync(cand_opt, A.o_cand, (size_t)total * sizeof(CandRec), hipMemcpyDeviceToHost, ctx->stream));
+    if (o->width != q->width || o->height != q->height || o->width != pics[0].org->width || o->height != pics[0].org->height) {
+      std::snprintf(msg, sizeof msg, "mlt_predict_trees_sweep: entry %d: every picture of a call must have the width and height of entry 0's (%d x %d)", p,
+                    pics[0].org->width, pics[0].org->height);
+      ctx->err = msg;
+      return MLT_ERR_ARG;
+    }
+    for (int k = 0; k < Q; ++k) {   // the QP of entry p under point k
+      const long long qp = (long long)pics[p].qp + (long long)qps[k];
+      if (qp < INT32_MIN || qp > INT32_MAX) {
+        std::snprintf(msg, sizeof msg, "mlt_predict_trees_sweep: entry %d: its qp offset %d + qps[%d] = %d does not fit int32", p, pics[p].qp, k, qps[k]);
+        ctx->err = msg;
+        return MLT_ERR_ARG;
+      }
+    }
   }
-  if (leaf_maps_opt) HIP_TRY(ctx, hipMemcpyAsync(leaf_maps_opt, A.map, (size_t)Q * d.map_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  std::memcpy(first_node, first.data(), ((size_t)Q + 1) * 4);
-  if (union_nodes_opt) std::memcpy(union_nodes_opt, un_l.data(), 16);
-  return MLT_OK;
+  const int W = pics[0].org->width, H = pics[0].org->height;
+  const int max_nodes = mlt_tree_max_nodes(W, H, lv.top, lv.mn);
+  const long long cap_all = (long long)P * Q * max_nodes;
+  if (node_cap < cap_all || cap_all > 0x7fffffff) {
+    char msg[192];
+    std::snprintf(msg, sizeof msg, "mlt_predict_trees_sweep: node_cap %d is below %d x %d x mlt_tree_max_nodes = %d of a %d x %d picture", node_cap, P, Q, max_nodes, W, H);
+    ctx->err = msg;
+    return MLT_ERR_ARG;
+  }
+  // ---- arguments are good: the union descent runs on this context's own device (devices[0] of a multi-device context) ----
+  // one entry: its offset goes into the points (integers, as the sweep heads would add it) and the descent is mlt_predict_tree_sweep's
+  int32_t folded[MLT_SWEEP_MAX_QPS];
+  for (int k = 0; k < Q; ++k) folded[k] = P == 1 ? (int32_t)((long long)pics[0].qp + qps[k]) : qps[k];
+  SweepDescent d;
+  if ((rc = descend_sweep(ctx, "mlt_predict_trees_sweep", lv, W, H, P, pics, folded, Q, (cfg->flags & MLT_TREE_BY_CANDIDATES) != 0,
+                          TreeWant{leaf_maps_opt != nullptr, logits_opt != nullptr, dec_opt != nullptr, cand_opt != nullptr}, d)))
+    return rc;
+  return sweep_results(ctx, "mlt_predict_trees_sweep", lv, d, P, Q, max_nodes, nodes, first_node, union_nodes_opt, leaf_maps_opt, logits_opt, logit_stride, dec_opt, cand_opt);
 }
 
 #pragma GCC visibility pop

@@ -209,7 +209,7 @@ __device__ __forceinline__ uint32_t tree_point_cmask(const DecisionRec &d, const
   return nan ? (1u << head_classes) - 1u : 1u << d.raw_mode;
 }
 
-__device__ __forceinline__ void tree_sweep_write_node(const TreeSweepExpandArgs &a, int idx, int x, int y, int size, int depth, int flags, int parent, uint32_t alive) {
+__device__ __forceinline__ void tree_sweep_write_node(const TreeSweepExpandArgs &a, int idx, int pic, int x, int y, int size, int depth, int flags, int parent, uint32_t alive) {
   if (idx < 0 || idx >= a.node_cap) return;   // (the host sizes every level for a union that descends everywhere: never taken)
   TreeNodeRec r;
   r.x = x; r.y = y; r.size = (int16_t)size; r.depth = (int8_t)depth; r.flags = (uint8_t)flags;
@@ -217,20 +217,29 @@ __device__ __forceinline__ void tree_sweep_write_node(const TreeSweepExpandArgs 
   a.nodes[idx] = r;
   a.xy[2 * (size_t)idx] = x;
   a.xy[2 * (size_t)idx + 1] = y;
+  a.pic[idx] = pic;
   a.alive[idx] = alive;
   a.desc[idx] = 0u;
 }
 
+// The next level of the union of n_pictures entries is tree_expand_kernel's: with nr roots per entry, R_i the exclusive rank of descending node i over the WHOLE
+// level and D_p the rank at the start of entry p's segment, entry p's segment starts at next_start + p nr + 4 D_p and node i's children at
+// next_start + (p_i + 1) nr + 4 R_i; an empty segment takes the rank of the first non-empty segment behind it, or the level's total.  One entry: D_0 = 0.
 __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_sweep_kernel(const TreeSweepExpandArgs a) {
   __shared__ int wave_total[MLT_TREE_TILE / 64];
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, Q = a.n_qps, nr = a.n_next_roots, child_size = a.size >> 1;
+  __shared__ int seg_rank[MLT_TREES_MAX_PICTURES_K];       // D_p as published by the first node of a non-empty segment
+  __shared__ int seg_first[MLT_TREES_MAX_PICTURES_K + 1];  // D_p of every entry; [n_pictures] = the level's total
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, Q = a.n_qps, P = a.n_pictures, nr = a.n_next_roots, child_size = a.size >> 1;
   const uint32_t all = Q >= 32 ? 0xFFFFFFFFu : (1u << Q) - 1u;
+  const int32_t *cur_start = a.seg_start + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P, *cur_n = a.seg_n + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P;
   int base = 0;   // descending nodes of the tiles before this one (the same value in every thread)
   for (int t0 = 0; t0 < a.lvl_n; t0 += MLT_TREE_TILE) {
     const int i = t0 + tid;
     const bool in = i < a.lvl_n;
     const int node = a.lvl_start + (in ? i : 0);
     uint32_t dm = 0u;
+    int p = 0;
+    if (in) p = a.pic[node];
     if (in && a.descend_mask) {
       const uint32_t al = a.alive[node] & all;
       for (int q = 0; q < Q; ++q) {
@@ -257,13 +266,16 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_sweep_kernel(const 
     }
     __syncthreads();   // (the next tile overwrites wave_total)
     if (in) {
+      const int rank = base + woff + before;
+      const bool p_ok = (unsigned)p < (unsigned)P;
+      if (p_ok && node == cur_start[p]) seg_rank[p] = rank;   // the segment's first node: one writer per entry
       int first_child = -1;
-      if (desc) {
-        const int k = nr + 4 * (base + woff + before);
+      if (desc && p_ok) {
+        const int k = (p + 1) * nr + 4 * rank;
         if (k + 3 < a.next_cap && a.next_start + k + 3 < a.node_cap) {
           const int fc = first_child = a.next_start + k;
           const int x = a.xy[2 * (size_t)node], y = a.xy[2 * (size_t)node + 1];
-          for (int j = 0; j < 4; ++j) tree_sweep_write_node(a, fc + j, x + (j & 1) * child_size, y + (j >> 1) * child_size, child_size, a.lvl + 1, 0, node, dm);
+          for (int j = 0; j < 4; ++j) tree_sweep_write_node(a, fc + j, p, x + (j & 1) * child_size, y + (j >> 1) * child_size, child_size, a.lvl + 1, 0, node, dm);
         }
       }
       a.nodes[node].first_child = first_child;
@@ -272,13 +284,26 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_sweep_kernel(const 
     base += total;
   }
   if (!a.next_roots && !a.count) return;   // the last level
-  // the next level opens with the border roots (host-known, raster order): part of every tree
-  for (int r = tid; r < nr && r < a.next_cap; r += MLT_TREE_TILE)
-    tree_sweep_write_node(a, a.next_start + r, a.next_roots[2 * r], a.next_roots[2 * r + 1], child_size, a.lvl + 1, a.root_flags, -1, all);
-  if (tid == 0 && a.count) a.count[0] = nr + 4 * base;
+  __syncthreads();   // seg_rank is complete
+  if (tid <= P) {
+    int q = tid;
+    while (q < P && (a.lvl < 0 || cur_n[q] == 0)) ++q;
+    seg_first[tid] = q < P ? seg_rank[q] : base;
+  }
+  __syncthreads();
+  if (tid < P) {   // the next level's rows of the segment table
+    a.seg_start[(size_t)(a.lvl + 1) * P + tid] = a.next_start + tid * nr + 4 * seg_first[tid];
+    a.seg_n[(size_t)(a.lvl + 1) * P + tid] = nr + 4 * (seg_first[tid + 1] - seg_first[tid]);
+  }
+  // every entry's next segment opens with the border roots (host-known, raster order): part of every tree
+  for (int i = tid; i < P * nr; i += MLT_TREE_TILE) {
+    const int p = i / nr, r = i - p * nr, k = p * nr + 4 * seg_first[p] + r;
+    if (k < a.next_cap) tree_sweep_write_node(a, a.next_start + k, p, a.next_roots[2 * r], a.next_roots[2 * r + 1], child_size, a.lvl + 1, a.root_flags, -1, all);
+  }
+  if (tid == 0 && a.count) a.count[0] = P * nr + 4 * base;
 }
 
-// One work item per 16 x 16 block of every union node of the level; under a point the leaves are disjoint, and every point has a map of its own.
+// One work item per 16 x 16 block of every union node of the level; under a point the leaves are disjoint, and every (entry, point) has a map of its own.
 __global__ __launch_bounds__(256) void tree_sweep_raster_kernel(const TreeSweepRasterArgs a) {
   const size_t total = (size_t)a.lvl_n << (2 * a.blk_l), step = (size_t)gridDim.x * 256;
   const uint32_t all = a.n_qps >= 32 ? 0xFFFFFFFFu : (1u << a.n_qps) - 1u;
@@ -288,26 +313,28 @@ __global__ __launch_bounds__(256) void tree_sweep_raster_kernel(const TreeSweepR
     const uint32_t leaf = a.alive[node] & ~a.desc[node] & all;
     if (!leaf) continue;
     const TreeNodeRec &r = a.nodes[node];
-    const int mx = (r.x >> 4) + (b & ((1 << a.blk_l) - 1)), my = (r.y >> 4) + (b >> a.blk_l);
-    if (mx < 0 || my < 0 || mx >= a.map_w || my >= a.map_h) continue;   // (a node is a complete CU of the picture: never taken)
+    const int mx = (r.x >> 4) + (b & ((1 << a.blk_l) - 1)), my = (r.y >> 4) + (b >> a.blk_l), p = a.pic[node];
+    if (mx < 0 || my < 0 || mx >= a.map_w || my >= a.map_h || (unsigned)p >= (unsigned)a.n_pictures) continue;   // (a node is a complete CU of its entry's picture: never taken)
     for (int q = 0; q < a.n_qps; ++q)
       if ((leaf >> q) & 1u)
-        a.map[(size_t)q * a.map_bytes + (size_t)my * a.map_w + mx] = (uint8_t)(a.blk_l | ((a.dec[(size_t)q * (size_t)a.slab + (size_t)i].split_mode + 1) << 4));
+        a.map[((size_t)p * a.n_qps + q) * a.map_bytes + (size_t)my * a.map_w + mx] = (uint8_t)(a.blk_l | ((a.dec[(size_t)q * (size_t)a.slab + (size_t)i].split_mode + 1) << 4));
   }
 }
 
-// Workgroup q: the ordered scan of bit q of alive over every level's nodes, level after level (tree_expand_kernel's tile scan with the base carried on).
+// Workgroup p * n_qps + q: the ordered scan of bit q of alive over entry p's segment of every level, level after level (tree_expand_kernel's tile scan with the
+// base carried on).  Every union node belongs to one entry, so idx[q][node] has one writer.
 __global__ __launch_bounds__(MLT_TREE_TILE) void tree_sweep_rank_kernel(const TreeSweepPackArgs a) {
   __shared__ int wave_total[MLT_TREE_TILE / 64];
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, q = (int)blockIdx.x;
-  if (q >= a.n_qps) return;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, P = a.n_pictures;
+  if ((int)blockIdx.x >= P * a.n_qps) return;
+  const int p = (int)blockIdx.x / a.n_qps, q = (int)blockIdx.x - p * a.n_qps;
   int32_t *idx = a.idx + (size_t)q * (size_t)a.node_cap;
   int base = 0;
   for (int l = 0; l < a.n_levels && l < MLT_TREES_LEVELS; ++l) {
-    const int start = MLT_TREE_SEL(a.lvl_start, l), n = MLT_TREE_SEL(a.lvl_n, l);
+    const int start = a.seg_start[(size_t)l * P + p], n = a.seg_n[(size_t)l * P + p];
     for (int t0 = 0; t0 < n; t0 += MLT_TREE_TILE) {
       const int i = t0 + tid, node = start + i;
-      const bool in = i < n && node < a.node_cap;
+      const bool in = i < n && node >= 0 && node < a.node_cap;
       const bool on = in && ((a.alive[node] >> q) & 1u) != 0u;
       const unsigned long long b = __ballot(on);
       const int before = __popcll(b & ((1ull << lane) - 1ull));
@@ -324,21 +351,43 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void tree_sweep_rank_kernel(const Tr
       base += total;
     }
   }
-  if (tid == 0) a.total[q] = base;
+  if (tid == 0) a.total[blockIdx.x] = base;
 }
 
+#define MLT_TREE_SWEEP_MAX_SLICES (MLT_TREES_MAX_PICTURES_K * MLT_SWEEP_MAX_QPS_K)
+
 __global__ __launch_bounds__(256) void tree_sweep_pack_kernel(const TreeSweepPackArgs a) {
-  __shared__ int first[MLT_SWEEP_MAX_QPS_K + 1];
-  const int tid = (int)threadIdx.x, Q = a.n_qps;
-  if (tid <= Q && tid <= MLT_SWEEP_MAX_QPS_K) {
-    int f = 0;
-    for (int q = 0; q < tid; ++q) f += a.total[q];
-    first[tid] = f;
-    if (blockIdx.x == 0) a.first_node[tid] = f;
+  __shared__ int first[MLT_TREE_SWEEP_MAX_SLICES + 1];   // where slice p * n_qps + q starts: every workgroup sums the slices' totals for itself
+  __shared__ int part[256];
+  const int tid = (int)threadIdx.x, Q = a.n_qps, P = a.n_pictures;
+  const int S = P * Q <= MLT_TREE_SWEEP_MAX_SLICES ? P * Q : MLT_TREE_SWEEP_MAX_SLICES, per = (S + 255) / 256;
+  const int s_lo = tid * per < S ? tid * per : S, s_hi = s_lo + per < S ? s_lo + per : S;
+  {
+    int sum = 0;
+    for (int s = s_lo; s < s_hi; ++s) sum += a.total[s];
+    part[tid] = sum;
   }
-  if (blockIdx.x == 0 && tid < MLT_TREES_LEVELS) a.union_nodes[tid] = tid < a.n_levels ? MLT_TREE_SEL(a.lvl_n, tid) : 0;
   __syncthreads();
-  int un = 0;   // union nodes over all levels
+  {
+    int f = 0;
+    for (int t = 0; t < tid; ++t) f += part[t];
+    for (int s = s_lo; s < s_hi; ++s) {
+      first[s] = f;
+      if (blockIdx.x == 0) a.first_node[s] = f;
+      f += a.total[s];
+    }
+    if (s_lo < S && s_hi == S) {   // the thread of the last slice
+      first[S] = f;
+      if (blockIdx.x == 0) a.first_node[S] = f;
+    }
+  }
+  if (blockIdx.x == 0)
+    for (int t = tid; t < P * MLT_TREES_LEVELS; t += 256) {
+      const int p = t / MLT_TREES_LEVELS, l = t - p * MLT_TREES_LEVELS;
+      a.union_nodes[t] = l < a.n_levels ? a.seg_n[(size_t)l * P + p] : 0;
+    }
+  __syncthreads();
+  int un = 0;   // union nodes over all levels and entries
   for (int l = 0; l < a.n_levels && l < MLT_TREES_LEVELS; ++l) un += MLT_TREE_SEL(a.lvl_n, l);
   const size_t items = (size_t)Q * (size_t)un, step = (size_t)gridDim.x * 256;
   for (size_t it = (size_t)blockIdx.x * 256 + tid; it < items; it += step) {
@@ -347,8 +396,10 @@ __global__ __launch_bounds__(256) void tree_sweep_pack_kernel(const TreeSweepPac
     while (l + 1 < a.n_levels && u >= MLT_TREE_SEL(a.lvl_n, l)) { u -= MLT_TREE_SEL(a.lvl_n, l); ++l; }
     const int start = MLT_TREE_SEL(a.lvl_start, l), g = start + u;
     if (g >= a.node_cap || !((a.alive[g] >> q) & 1u)) continue;
+    const int p = a.pic[g];
+    if ((unsigned)p >= (unsigned)P) continue;   // (never taken)
     const int32_t *idx = a.idx + (size_t)q * (size_t)a.node_cap;
-    const int li = idx[g], dst = first[q] + li;
+    const int li = idx[g], dst = first[p * Q + q] + li;
     if (li < 0 || (unsigned)dst >= (unsigned)a.out_cap) continue;   // (never taken)
     const int cap = MLT_TREE_SEL(a.lvl_cap, l), nl = MLT_TREE_SEL(a.n_logits, l);
     const size_t slab0 = (size_t)Q * (size_t)start, e = slab0 + (size_t)q * (size_t)cap + (size_t)u;   // element (l, q, u): level l starts at node off[l] = start

@@ -9,7 +9,8 @@ tools/confidence_sweep.py evaluates on a call dump.
 with the device's tie and NaN rules; tools/candidate_sweep.py evaluates it on a call dump.
 
 `build_tree` restates the partition tree of a picture (include/mltcnn.h: mlt_predict_tree): levels, border roots, node order, descent rule and leaf map, with the
-network behind a callback -- the device's tree driven from the host, or any other decider's."""
+network behind a callback -- the device's tree driven from the host, or any other decider's.  `build_trees_sweep` restates the union descent of
+mlt_predict_trees_sweep (several entries, several points each) the same way; `build_tree_sweep` (mlt_predict_tree_sweep) is that with one entry."""
 from __future__ import annotations
 
 import numpy as np
@@ -207,46 +208,76 @@ def build_tree_sweep(width: int, height: int, top: int, min_size: int, descend_m
     point q's record); it descends in the union iff desc != 0 and its four children are alive under desc; roots are alive under every point.  Tree q is then
     the ordered compaction of every union level by bit q, parent / first_child renumbered inside the slice.
     -> ([(nodes TREE_NODE_DTYPE [n_q], leaf_map uint8 [height // 16, width // 16]) per point], union_nodes int32 [4]: union nodes per level from `top` down)."""
-    assert top in TREE_SIZES and min_size in TREE_SIZES and min_size <= top and 1 <= n_points <= 32
-    Q = n_points
+    (trees, counts), = build_trees_sweep(width, height, top, min_size, descend_mask, lambda size, pic, xy: decide(size, xy), 1, n_points, by_candidates=by_candidates)
+    return trees, counts
+
+
+def build_trees_sweep(width: int, height: int, top: int, min_size: int, descend_mask, decide, n_pictures: int, n_points: int, by_candidates: bool = False):
+    """The union descent of mlt_predict_trees_sweep restated on the host: the trees of n_pictures entries of one geometry under n_points points each from ONE
+    descent.  A level is one list over all entries -- entry 0's union segment (its border roots, then four children per node with desc != 0), entry 1's, ... --
+    and decide(size, pic_index, xy) -> (split_mode, confidence, cand_mask), each [n_points, n], gives the records of EVERY point for that list (pic_index [n]
+    int32, xy [n, 2] int32); it is called once per level with at least one node.  Inside an entry the rules are build_tree_sweep's.
+    -> [(trees, union_nodes) per entry], each as build_tree_sweep returns them."""
+    assert top in TREE_SIZES and min_size in TREE_SIZES and min_size <= top and 1 <= n_points <= 32 and n_pictures >= 1
+    P, Q = n_pictures, n_points
     levels = [s for s in TREE_SIZES if min_size <= s <= top]
     everyone = np.uint32((1 << Q) - 1)   # (Python integers: no shift by 32)
-    union = []           # per level: x, y, flags, parent (index in the previous level), alive, desc, first (index in the next level of the first child), records
-    prev = None
+    unions = [[] for _ in range(P)]      # per entry, per level: build_tree_sweep's level
     for size in levels:
         roots = tree_roots(width, height, top, size)
-        x, y = roots[:, 0].astype(np.int32), roots[:, 1].astype(np.int32)
-        parent = np.full(len(roots), -1, np.int64)
-        alive = np.full(len(roots), everyone, np.uint32)
-        flags = np.full(len(roots), 0 if size == top else 1, np.uint8)
-        if prev is not None:
-            par = np.flatnonzero(prev["desc"] != 0)
-            prev["first"][par] = len(roots) + 4 * np.arange(len(par))
-            j = np.tile(np.arange(4), len(par))   # z-order: TL, TR, BL, BR
-            x = np.concatenate([x, np.repeat(prev["x"][par], 4) + (j & 1) * size]).astype(np.int32)
-            y = np.concatenate([y, np.repeat(prev["y"][par], 4) + (j >> 1) * size]).astype(np.int32)
-            parent = np.concatenate([parent, np.repeat(par, 4)])
-            alive = np.concatenate([alive, np.repeat(prev["desc"][par], 4)]).astype(np.uint32)
-            flags = np.concatenate([flags, np.zeros(4 * len(par), np.uint8)])
-        n = len(x)
-        lvl = {"size": size, "x": x, "y": y, "flags": flags, "parent": parent, "alive": alive, "desc": np.zeros(n, np.uint32), "first": np.full(n, -1, np.int64)}
-        if n:
-            split, conf, cmask = (np.asarray(a).reshape(Q, n) for a in decide(size, np.stack([x, y], axis=1).astype(np.int32)))
-            lvl["split"], lvl["conf"], lvl["cmask"] = split.astype(np.int32), conf.astype(np.float32), cmask.astype(np.uint32)
-            if size > min_size:
-                mask = int((descend_mask or {}).get(size, 0)) or 2
-                for q in range(Q):
-                    if by_candidates:
-                        d = (lvl["cmask"][q] & np.uint32(mask)) != 0
-                    else:
-                        sm = lvl["split"][q].astype(np.int64)
-                        d = (sm >= 0) & (((mask >> np.clip(sm, 0, 31)) & 1) != 0)
-                    d &= ((alive >> np.uint32(q)) & np.uint32(1)) != 0
-                    lvl["desc"] |= (d.astype(np.uint32) << np.uint32(q)).astype(np.uint32)
-        union.append(lvl)
-        prev = lvl
+        segs = []
+        for p in range(P):
+            prev = unions[p][-1] if unions[p] else None
+            x, y = roots[:, 0].astype(np.int32), roots[:, 1].astype(np.int32)
+            parent = np.full(len(roots), -1, np.int64)
+            alive = np.full(len(roots), everyone, np.uint32)
+            flags = np.full(len(roots), 0 if size == top else 1, np.uint8)
+            if prev is not None:
+                par = np.flatnonzero(prev["desc"] != 0)
+                prev["first"][par] = len(roots) + 4 * np.arange(len(par))
+                j = np.tile(np.arange(4), len(par))   # z-order: TL, TR, BL, BR
+                x = np.concatenate([x, np.repeat(prev["x"][par], 4) + (j & 1) * size]).astype(np.int32)
+                y = np.concatenate([y, np.repeat(prev["y"][par], 4) + (j >> 1) * size]).astype(np.int32)
+                parent = np.concatenate([parent, np.repeat(par, 4)])
+                alive = np.concatenate([alive, np.repeat(prev["desc"][par], 4)]).astype(np.uint32)
+                flags = np.concatenate([flags, np.zeros(4 * len(par), np.uint8)])
+            n = len(x)
+            segs.append({"size": size, "x": x, "y": y, "flags": flags, "parent": parent, "alive": alive, "desc": np.zeros(n, np.uint32), "first": np.full(n, -1, np.int64),
+                         "split": np.zeros((Q, n), np.int32), "conf": np.zeros((Q, n), np.float32), "cmask": np.zeros((Q, n), np.uint32)})
+        total = sum(len(s["x"]) for s in segs)
+        if total:
+            xy = np.stack([np.concatenate([s["x"] for s in segs]), np.concatenate([s["y"] for s in segs])], axis=1).astype(np.int32)
+            pic = np.concatenate([np.full(len(s["x"]), p, np.int32) for p, s in enumerate(segs)])
+            split, conf, cmask = (np.asarray(a).reshape(Q, total) for a in decide(size, pic, xy))
+            at = 0
+            for lvl in segs:
+                n = len(lvl["x"])
+                lvl["split"], lvl["conf"], lvl["cmask"] = split[:, at:at + n].astype(np.int32), conf[:, at:at + n].astype(np.float32), cmask[:, at:at + n].astype(np.uint32)
+                at += n
+                if size > min_size and n:
+                    mask = int((descend_mask or {}).get(size, 0)) or 2
+                    for q in range(Q):
+                        if by_candidates:
+                            d = (lvl["cmask"][q] & np.uint32(mask)) != 0
+                        else:
+                            sm = lvl["split"][q].astype(np.int64)
+                            d = (sm >= 0) & (((mask >> np.clip(sm, 0, 31)) & 1) != 0)
+                        d &= ((lvl["alive"] >> np.uint32(q)) & np.uint32(1)) != 0
+                        lvl["desc"] |= (d.astype(np.uint32) << np.uint32(q)).astype(np.uint32)
+        for p in range(P):
+            unions[p].append(segs[p])
+    return [(_slices_of_union(unions[p], Q, width, height, levels), _union_counts(unions[p])) for p in range(P)]
+
+
+def _union_counts(union) -> np.ndarray:
     counts = np.zeros(4, np.int32)
     counts[:len(union)] = [len(l["x"]) for l in union]
+    return counts
+
+
+def _slices_of_union(union, Q: int, width: int, height: int, levels):
+    """Tree q of a union (build_tree_sweep's levels): the ordered compaction of every level by bit q of alive, parent / first_child renumbered inside the slice,
+    and its leaf map."""
     trees = []
     for q in range(Q):
         bit = lambda m: ((m >> np.uint32(q)) & np.uint32(1)) != 0
@@ -263,9 +294,9 @@ def build_tree_sweep(width: int, height: int, top: int, min_size: int, descend_m
             r = nodes[idx[l][on]]
             r["x"], r["y"], r["size"], r["depth"], r["flags"] = lvl["x"][on], lvl["y"][on], lvl["size"], l, lvl["flags"][on]
             p = lvl["parent"][on]
-            r["parent"] = np.where(p >= 0, idx[l - 1][np.maximum(p, 0)], -1) if l else -1
+            r["parent"] = np.where(p >= 0, idx[l - 1][np.maximum(p, 0)], -1) if l and (p >= 0).any() else -1
             down = bit(lvl["desc"][on])
-            r["first_child"] = np.where(down, idx[l + 1][np.maximum(lvl["first"][on], 0)], -1) if l + 1 < len(union) else -1
+            r["first_child"] = np.where(down, idx[l + 1][np.maximum(lvl["first"][on], 0)], -1) if l + 1 < len(union) and down.any() else -1
             r["split_mode"], r["confidence"], r["cand_mask"] = lvl["split"][q][on], lvl["conf"][q][on], lvl["cmask"][q][on]
             nodes[idx[l][on]] = r
         leaf_map = np.full((height // 16, width // 16), 0xFF, np.uint8)
@@ -276,4 +307,4 @@ def build_tree_sweep(width: int, height: int, top: int, min_size: int, descend_m
                 for dx in range(size // 16):
                     leaf_map[lv["y"] // 16 + dy, lv["x"] // 16 + dx] = val
         trees.append((nodes, leaf_map))
-    return trees, counts
+    return trees

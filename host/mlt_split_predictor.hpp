@@ -338,6 +338,44 @@ class SplitPredictor {
     return trees;
   }
 
+  // The partition trees of SEVERAL picture pairs of one geometry under several QPs each from one call (include/mltcnn.h: mlt_predict_trees_sweep): one descent
+  // over the unions of all entries, the conv trunk once per union node.  pics[p] = {org, pred, poc, qp OFFSET of the entry}; tree [p][q] is what predictTree
+  // returns for entry p with qp = pics[p].qp + qps[q].  unionNodesOpt: [pics.size()][4].  On failure every tree is EMPTY (the result still has one row per
+  // entry and one tree per QP).
+  std::vector<std::vector<PartitionTree>> predictTreesSweep(const std::vector<mlt_tree_picture> &pics, int width, int height, const std::vector<int32_t> &qps,
+                                                            int topSize = 128, int minSize = 16, bool byCandidates = false, int32_t *unionNodesOpt = nullptr) {
+    Timer tm(this, 0, 0);
+    const int P = (int)pics.size(), Q = (int)qps.size(), per = mlt_tree_max_nodes(width, height, topSize, minSize);
+    const long long slices = (long long)P * Q, cap = slices * per;
+    std::vector<std::vector<PartitionTree>> trees((size_t)P, std::vector<PartitionTree>((size_t)Q));
+    mlt_tree_config cfg{};
+    cfg.struct_size = (uint32_t)sizeof cfg;
+    cfg.top_size = topSize; cfg.min_size = minSize;
+    cfg.flags = byCandidates ? MLT_TREE_BY_CANDIDATES : 0u;
+    const int mapW = width / 16, mapH = height / 16;
+    const size_t mapBytes = (size_t)mapW * (size_t)mapH;
+    std::vector<mlt_tree_node> nodes;
+    std::vector<uint8_t> maps;
+    std::vector<int32_t> first((size_t)slices + 1, 0);
+    const bool sized = P >= 1 && P <= MLT_TREES_MAX_PICTURES && Q >= 1 && Q <= MLT_SWEEP_MAX_QPS && per > 0 && cap <= 0x7fffffff;
+    if (sized) { nodes.resize((size_t)cap); maps.assign((size_t)slices * mapBytes, (uint8_t)0xFF); }
+    if (!m_ctx || !sized || mlt_predict_trees_sweep(m_ctx, P, pics.data(), &cfg, qps.data(), Q, nodes.data(), (int)cap, first.data(), unionNodesOpt, maps.data(), nullptr, 0,
+                                                    nullptr, nullptr) != MLT_OK) {
+      std::fprintf(stderr, "error\n");  // EncCu.cpp:925
+      ++m_failed;
+      return trees;
+    }
+    for (long long s = 0; s < slices; ++s) {
+      PartitionTree &t = trees[(size_t)(s / Q)][(size_t)(s % Q)];
+      t.nodes.assign(nodes.begin() + first[(size_t)s], nodes.begin() + first[(size_t)s + 1]);
+      t.leafMap.assign(maps.begin() + (long)((size_t)s * mapBytes), maps.begin() + (long)(((size_t)s + 1) * mapBytes));
+      t.mapW = mapW; t.mapH = mapH;
+      for (const mlt_tree_node &nd : t.nodes)
+        if (nd.split_mode < 0) ++m_gated;
+    }
+    return trees;
+  }
+
   // The class indices a candidate record keeps, most probable first (classes[] holds up to 8); returns how many.
   static int keptClasses(const mlt_candidates &c, int classes[8]) {
     int n = 0;

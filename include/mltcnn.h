@@ -368,7 +368,7 @@ int mlt_predict_at(mlt_ctx *ctx, int size, const mlt_picture *org, const mlt_pic
  * size that is not loaded.  n == 0 returns MLT_OK.
  * Chunked by the context's pass size like the twins; the device entry blocks once per chunk for the guards' 4-byte count, the picture entry is synchronous and, on a
  * multi-device context, sharded (every device writes its range of every slab).  A sweep call with candidate records does NOT make deferred batches carry candidate
- * records.  Partition trees under several QPs: mlt_predict_tree_sweep below.  Not there: host-dense, single-CU and deferred forms, a sweep over poc. */
+ * records.  Partition trees under several QPs: mlt_predict_tree_sweep and (several pictures) mlt_predict_trees_sweep below.  Not there: host-dense, single-CU and deferred forms, a sweep over poc. */
 #define MLT_SWEEP_MAX_QPS 32
 int mlt_predict_batch_device_sweep(mlt_ctx *ctx, int n, int size, const void *d_org, const void *d_pred, const void *d_poc, const int32_t *qps /* HOST */, int n_qps,
                                    void *d_split_opt, void *d_logits_opt, void *d_decisions_opt, void *d_candidates_opt);
@@ -506,13 +506,44 @@ int mlt_predict_trees(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture *pics
  *           picture NULL, of another context or of another geometry); node_cap < n_qps * mlt_tree_max_nodes(width, height, top_size, min_size).
  *           MLT_ERR_SIZE_DISABLED: a size top..min is not loaded.  MLT_ERR_NOMEM: the device arena cannot be grown.  NULL ctx: MLT_ERR_ARG.
  * All arrays are HOST memory.  Synchronous.  On a multi-device context the call runs on devices[0] with a one-device context's bytes.
- * Not there: several pictures times several QPs in one call, a sweep over poc, an asynchronous form. */
+ * Several pictures times several QPs in one call: mlt_predict_trees_sweep below.  Not there: a sweep over poc, an asynchronous form. */
 int mlt_predict_tree_sweep(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pred, const mlt_tree_config *cfg,
                            const int32_t *qps /* HOST */, int n_qps,
                            mlt_tree_node *nodes, int node_cap, int32_t *first_node /* [n_qps + 1] */,
                            int32_t *union_nodes_opt /* [4]: nodes the network evaluated per level top.., 0 for levels below min_size */,
                            uint8_t *leaf_maps_opt /* [n_qps][height/16][width/16] */,
                            float *logits_opt, int logit_stride, mlt_decision *dec_opt, mlt_candidates *cand_opt);
+
+/* ---- Partition trees of SEVERAL picture pairs under SEVERAL QPs each in one call (new export; MLT_ABI_VERSION stays 4, no struct changes) ----
+ * A GOP in device memory and four base QPs: mlt_predict_trees' level-wide network passes over all pictures combined with mlt_predict_tree_sweep's union descent.
+ * ONE descent over the unions of all entries: per level one node list -- entry 0's union segment, entry 1's, ... -- one gather and one trunk pass per union node,
+ * the heads under every point, and n_pictures x n_qps trees carved out of the unions.
+ *
+ * ENTRIES   as mlt_predict_trees: 1 .. MLT_TREES_MAX_PICTURES pairs of ONE geometry, repeats allowed; an entry is the unit (entries that repeat a pair are not
+ *           merged).  pics[p].qp is the entry's QP OFFSET (an RA GOP does not code every frame at the base QP).  cfg->poc and cfg->qp are NOT read.
+ * POINTS    qps[0 .. n_qps) is a HOST array, 1 <= n_qps <= MLT_SWEEP_MAX_QPS, any values in any order, duplicates and negative values included.  The QP of
+ *           entry p under point q is pics[p].qp + qps[q]; the sum is formed in 64 bits and must fit int32.
+ * RESULT    slice s = p * n_qps + q is nodes[first_node[s] .. first_node[s + 1]); first_node[n_pictures * n_qps] is the total node count.  Slice s is BYTE FOR
+ *           BYTE what mlt_predict_tree returns for (pics[p].org, pics[p].pred) with cfg.poc = pics[p].poc and cfg.qp = pics[p].qp + qps[q] -- that is, slice s
+ *           of mlt_predict_trees over the n_pictures x n_qps entries {org_p, pred_p, poc_p, qp_p + qps[q]} in that order.  Leaf map s (leaf_maps_opt +
+ *           s * (height / 16) * (width / 16)), the decision and the candidate records are that call's; logits are whole 15-float rows, zeros behind
+ *           mlt_num_logits(size).
+ * UNION     union_nodes_opt[p * 4 + l], l = 0 at top_size: the number of distinct nodes of that level on which the network ran for entry p; 0 below min_size.
+ * GUARDS    confidence gate, candidate policy, the three guards and MLT_TREE_BY_CANDIDATES act per (entry, point) exactly as in mlt_predict_tree.  A union node
+ *           is re-evaluated with the exact arithmetic iff it is flagged under at least one point it is alive under; the exact results replace the fast ones in
+ *           those slabs only.  guard_reruns grows by the number of distinct (entry, node) pairs re-run: with a[p][q] what the single calls add,
+ *           sum_p max_q a[p][q] <= growth <= sum_{p, q} a[p][q].
+ * ERRORS    everything is checked before anything is enqueued and on any error every output stays untouched.  MLT_ERR_ARG: what mlt_predict_trees and
+ *           mlt_predict_tree_sweep check; pics[p].qp + qps[q] outside int32; n_pictures * n_qps * mlt_tree_max_nodes(...) (64 bits) beyond int32 or above
+ *           node_cap.  MLT_ERR_SIZE_DISABLED: a size top..min is not loaded.  MLT_ERR_NOMEM: the device arena cannot be grown.  NULL ctx: MLT_ERR_ARG.
+ * All arrays are HOST memory.  Synchronous.  On a multi-device context the call runs on devices[0] with a one-device context's bytes.
+ * Not there: a sweep over poc, per-picture point lists beyond the offset, pictures of different geometry in one call, an asynchronous form. */
+int mlt_predict_trees_sweep(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture *pics, const mlt_tree_config *cfg,
+                            const int32_t *qps /* HOST */, int n_qps,
+                            mlt_tree_node *nodes, int node_cap, int32_t *first_node /* [n_pictures * n_qps + 1] */,
+                            int32_t *union_nodes_opt /* [n_pictures][4] */,
+                            uint8_t *leaf_maps_opt /* [n_pictures][n_qps][height/16][width/16] */,
+                            float *logits_opt, int logit_stride, mlt_decision *dec_opt, mlt_candidates *cand_opt);
 
 int mlt_synchronize(mlt_ctx *ctx);
 

@@ -21,6 +21,12 @@ children, down to S (default 16); loads every size 128 .. S, writes `<out>_tree_
 network once per union node, the heads once per QP); --qp is not consulted and --frames does not go with it.  Writes `<out>_qp<QP>_tree_nodes.npy` and
 `<out>_qp<QP>_leafmap.npy` per QP and prints the nodes per level per QP and of the union.
 
+--tree --frames N --gop-qps 22,27,32,37 [--qp-offsets 0,3,4,3,...]: the trees of N frames under several base QPs each from ONE call (MltCnn.predict_trees_sweep:
+one descent over the unions of all frames, the network once per union node); frame f under base QP b runs at QP b + offset f (--qp-offsets: one integer per
+frame, default 0 for all; an RA GOP does not code every frame at the base QP); --qp is not consulted.  Writes `<out>_f<f>_qp<QP>_tree_nodes.npy` and
+`<out>_f<f>_qp<QP>_leafmap.npy` per (frame, QP), <QP> the frame's QP b + offset, and prints the nodes per level per (frame, QP) and of every frame's union.
+(--tree --frames N --tree-qps stays refused: --tree-qps is the one-frame form.)
+
 --qps 22,27,32,37 (without --tree): one map set PER QP from ONE sweep call per size (MltCnn.predict_at_sweep: the network runs once, the heads once per QP),
 written as `<out>_<S>_qp<QP>_split.npy` etc.; --qp is not consulted.  Combined with --tree it is refused: trees under several QPs are --tree-qps.
 
@@ -212,6 +218,25 @@ def run_tree_sweep(m, org: np.ndarray, pred: np.ndarray, poc: int, qps, min_size
         return m.predict_tree_sweep(pics[0][0], pics[0][1], poc, qps, top=128, min_size=min_size, want=("leaf_map",))
 
 
+def run_trees_sweep(m, org: np.ndarray, pred: np.ndarray, poc: int, qp_offsets, qps, min_size: int = 16) -> list:
+    """org / pred: [frames, height, width]; m: an MltCnn with tree_sizes(min_size) loaded -> result[frame][point], each {"nodes", "leaf_map", "first_node",
+    "union_nodes"}, all from ONE call (MltCnn.predict_trees_sweep); frame f takes poc + f and, under point q, QP qp_offsets[f] + qps[q]."""
+    assert org.ndim == 3
+    with uploaded(m, org, pred) as pics:
+        return m.predict_trees_sweep(pics, [poc + f for f in range(len(pics))], list(qp_offsets), qps, top=128, min_size=min_size, want=("leaf_map",))
+
+
+def parse_offsets(text: str, frames: int) -> tuple:
+    """"0,3,4,3" -> (0, 3, 4, 3): one integer per frame."""
+    try:
+        off = tuple(int(v) for v in text.split(",") if v.strip())
+    except ValueError:
+        raise ValueError(f"--qp-offsets {text}: want comma-separated integers") from None
+    if len(off) != frames:
+        raise ValueError(f"--qp-offsets {text}: want one value per frame ({frames}), got {len(off)}")
+    return off
+
+
 def save_tree(prefix: str, t: dict) -> None:
     np.save(f"{prefix}_tree_nodes.npy", t["nodes"])
     np.save(f"{prefix}_leafmap.npy", t["leaf_map"])
@@ -238,6 +263,8 @@ def parse_args(argv=None):
     ap.add_argument("--min-size", type=int, default=None, help="with --tree: the smallest CU size of the descent (default 16)")
     ap.add_argument("--frames", type=int, default=None, help="with --tree: the inputs hold this many frames; all trees from one call, --poc is the first frame's")
     ap.add_argument("--tree-qps", default=None, help="with --tree: comma-separated QPs, one tree per QP from one call (not with --frames)")
+    ap.add_argument("--gop-qps", default=None, help="with --tree --frames N: comma-separated base QPs, one tree per (frame, QP) from one call")
+    ap.add_argument("--qp-offsets", default=None, help="with --gop-qps: one QP offset per frame, comma-separated (default 0)")
     args = ap.parse_args(argv)
     sizes = tuple(int(s) for s in args.sizes.split(",") if s)
     if not sizes or any(s not in SIZES for s in sizes) or (args.weights_dir is None) == (args.synthetic is None):
@@ -262,6 +289,19 @@ def parse_args(argv=None):
             args.tree_qp_list = parse_qps(args.tree_qps)
         except ValueError as e:
             ap.error(str(e).replace("--qps", "--tree-qps"))
+    args.gop_qp_list, args.qp_offset_list = None, None
+    if args.gop_qps is not None:
+        if not args.tree or args.frames is None:
+            ap.error("--gop-qps goes with --tree --frames N")
+        try:
+            args.gop_qp_list = parse_qps(args.gop_qps)
+            args.qp_offset_list = parse_offsets(args.qp_offsets, args.frames) if args.qp_offsets is not None else (0,) * args.frames
+        except ValueError as e:
+            ap.error(str(e).replace("--qps", "--gop-qps"))
+        if any(not -2 ** 31 <= o + q < 2 ** 31 for o in args.qp_offset_list for q in args.gop_qp_list):
+            ap.error("--gop-qps / --qp-offsets: an offset + QP does not fit 32 bits")
+    elif args.qp_offsets is not None:
+        ap.error("--qp-offsets goes with --gop-qps")
     if args.tree:
         if args.min_size is None:
             args.min_size = 16
@@ -293,6 +333,18 @@ def main(argv=None):
         if args.coverage > 0 or args.max_modes > 0:
             m.set_candidate_policy(s, args.coverage, args.max_modes)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    if args.tree and args.gop_qp_list is not None:
+        res = run_trees_sweep(m, org, pred, args.poc, args.qp_offset_list, args.gop_qp_list, args.min_size)
+        for f, (off, row) in enumerate(zip(args.qp_offset_list, res)):
+            for qp, t in zip(args.gop_qp_list, row):
+                save_tree(f"{args.out}_f{f}_qp{qp + off}", t)
+                print(f"frame {f} (poc {args.poc + f}) qp {qp + off}: {len(t['nodes'])} nodes from node {t['first_node']}  " +
+                      "  ".join(f"{size}: {count} ({desc} descend)" for size, count, desc in tree_summary(t["nodes"])))
+            union = [int(v) for v in row[0]["union_nodes"]]
+            print(f"frame {f} union: {sum(union)} nodes evaluated for {sum(len(t['nodes']) for t in row)} nodes of {len(row)} trees  " +
+                  "  ".join(f"{size}: {count}" for size, count in zip(SIZES, union) if size >= args.min_size))
+        m.close()
+        return 0
     if args.tree and args.frames is not None:
         for f, t in enumerate(run_trees(m, org, pred, args.poc, args.qp, args.min_size)):
             save_tree(f"{args.out}_f{f}", t)
