@@ -22,6 +22,7 @@ const Tuning &tuning() {
     u.no_block_fusion = on("MLT_NO_BLOCK_FUSION");
     u.no_chain = on("MLT_NO_CHAIN") || u.no_block_fusion; u.no_chain_s2 = on("MLT_NO_CHAIN_S2"); u.no_c16 = on("MLT_NO_C16"); u.chain64 = !on("MLT_NO_CHAIN64");
     u.no_l0_s5 = on("MLT_NO_L0_S5");
+    u.no_xs_handoff = on("MLT_NO_XS_HANDOFF") || u.debug_dump_dir != nullptr;   // (the layer dumps are those of the sc hand-off)
     u.l0_stream_min = on("MLT_NO_L0_STREAM") ? 0 : (int)num("MLT_L0_STREAM_MIN", 128);
     u.l1_stream_min = on("MLT_NO_L1_STREAM") ? 0 : (int)num("MLT_L1_STREAM_MIN", 128);
     u.guard_wait_mode = on("MLT_GUARD_SPIN_WAIT") ? 1 : on("MLT_GUARD_BLOCKING_WAIT") ? 2 : 0;
@@ -286,8 +287,9 @@ int run_stem_block(mlt_ctx *ctx, const mlt::Model &m, int n, int S, const Planes
 
 // All of layer0 of 128 x 128 CUs in one launch (layer0_stream_kernel): bit-identical to run_stem_block + run_block32, b0 never reaches HBM.
 // c5 != nullptr: layer1.0.conv1 + shortcut ride along as a fifth stage (layer0_stream_kernel<true>): y is not written, t -> y_t (NHWC), sc -> y_sc (chunk-major)
+// xs (with c5, when run_layer1_stream(..., c5) follows): layer0_stream_xs_kernel -- y_sc receives the shortcut's input [n][32][32][32] instead, half the bytes
 int run_layer0_stream(mlt_ctx *ctx, const mlt::Model &m0, const mlt::Model &m1, int n, const Planes &pl, void *y, int32_t *d_flat, bool flat_is_clear,
-                      const mlt::PackedConv *c5, void *y_t, void *y_sc) {
+                      const mlt::PackedConv *c5, void *y_t, void *y_sc, bool xs) {
   const mlt::PackedConv &c2 = m0.blocks[0][0].conv2;
   const mlt::Block &B1 = m1.blocks[0][1];
   Layer0Args a{};
@@ -302,13 +304,13 @@ int run_layer0_stream(mlt_ctx *ctx, const mlt::Model &m0, const mlt::Model &m1, 
   const double px = (double)n * 64 * 64;
   Launch L{ctx};
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = c5 ? L.prof_begin("layer0_stream_h64(stem+layer0+layer1.0.conv1+sc)", 2.0 * px * 32 * (50 + 18 + 3 * 288) + 2.0 * (px / 4) * 64 * (288 + 32),
-                             (double)n * 128 * 128 * 4 + (px / 4) * 64 * 2 * 2, e0, e1)
+  int rc = c5 ? L.prof_begin("layer0_stream_h64(stem+layer0+layer1.0.conv1+sc)", 2.0 * px * 32 * (50 + 18 + 3 * 288) + 2.0 * (px / 4) * 64 * (288 + (xs ? 0 : 32)),
+                             (double)n * 128 * 128 * 4 + (px / 4) * (64 + (xs ? 32 : 64)) * 2, e0, e1, xs ? "xs hand-off" : nullptr)
               : L.prof_begin("layer0_stream_h64(stem+layer0.0+layer0.1)", 2.0 * px * 32 * (50 + 18 + 3 * 288), (double)n * 128 * 128 * 4 + px * 32 * 2, e0, e1);
   if (rc) return rc;
   const bool mfma32 = tuning().l0_mfma32;   // round 5's MFMA shape (A/B; the results are the same bits)
   plan_note(ctx, {{"y", c5 ? nullptr : y}, {"y_t", c5 ? y_t : nullptr}, {"y_sc", c5 ? y_sc : nullptr}, {"flat", d_flat}}, {{"flat_is_clear", flat_is_clear}, {"grid", grid_x}});
-  LAUNCH_TRY(ctx, mlt_launch_layer0_stream(a, c5 != nullptr, mfma32, grid_x, ctx->stream));
+  LAUNCH_TRY(ctx, mlt_launch_layer0_stream(a, c5 != nullptr, mfma32, xs, grid_x, ctx->stream));
   if ((rc = L.prof_end(e1))) return rc;
   if (c5) {
     if ((rc = debug_dump(ctx, "conv3x3_s2_32to64_h32+sc", y_t, (size_t)(px / 4) * 64 * 2))) return rc;
@@ -392,8 +394,12 @@ int run_chain3(mlt_ctx *ctx, const mlt::Block &B0, const mlt::Block &B1, int n, 
 
 // The three stride-1 convs of layer1 (64 channels at 32 x 32) as ONE streaming launch (layer1_stream_kernel): bit-identical to run_chain3's
 // 64-channel chain, weights resident in registers, b0 never in HBM.  t NHWC, sc chunk-major (what layer0_stream_kernel<true> / the stride-2 launch write).
-int run_layer1_stream(mlt_ctx *ctx, const mlt::Block &B0, const mlt::Block &B1, int n, const void *t, const void *sc, void *y, float *gap, bool y_c16) {
+// c5xs != nullptr (behind run_layer0_stream(..., xs)): layer1_stream_xs_kernel -- `sc` holds the shortcut's input and the launch computes the shortcut from
+// layer1.0.conv1's packed weights (tap 9), its shortcut biases and its accumulator scale
+int run_layer1_stream(mlt_ctx *ctx, const mlt::Block &B0, const mlt::Block &B1, int n, const void *t, const void *sc, void *y, float *gap, bool y_c16, const mlt::PackedConv *c5xs) {
   Layer1Args a{};
+  const bool xs = c5xs != nullptr;
+  if (xs) { a.w_sc = c5xs->d_w; a.bias_sc = c5xs->d_bias_sc; a.scale_sc = c5xs->acc_scale; }
   a.t = t; a.sc = sc; a.y = y; a.y_c16 = y_c16 ? 1 : 0; a.gap = gap; a.gap_slots = gap_slots(32 * 32); a.n = n;
   const mlt::PackedConv *pcs[3] = {&B0.conv2, &B1.conv1, &B1.conv2};
   for (int k = 0; k < 3; ++k) { a.w[k] = pcs[k]->d_w; a.bias[k] = pcs[k]->d_bias; a.scale[k] = pcs[k]->acc_scale; }
@@ -402,14 +408,15 @@ int run_layer1_stream(mlt_ctx *ctx, const mlt::Block &B0, const mlt::Block &B1, 
   const double px = (double)n * 32 * 32;
   Launch L{ctx};
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = L.prof_begin("layer1_stream_h32(conv2+conv1+conv2)", 3.0 * 2.0 * px * 64 * 64 * 9, px * 64 * 2 * 3 + 3.0 * 72 * 1024, e0, e1, y_c16 ? "single pass, y chunk-major, GAP" : "single pass, GAP");
+  int rc = L.prof_begin("layer1_stream_h32(conv2+conv1+conv2)", 3.0 * 2.0 * px * 64 * 64 * 9 + (xs ? 2.0 * px * 64 * 32 : 0.0), px * (64 * 2 + (xs ? 32 : 64)) * 2 + 3.0 * 72 * 1024 + (xs ? 4096.0 : 0.0), e0, e1,
+                        xs ? (y_c16 ? "xs hand-off, single pass, y chunk-major, GAP" : "xs hand-off, single pass, GAP") : y_c16 ? "single pass, y chunk-major, GAP" : "single pass, GAP");
   if (rc) return rc;
   // round 6: the 16x16x32 MFMA form exists (same bits) but measures 2 % SLOWER here than round 5's 32x32x16 form (0.882 against 0.863 ms, same box, alternating:
   // profiles/r06e_mfma16_ab.txt) -- the bare loop's +11 % is a clock effect at 1.6 GHz, this kernel already holds ~2.1 GHz and pays for twice the MFMA issue
   // slots and 8-byte epilogue accesses: it stays on 32x32x16 (MLT_TUNING=1 MLT_L1_MFMA16=1 selects the other form)
   const bool mfma32 = tuning().l1_mfma32;
   plan_note(ctx, {{"t", t}, {"sc", sc}, {"y", y}, {"gap", gap}}, {{"grid", grid_x}});
-  LAUNCH_TRY(ctx, mlt_launch_layer1_stream(a, mfma32, grid_x, ctx->stream));
+  LAUNCH_TRY(ctx, mlt_launch_layer1_stream(a, mfma32, xs, grid_x, ctx->stream));
   if ((rc = L.prof_end(e1))) return rc;
   return debug_dump(ctx, "chain3_s1_64_h32(conv2+conv1+conv2)", y, (size_t)px * 64 * 2);
 }
@@ -459,6 +466,7 @@ NetPlan plan_network(const mlt_ctx *ctx, const NetCfg &c, unsigned cls) {
   };
   bool cur_c16 = false;    // layout of the stage input
   bool l0_front = false;   // the layer0 streaming launch carried layer1.0.conv1 + shortcut
+  int l0_front_step = -1;  // ... and its place in the plan
   for (int s = 0; s < m.n_stages; ++s) {
     const bool last = s == m.n_stages - 1;
     const mlt::Model &ms = c.model_of(s, 0);  // first launch unit: layer0.0 / the stride-2 conv + shortcut
@@ -474,6 +482,7 @@ NetPlan plan_network(const mlt_ctx *ctx, const NetCfg &c, unsigned cls) {
       l0_front = !tn.no_l0_s5 && m.n_stages > 1 && !m10.exact && !m10.w2 && wants_chain(1) && !wants_s2(1) && m.planes[1] == 64 && !tn.no_c16 &&
                  c5.has_sc && c5.taps == 9 && c5.kc == 32 && c5.ct == 64 && c5.cin == 32 && c5.cout == 64 && c5.stride == 2;
       add(PlanStep::LAYER0_STREAM, 0).front = l0_front;
+      if (l0_front) l0_front_step = (int)P.size() - 1;
       continue;
     }
     if (fused_b0) add(PlanStep::STEM_BLOCK, 0);   // raw planes -> b0 in ONE kernel (t and sc never leave the chip)
@@ -498,6 +507,10 @@ NetPlan plan_network(const mlt_ctx *ctx, const NetCfg &c, unsigned cls) {
                             q2.taps == 9 && q2.kc == 64 && q2.ct == 64 && !last;
         PlanStep &st = add(stream ? PlanStep::LAYER1_STREAM : PlanStep::CHAIN, s);
         st.inside_s2 = chain_s2; st.x_c16 = cur_c16; st.sc_c16 = sc_c16; st.y_c16 = out_c16;
+        // the five-stage front followed by layer1's streaming launch, both in their shipped MFMA shapes: the front hands over the shortcut's INPUT (half
+        // the bytes) and layer1's loader waves compute the shortcut (layer0_stream_xs_kernel -> layer1_stream_xs_kernel; same bits).  Every other
+        // consumer of the front's sc -- the 64-channel chain -- and every other producer of layer1's sc -- the stride-2 launch -- keeps the sc hand-off.
+        if (stream && l0_front && l0_front_step >= 0 && !tn.no_xs_handoff && !tn.l0_mfma32 && tn.l1_mfma32) st.xs = P[(size_t)l0_front_step].xs = true;
         cur_c16 = out_c16;
         continue;
       }
@@ -590,7 +603,7 @@ int run_network(mlt_ctx *ctx, SizeState &st, const NetCfg &c, int n, const PassI
     }
     case PlanStep::LAYER0_STREAM:
       rc = run_layer0_stream(ctx, ms, mt, n, io.pl, outs[0], go.d_flat, go.flat_is_clear,
-                             ps.front ? &c.model_of(1, 0).blocks[1][0].conv1 : nullptr, pool[0], pool[1]);
+                             ps.front ? &c.model_of(1, 0).blocks[1][0].conv1 : nullptr, pool[0], pool[1], ps.front && ps.xs);
       break;
     case PlanStep::STEM_BLOCK:
       rc = run_stem_block(ctx, ms, n, S, io.pl, pool[2], go.d_flat, go.flat_is_clear);
@@ -611,7 +624,7 @@ int run_network(mlt_ctx *ctx, SizeState &st, const NetCfg &c, int n, const PassI
                       ps.x_c16, ps.y_c16, pool[2], ps.sc_c16);
       break;
     case PlanStep::LAYER1_STREAM:
-      rc = run_layer1_stream(ctx, mt.blocks[s][0], mt.blocks[s][1], n, pool[0], pool[1], outs[s], gaps[s], ps.y_c16);
+      rc = run_layer1_stream(ctx, mt.blocks[s][0], mt.blocks[s][1], n, pool[0], pool[1], outs[s], gaps[s], ps.y_c16, ps.xs ? &c.model_of(1, 0).blocks[1][0].conv1 : nullptr);
       break;
     case PlanStep::CONV_B0C2:
       cv.x = pool[0]; cv.y = pool[2]; cv.res = pool[1]; cv.relu = true;  // b0 = relu(bn2(conv2 t) + sc)

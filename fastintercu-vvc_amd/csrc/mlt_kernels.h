@@ -121,15 +121,21 @@ struct Layer0Args {
   const void *w5;
   const float *bias5, *bias5_sc;
   void *y_t, *y_sc;            // t [n][32][32][64] fp16 NHWC; sc chunk-major [n][4][1024][16] (ConvArgs.ysc_c16: what the 64-channel chain reads)
+                               // layer0_stream_xs_kernel: y_sc receives xs [n][32][32][32] fp16 = out[2Y][2X][.] instead (Layer1Args.sc)
   float scale5;
 };
 
 // The three stride-1 convs of layer1 (64 channels at 32 x 32) as a streaming pipeline (layer1_stream_kernel, round 5): chain_kernel<64>'s
 // arithmetic, weights resident in registers, rows through LDS rings, b0 never in HBM.
 #define MLT_L1_LDS_BYTES 159008  /* rings of 4 / 8 / 4 map rows + zero row (34 px x 144 B), 2 sc rows, 16 accumulator hand-over blocks of 4 KiB, biases */
+#define MLT_L1X_LDS_BYTES 159264 /* layer1_stream_xs_kernel: + the shortcut's 64 biases */
 struct Layer1Args {
   const void *t;               // [n][32][32][64] fp16 NHWC: relu(bn1(conv1 x)) of layer1.0
   const void *sc;              // the projection shortcut, chunk-major [n][4][1024][16] fp16 (ConvArgs.ysc_c16)
+                               // layer1_stream_xs_kernel: its INPUT xs [n][32][32][32] fp16 (layer0's output at even rows and columns) and, to compute it here,
+  const void *w_sc;            // ... layer1.0.conv1's packed weights (Layer0Args.w5: the shortcut is their tap 9),
+  const float *bias_sc;        // ... the shortcut's 64 folded BN biases
+  float scale_sc;              // ... and that conv's accumulator scale (Layer0Args.scale5)
   const void *w[3];            // layer1.0.conv2, layer1.1.conv1, layer1.1.conv2: packed fp16 (ct 64, kc 64: 72 KiB each)
   const float *bias[3];
   float scale[3];
@@ -454,7 +460,8 @@ bool mlt_conv_cfg(int cin, int cout, int stride, int exact, ConvCfg *out);
 hipError_t mlt_launch_stem5(const Stem5Args &a, int nsplit, int grid_x, int lds, hipStream_t st);  // nsplit as mlt_launch_conv
 hipError_t mlt_launch_block32(const Block32Args &a, bool w2, int grid_x, hipStream_t st);     // w2: hi+lo weights (8 x 32 tiles)
 hipError_t mlt_launch_stem_block(const StemBlockArgs &a, bool w2, int grid_x, hipStream_t st);
-hipError_t mlt_launch_layer0_stream(const Layer0Args &a, bool fuse5, bool mfma32, int grid_x, hipStream_t st);
-hipError_t mlt_launch_layer1_stream(const Layer1Args &a, bool mfma32, int grid_x, hipStream_t st);
+// xs: the pair layer0_stream_xs_kernel -> layer1_stream_xs_kernel (the shortcut's input is handed over and layer1 computes the shortcut); both or neither
+hipError_t mlt_launch_layer0_stream(const Layer0Args &a, bool fuse5, bool mfma32, bool xs, int grid_x, hipStream_t st);
+hipError_t mlt_launch_layer1_stream(const Layer1Args &a, bool mfma32, bool xs, int grid_x, hipStream_t st);
 hipError_t mlt_launch_heads(const HeadArgs &a, int n, hipStream_t st);
 hipError_t mlt_launch_heads_sweep(const HeadSweepArgs &a, int n, hipStream_t st);

@@ -802,14 +802,28 @@ template <bool F5, bool M16> static hipError_t launch_layer0_stream_t(const Laye
 // The four-stage form (fuse5 = false: weight sets whose layer1 does not open on the single pass) stays on 32x32x16: its 16x16x32 build reloads three of S2's
 // weight fragments from scratch every row (S2 carries two accumulator sets; the five-stage form's register allocation comes out without that), and it
 // was the five-stage form the A/B measured.
-hipError_t mlt_launch_layer0_stream(const Layer0Args &a, bool fuse5, bool mfma32, int grid_x, hipStream_t st) {
+// xs: the five-stage 16x16x32 form that hands layer1_stream_xs_kernel the shortcut's input instead of the shortcut (a new symbol over the shared body).
+hipError_t mlt_launch_layer0_stream(const Layer0Args &a, bool fuse5, bool mfma32, bool xs, int grid_x, hipStream_t st) {
+  if (xs) {
+    if (!fuse5 || mfma32) return hipErrorInvalidValue;
+    static DeviceOnce once;
+    if (hipError_t e = ensure_big_lds(layer0_stream_xs_kernel, once); e != hipSuccess) return e;
+    hipLaunchKernelGGL(layer0_stream_xs_kernel, dim3(grid_x), dim3(1024), MLT_L0F_LDS_BYTES, st, a);
+    return hipGetLastError();
+  }
   if (fuse5) return mfma32 ? launch_layer0_stream_t<true, false>(a, grid_x, st) : launch_layer0_stream_t<true, true>(a, grid_x, st);
   return launch_layer0_stream_t<false, false>(a, grid_x, st);
 }
 
-hipError_t mlt_launch_layer1_stream(const Layer1Args &a, bool mfma32, int grid_x, hipStream_t st) {
-  static DeviceOnce once[2];
-  if (mfma32) {  // round 5's form on v_mfma_f32_32x32x16_f16 (MLT_TUNING=1 MLT_L1_MFMA32=1: same-box A/B; same bits)
+hipError_t mlt_launch_layer1_stream(const Layer1Args &a, bool mfma32, bool xs, int grid_x, hipStream_t st) {
+  static DeviceOnce once[3];
+  if (xs) {      // behind layer0_stream_xs_kernel: a.sc holds the shortcut's input, the loader waves compute the shortcut (32x32x16 form)
+    if (!mfma32 || !a.w_sc || !a.bias_sc) return hipErrorInvalidValue;
+    if (hipError_t e = ensure_big_lds(layer1_stream_xs_kernel, once[2]); e != hipSuccess) return e;
+    hipLaunchKernelGGL(layer1_stream_xs_kernel, dim3(grid_x), dim3(1024), MLT_L1X_LDS_BYTES, st, a);
+    return hipGetLastError();
+  }
+  if (mfma32) {  // the default: round 5's form on v_mfma_f32_32x32x16_f16 (MLT_TUNING=1 MLT_L1_MFMA16=1 selects the other; same bits)
     if (hipError_t e = ensure_big_lds(layer1_stream_kernel<false>, once[0]); e != hipSuccess) return e;
     hipLaunchKernelGGL(layer1_stream_kernel<false>, dim3(grid_x), dim3(1024), MLT_L1_LDS_BYTES, st, a);
     return hipGetLastError();

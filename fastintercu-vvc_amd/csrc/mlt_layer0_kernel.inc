@@ -53,8 +53,14 @@
 // lane): 18 + 18 fragments per row and 16 accumulator registers as before; a lane ends up with 4 consecutive channels of two pixels per cout block, so the
 // epilogues need TWO bias quads instead of four and write 8-byte pieces without permlane pairing.  S1 (five k = 16 steps per row + border steps) keeps the
 // 32x32x16 shape: its accumulators never meet another stage's.  M16 = false is round 5's form (MLT_TUNING=1 MLT_L0_MFMA32=1; A/B).
-template <bool F5, bool M16>
-__global__ __launch_bounds__(1024) void layer0_stream_kernel(const Layer0Args a) {
+// XS (the five-stage 16x16x32 form only; layer0_stream_xs_kernel): S5 hands layer1_stream_xs_kernel the INPUT of layer1's projection shortcut instead of
+// its output -- xs[Y][X][0..31] = out[2Y][2X][.], [n][32][32][32] fp16 in the first half of the sc buffer -- and that kernel's loader waves run the
+// shortcut's K = 32 product (mlt_layer1_kernel.inc).  The centre tap's activation fragment of pixel half hf that S5 re-read for the shortcut IS 16 bytes of
+// xs per lane (lane (p16, g4): channels 8 g4 .. 8 g4 + 7 of out[2Y][2 (16 hf + p16)]): S5 wave cb stores half hf = cb, one coalesced 1 KiB store per row, and
+// the shortcut's weight reads, MFMAs, epilogue and W5 are gone.  64 KiB per CU leave the chip instead of 128 KiB, and 64 instead of 128 come back.
+template <bool F5, bool M16, bool XS>
+__device__ __forceinline__ void layer0_stream_body(const Layer0Args &a) {
+  static_assert(!XS || (F5 && M16), "the xs hand-off exists for the five-stage 16x16x32 form");
   constexpr int PS = 80, RW = 66, ROWB = RW * PS;                // map rows: zero pixel, 64 pixels, zero pixel
   constexpr int NRT = F5 ? 6 : 8, NRB = 8, NRU = F5 ? 6 : 8, NRO = F5 ? 6 : 0;  // ring slots per map (live rows: 6 / 8 / 6 / 6)
   constexpr int RP = 136, RAWB = RP * 4, NRAW = 16;              // raw rows: 4 zero dwords, 128 (org, |org - pred|) fp16 pairs, 4 zero dwords
@@ -92,11 +98,11 @@ __global__ __launch_bounds__(1024) void layer0_stream_kernel(const Layer0Args a)
     BL[96 + tid] = a.bias4[tid];
     if constexpr (F5) {
       BL[128 + tid] = a.bias5[tid]; BL[160 + tid] = a.bias5[32 + tid];
-      BL[192 + tid] = a.bias5_sc[tid]; BL[224 + tid] = a.bias5_sc[32 + tid];
+      if constexpr (!XS) { BL[192 + tid] = a.bias5_sc[tid]; BL[224 + tid] = a.bias5_sc[32 + tid]; }
     }
   }
   if (wave < 4) *(uint4v *)(WB + wave * 1024 + lane * 16) = *(const uint4v *)((const char *)a.w + ((wave < 2 ? 7 : 3) + wave) * 1024 + lane * 16);
-  if (F5 && wave >= 4 && wave < 8) {   // W5[cb][ks] = A fragment of (tap 9, ks, cb)
+  if (F5 && !XS && wave >= 4 && wave < 8) {   // W5[cb][ks] = A fragment of (tap 9, ks, cb)
     const int cb = (wave - 4) >> 1, ks = (wave - 4) & 1;
     *(uint4v *)(W5 + (cb * 2 + ks) * 1024 + lane * 16) = *(const uint4v *)((const char *)a.w5 + ((18 + ks) * 2 + cb) * 1024 + lane * 16);
   }
@@ -663,11 +669,12 @@ __global__ __launch_bounds__(1024) void layer0_stream_kernel(const Layer0Args a)
           for (int q = 0; q < 4; ++q) acc[q >> 1][q & 1] = float4v{0.f, 0.f, 0.f, 0.f};
           static_for<18>([&](auto itc) {
             constexpr int item = decltype(itc)::value, tp = item >> 1, hf = item & 1, e = item - (18 - PD);   // e >= 0: extra read number e follows this item
-            lds_wait<((17 - item) < (PD - 1) ? (17 - item) : (PD - 1)) + (e > 0 ? e : 0)>();
+            lds_wait<((17 - item) < (PD - 1) ? (17 - item) : (PD - 1)) + (e > 0 ? (XS ? 1 : e) : 0)>();             // (XS: ONE extra read, behind item 18 - PD)
             lds_touch(bf[item % PD]);
             acc[0][hf] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[2 * tp], bf[item % PD], acc[0][hf], 0, 0, 0);
             acc[1][hf] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[2 * tp + 1], bf[item % PD], acc[1][hf], 0, 0, 0);
             if constexpr (item + PD < 18) rd(std::integral_constant<int, item + PD>{});
+            else if constexpr (XS) { if constexpr (e == 0) lds_read128<PS>(bf[item % PD], rows[1] + cb * (32 * PS)); }   // centre tap, pixel half cb: this wave's piece of xs
             else if constexpr (e < 2) lds_read128<(1 + 32 * e) * PS>(bf[item % PD], rows[1]);   // centre tap (dy 1, dx 1), pixel half e
             else lds_read128<(e - 2) * 256>(bf[item % PD], wsa);                                 // shortcut weights, cout block e - 2
           });
@@ -681,6 +688,10 @@ __global__ __launch_bounds__(1024) void layer0_stream_kernel(const Layer0Args a)
           for (int q = 0; q < 4; ++q)   // t: NHWC, couts cb * 32 + 16 c + 4 g .. of pixel 16 hf + p16
             *(half4 *)(cu_t + ot + 32 * (q >> 1) + 16 * 128 * (q & 1)) = act_quad<0>(acc[q >> 1][q & 1], a.scale5, *(const float4v *)(bl5 + 16 * (q >> 1)), false, none, true);
           lds_wait<0>();
+          if constexpr (XS) {   // xs [n][32][32][32]: row Y, pixels 16 cb .. 16 cb + 15, this lane's 8 channels
+            lds_touch(bf[(18 - PD) % PD]);
+            *(half8 *)((char *)a.y_sc + n * (size_t)(32 * 32 * 32 * 2) + (Y * 32 + 16 * cb) * 64 + p16 * 64 + g4 * 16) = bf[(18 - PD) % PD];
+          } else {
           static_for<PD>([&](auto ic) { lds_touch(bf[decltype(ic)::value]); });
           float4v accs[2][2];
           const float4v z4 = {0.f, 0.f, 0.f, 0.f};
@@ -689,6 +700,7 @@ __global__ __launch_bounds__(1024) void layer0_stream_kernel(const Layer0Args a)
 #pragma unroll
           for (int q = 0; q < 4; ++q)   // sc chunk-major ([n][64 / 16][32 x 32][16] fp16): chunk 2 cb + c, this lane's channels 4 g .. 4 g + 3
             *(half4 *)(cu_sc + os + (q >> 1) * (1024 * 32) + 16 * 32 * (q & 1)) = act_quad<0>(accs[q >> 1][q & 1], a.scale5, *(const float4v *)(bl5 + 64 + 16 * (q >> 1)), false, none, false);
+          }
         }
         L0_STEP_END();
         continue;
@@ -748,3 +760,6 @@ __global__ __launch_bounds__(1024) void layer0_stream_kernel(const Layer0Args a)
   }
 #undef L0_STEP_END
 }
+template <bool F5, bool M16>
+__global__ __launch_bounds__(1024) void layer0_stream_kernel(const Layer0Args a) { layer0_stream_body<F5, M16, false>(a); }
+__global__ __launch_bounds__(1024) void layer0_stream_xs_kernel(const Layer0Args a) { layer0_stream_body<true, true, true>(a); }   // five stages, 16x16x32, xs hand-off

@@ -30,8 +30,19 @@
 #ifndef CFG_L1_KO
 #define CFG_L1_KO 0      // measurement only (results wrong): 1 the epilogue waves do nothing, 2 no accumulator hand-over (first halves do not store, second halves start from zero), 4 loaders idle
 #endif
-template <bool M16>
-__global__ __launch_bounds__(1024) void layer1_stream_kernel(const Layer1Args a) {
+// XS (the 32x32x16 form only; layer1_stream_xs_kernel, behind layer0_stream_xs_kernel): `a.sc` holds xs -- the even pixels of the even rows of layer0's
+// output, [n][32][32][32] fp16 -- instead of the projection shortcut, and the two loader waves that carry no GAP sums (14, 15: cout block cb = wave - 14)
+// compute the shortcut row themselves: sc = bn(conv1x1 stride 2) is a K = 32 product, two chained 32x32x16 MFMAs from a zero accumulator on two A
+// fragments that stay in registers (tap 9 of the packed stride-2 weights) and the row's two B fragments straight from HBM (lane (p, h), k step ks: channels
+// 16 ks + 8 h .. + 7 of pixel p), then S5's epilogue expression and the 16-byte stores into the Sc slot that `commit` filled.  Same bits as S5's one
+// 16x16x32 MFMA (scripts/probes/mfma_shape_bits_probe.hip); the conv waves, the slot timing and the rings do not change.  The sc row of 128 B per pixel
+// neither leaves the front kernel nor comes back: 64 B per pixel do.
+// xs rows in flight: four register slots of two fragments.  Slots 0 / 1 hold the rows of steps k0, k0 + 1 of a step group and are re-issued, right after
+// their use, for steps k0 + 4, k0 + 5 (drained with the t rows at the group's end, three steps later); slots 2 / 3 are issued in the same two steps for
+// steps k0 + 2, k0 + 3 of the SAME group (two steps ahead, counted waits) -- every load is issued in the first half of a group, as the t rows are.
+template <bool M16, bool XS>
+__device__ __forceinline__ void layer1_stream_body(const Layer1Args &a) {
+  static_assert(!XS || !M16, "the xs hand-off exists for the 32x32x16 form");
   constexpr int PS = 144, RW = 34, ROWB = RW * PS;               // map rows: zero pixel, 32 pixels of 64 channels (+ 16 B), zero pixel
   constexpr int NRT = 4, NRB = 8, NRU = 4;                       // ring slots: t, b0 (also the last conv's residual), u
   constexpr int HB = 4096;                                       // one accumulator block in LDS: [quad 4][lane 64][16 B]
@@ -43,9 +54,9 @@ __global__ __launch_bounds__(1024) void layer1_stream_kernel(const Layer1Args a)
   char *Sc = Z + ROWB;                                           // sc rows, chunk-major as in HBM: [slot 2][chunk 4][pixel 32][32 B]
   char *Hd = Sc + 2 * 4096;                                      // accumulator hand-over: [link 4][cout block 2][slot 2][HB]; links: conv 0/1/2 first -> second half, conv 2 -> epilogue
   char *He = Hd + 3 * 2 * 2 * HB;                                // [cout block 2][slot 2][HE]
-  float *BL = (float *)(He + 2 * 2 * HE);                        // biases [conv 3][64]
+  float *BL = (float *)(He + 2 * 2 * HE);                        // biases [conv 3][64]; XS: + the shortcut's [64]
   constexpr int ZERO_BYTES = (NRT + NRB + NRU + 1) * ROWB + 2 * 4096;
-  static_assert(ZERO_BYTES % 16 == 0 && MLT_L1_LDS_BYTES == ZERO_BYTES + 3 * 2 * 2 * HB + 2 * 2 * HE + 3 * 64 * 4, "LDS layout");
+  static_assert(ZERO_BYTES % 16 == 0 && MLT_L1_LDS_BYTES == ZERO_BYTES + 3 * 2 * 2 * HB + 2 * 2 * HE + 3 * 64 * 4 && MLT_L1X_LDS_BYTES == MLT_L1_LDS_BYTES + 64 * 4, "LDS layout");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int p = lane & 31, h = lane >> 5;
@@ -54,6 +65,7 @@ __global__ __launch_bounds__(1024) void layer1_stream_kernel(const Layer1Args a)
   const int rows_total = 32 * nloc, ksteps = rows_total + 11;
   for (int o = tid * 16; o < ZERO_BYTES; o += 1024 * 16) *(uint4v *)(smem + o) = uint4v{0u, 0u, 0u, 0u};
   if (tid < 192) BL[tid] = a.bias[tid >> 6][tid & 63];
+  if (XS && tid >= 192 && tid < 256) BL[tid] = a.bias_sc[tid - 192];
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
   auto lds_of = [&](const char *q) -> uint32_t { return lds0 + (uint32_t)(q - smem); };
@@ -253,7 +265,38 @@ __global__ __launch_bounds__(1024) void layer1_stream_kernel(const Layer1Args a)
       for (int i = 0; i < NP; ++i) {
         const int ch = NP * li + i;
         tv[i] = *(const uint4v *)((const char *)a.t + (nt * 1024 + (size_t)(gt & 31) * 32) * 128 + ch * 1024 + lane * 16);
-        sv[i] = *(const uint4v *)((const char *)a.sc + (((ns * 4 + ch) << 10) + (size_t)(gs & 31) * 32) * 32 + lane * 16);
+        if constexpr (!XS) sv[i] = *(const uint4v *)((const char *)a.sc + (((ns * 4 + ch) << 10) + (size_t)(gs & 31) * 32) * 32 + lane * 16);
+      }
+    };
+    // XS, waves 14 / 15: the two B fragments of xs row k - 2 (unconditional and clamped, as above), and the shortcut row from them
+    const int cbx = li & 1;
+    half8 xa[2];
+    uint4v xr[RD][2];
+    auto issue_x = [&](uint4v (&xv)[2], int k) {
+      int gs = k - 2;
+      gs = gs < 0 ? 0 : gs < rows_total ? gs : rows_total - 1;
+      const size_t ns = (size_t)blockIdx.x + (size_t)(gs >> 5) * gridDim.x;
+      const char *src = (const char *)a.sc + ((ns * 1024 + (size_t)(gs & 31) * 32 + p) * 32 + 8 * h) * 2;
+      xv[0] = *(const uint4v *)src;
+      xv[1] = *(const uint4v *)(src + 32);
+    };
+    auto sc_row = [&](const uint4v (&xv)[2], int k) {
+      const int gs = k - 2;
+      if (gs >= 0 && gs < rows_total) {
+        float16v accs;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) accs[i] = 0.f;
+        accs = __builtin_amdgcn_mfma_f32_32x32x16_f16(xa[0], *(const half8 *)&xv[0], accs, 0, 0, 0);
+        accs = __builtin_amdgcn_mfma_f32_32x32x16_f16(xa[1], *(const half8 *)&xv[1], accs, 0, 0, 0);
+        const float *bl = BL + 3 * 64 + cbx * 32 + 4 * h;
+        char *dst = Sc + ((gs & 1) * 4 + 2 * cbx) * 1024 + p * 32 + 16 * h;   // chunks 2 cb / 2 cb + 1, this lane's 8 channels
+        static_for<2>([&](auto qc) {
+          constexpr int qq = decltype(qc)::value;
+          const half4 none{};
+          const half4 s0 = act_quad<2 * qq>(accs, a.scale_sc, *(const float4v *)(bl + 8 * (2 * qq)), false, none, false);
+          const half4 s1 = act_quad<2 * qq + 1>(accs, a.scale_sc, *(const float4v *)(bl + 8 * (2 * qq + 1)), false, none, false);
+          *(uint4v *)(dst + qq * 1024) = pair16(s0, s1);
+        });
       }
     };
     auto commit = [&](const uint4v (&tv)[NP], const uint4v (&sv)[NP], int k) {
@@ -262,7 +305,7 @@ __global__ __launch_bounds__(1024) void layer1_stream_kernel(const Layer1Args a)
       for (int i = 0; i < NP; ++i) {
         const int ch = NP * li + i;
         if (gt >= 0 && gt < rows_total) *(uint4v *)(Tr + (gt & (NRT - 1)) * ROWB + (8 * ch + (lane >> 3) + 1) * PS + (lane & 7) * 16) = tv[i];
-        if (gs >= 0 && gs < rows_total) *(uint4v *)(Sc + ((gs & 1) * 4 + ch) * 1024 + lane * 16) = sv[i];
+        if (!XS && gs >= 0 && gs < rows_total) *(uint4v *)(Sc + ((gs & 1) * 4 + ch) * 1024 + lane * 16) = sv[i];
       }
     };
     const int cb = li & 1, ch = lane & 31;
@@ -287,27 +330,56 @@ __global__ __launch_bounds__(1024) void layer1_stream_kernel(const Layer1Args a)
         a.gap[(n * a.gap_slots + r) * 64 + cb * 32 + ch] = x[0];
       }
     };
+    // XS: the loop exists twice, once per role (waves 12 / 13: t + GAP, waves 14 / 15: t + shortcut) -- a wave-uniform branch around the xs loads inside
+    // ONE loop makes the compiler's wait for a row count the younger loads of the path that issued none, and the counted waits become drains
+    auto loader = [&](auto xsc) {
+      constexpr bool X = decltype(xsc)::value;   // this wave computes the shortcut rows
 #pragma unroll
-    for (int d = 0; d < RD; ++d) issue(tc[d], sc_[d], d);
-    L1_STEP_END();
-    for (int k0 = 0; k0 < ksteps; k0 += RD) {
-      static_for<RD>([&](auto slc) {
-        constexpr int sl = decltype(slc)::value;
-        const int k = k0 + sl;
-        if (k >= ksteps) return;
-        if (!(CFG_L1_KO & 4)) commit(tc[sl], sc_[sl], k);
-        if constexpr (sl < RD / 2 && !(CFG_L1_KO & 4)) {
-          issue(tn[2 * sl], sn[2 * sl], k0 + RD + 2 * sl);
-          issue(tn[2 * sl + 1], sn[2 * sl + 1], k0 + RD + 2 * sl + 1);
-        }
-        gap_row(k);
-        L1_STEP_END();
-      });
+      for (int d = 0; d < RD; ++d) issue(tc[d], sc_[d], d);
+      if constexpr (X) {
 #pragma unroll
-      for (int d = 0; d < RD; ++d)
+        for (int ks = 0; ks < 2; ++ks) xa[ks] = *(const half8 *)((const char *)a.w_sc + ((18 + ks) * 2 + cbx) * 1024 + lane * 16);   // tap 9 of the packed stride-2 weights
+        asm volatile("" ::"v"(xa[0]), "v"(xa[1]));
+        issue_x(xr[0], 0);
+        issue_x(xr[1], 1);
+      }
+      L1_STEP_END();
+      // (X: whole step groups only, with no way round a slot -- a path on which slot 1 is skipped and slot 2 runs exists for the compiler, and on it the
+      // rows of slots 2 / 3 are the youngest loads: their waits came out as drains.  ksteps = 32 nloc + 11 leaves three steps, which touch no t / sc row.)
+      int k0 = 0;
+      for (; X ? k0 + RD <= ksteps : k0 < ksteps; k0 += RD) {
+        static_for<RD>([&](auto slc) {
+          constexpr int sl = decltype(slc)::value;
+          const int k = k0 + sl;
+          if constexpr (!X) { if (k >= ksteps) return; }
+          if (!(CFG_L1_KO & 4)) commit(tc[sl], sc_[sl], k);
+          if constexpr (sl < RD / 2 && !(CFG_L1_KO & 4)) {
+            issue(tn[2 * sl], sn[2 * sl], k0 + RD + 2 * sl);
+            issue(tn[2 * sl + 1], sn[2 * sl + 1], k0 + RD + 2 * sl + 1);
+          }
+          if constexpr (X && !(CFG_L1_KO & 4)) {
+            sc_row(xr[sl], k);
+            if constexpr (sl < RD / 2) {
+              issue_x(xr[RD / 2 + sl], k0 + RD / 2 + sl);   // (the nearer row first: its wait leaves the other one in flight)
+              issue_x(xr[sl], k0 + RD + sl);
+            }
+          }
+          if constexpr (!X) gap_row(k);
+          L1_STEP_END();
+        });
 #pragma unroll
-        for (int i = 0; i < NP; ++i) { tc[d][i] = tn[d][i]; sc_[d][i] = sn[d][i]; }
-    }
+        for (int d = 0; d < RD; ++d)
+#pragma unroll
+          for (int i = 0; i < NP; ++i) { tc[d][i] = tn[d][i]; sc_[d][i] = sn[d][i]; }
+      }
+      if constexpr (X)
+        for (; k0 < ksteps; ++k0) L1_STEP_END();   // k0 >= rows_total + 8: behind the last t row (k) and the last sc row (k - 2)
+    };
+    if (XS && li >= 2) loader(std::true_type{});
+    else loader(std::false_type{});
   }
 #undef L1_STEP_END
 }
+template <bool M16>
+__global__ __launch_bounds__(1024) void layer1_stream_kernel(const Layer1Args a) { layer1_stream_body<M16, false>(a); }
+__global__ __launch_bounds__(1024) void layer1_stream_xs_kernel(const Layer1Args a) { layer1_stream_body<false, true>(a); }   // 32x32x16, xs hand-off

@@ -44,6 +44,7 @@ struct Tuning {
   int wg_cap, wg_cap0, wg_cap1, wg_cap2;   // MLT_WG_CAP / _CAP0 / _CAP1 / _CAP2: persistent workgroups per launch (256 = one per CU)
   bool l0_mfma32, l1_mfma32;       // MLT_L0_MFMA32: layer0_stream_kernel on round 5's 32x32x16 MFMAs; layer1_stream_kernel runs them unless MLT_L1_MFMA16 (same bits either way)
   bool no_chain, no_chain_s2, no_c16, chain64, no_block_fusion, no_l0_s5;   // MLT_NO_CHAIN, _CHAIN_S2, _C16, _CHAIN64, _BLOCK_FUSION, _L0_S5: knock-outs of the fused forms
+  bool no_xs_handoff;              // MLT_NO_XS_HANDOFF (also set by MLT_DEBUG_DUMP_DIR): the streaming pair hands over layer1's shortcut (sc) instead of its input (xs); A/B, same bits
   int l0_stream_min, l1_stream_min;        // MLT_L0_STREAM_MIN / MLT_L1_STREAM_MIN (128; MLT_NO_L0_STREAM / MLT_NO_L1_STREAM: 0 = never)
   int guard_wait_mode;             // 0 sleep-then-poll, 1 MLT_GUARD_SPIN_WAIT, 2 MLT_GUARD_BLOCKING_WAIT
   bool no_small_mix, no_mag_guard, no_graph;   // MLT_NO_SMALL_MIX, MLT_NO_MAG_GUARD, MLT_NO_GRAPH (also set by MLT_DEBUG_DUMP_DIR)
@@ -77,7 +78,7 @@ struct NetCfg {   // the arithmetic of a pass: every launch unit takes its weigh
 struct PlanStep {
   enum Kind : uint8_t {
     FLAT_STAT,      // the flat-content statistic as a launch of its own (the first kernel does not read the raw planes as aligned quads)
-    LAYER0_STREAM,  // all of layer0 (front: + layer1.0.conv1 + shortcut) from the raw planes          -> out[0] | t = pool0, sc = pool1 (chunk-major)
+    LAYER0_STREAM,  // all of layer0 (front: + layer1.0.conv1 + shortcut) from the raw planes          -> out[0] | t = pool0, sc = pool1 (chunk-major; xs: its input)
     STEM_BLOCK,     // layer0.0 from the raw planes                                                      -> b0 = pool2
     STEM5,          // composed first layer: t, sc of layer0.0                                           -> pool0, pool1
     CONV_S2,        // stride-2 conv + shortcut that open stage s: stage input                           -> t = pool0, sc = pool1
@@ -91,6 +92,7 @@ struct PlanStep {
   } kind;
   int8_t s = 0;             // stage
   bool front = false;       // LAYER0_STREAM: layer1.0.conv1 + shortcut ride along
+  bool xs = false;          // LAYER0_STREAM (front) + the LAYER1_STREAM behind it: pool1 carries the shortcut's INPUT (xs), layer1's launch computes the shortcut
   bool inside_s2 = false;   // CHAIN: the stage's stride-2 conv + shortcut run inside the launch
   bool x_c16 = false;       // CHAIN (inside_s2): the stage input is chunk-major
   bool sc_c16 = false;      // CONV_S2 writes / CHAIN, LAYER1_STREAM read the shortcut chunk-major
