@@ -56,8 +56,20 @@ template <class T> __device__ __forceinline__ T karg_reload(size_t off) {
 //     tile top): every activation is converted ONCE per conv.  (First form of this kernel: each item converted its fp16 fragment in
 //     registers -- v_cvt_scalef32_pk_fp8_f16 nine times per activation -- and the conversions ate the whole gain: 1.57 ms against 1.26 with
 //     them knocked out.)  Per accumulator: hi k-steps 0..3 of a tap, then its lo product.
-template <int C, int HL, int SPW_L, int WCB, int WPB, int WAVES_C, int WAVES_P, int GT, int RB, int FD, int MINW, int NCONV, bool SPLIT_ROLES, bool S2 = false, bool KEEP = true, bool OOBZ = false, bool W2 = false, bool LO8 = false>
-__global__ __launch_bounds__(64 * WAVES_C * WAVES_P, MINW) void chain_kernel(const ChainArgs a) {
+//   * WIDE (stage256_wide_kernel: the whole 256-channel stage, two cout passes): a wave carries the accumulators of BOTH cout passes -- its two 32-cout
+//     blocks in pass 0 and in pass 1, 128 couts x 32 pixels -- so one activation fragment feeds four MFMAs instead of two being read once per pass
+//     (fragment reads per two MFMAs 3 -> 2.5), and every stride-2 input patch is staged ONCE per tile instead of once per pass.  Ring steps keep
+//     their bytes, their number and their MFMAs per wave, cut the other way:
+//       stride-1 convs: a step is 6 consecutive (tap, k16) items of a 64-channel chunk for both passes -- two contiguous 24 KiB runs of the packing
+//         [pass][chunk][tap][k16][4 blocks][1 KiB] -- 6 steps per chunk, 24 per conv; every second step starts in the middle of a tap, and a step PAIR
+//         (12 items = 3 taps) is unrolled statically;
+//       stride-2 phase: a step is taps 0-4 or taps 5-9 (the shortcut tap included) of a 16-channel chunk for both passes -- two contiguous 20 KiB
+//         runs of s2_w; patch c serves steps 2c and 2c + 1 (8 patch DMAs per tile instead of 16), three patch buffers, patch c in buffer c % 3,
+//         requested at step 2c - 4.
+//     Per accumulator the order is still (chunk, tap, k16): every logit keeps its bytes.  Both passes end together, so no tile is held back in
+//     registers (hold0 / hold) while the other pass still reads the buffer.
+template <int C, int HL, int SPW_L, int WCB, int WPB, int WAVES_C, int WAVES_P, int GT, int RB, int FD, int MINW, int NCONV, bool SPLIT_ROLES, bool S2 = false, bool KEEP = true, bool OOBZ = false, bool W2 = false, bool LO8 = false, bool WIDE = false>
+__device__ __forceinline__ void chain_body(const ChainArgs &a) {
   constexpr int KC = 64, NCHUNK = C / KC, KS = KC / 16, SLOTS = KC / 8, TAPS = 9, NG = (TAPS + GT - 1) / GT, GT_LAST = TAPS - (NG - 1) * GT;  // a last, shorter tap group when GT does not divide 9
   constexpr int CBT = WCB * WAVES_C, CT = 32 * CBT, NPASS = C / CT, NW = WAVES_C * WAVES_P;
   constexpr int H = 1 << HL, HW = H * H, M = HW << SPW_L;
@@ -93,7 +105,14 @@ __global__ __launch_bounds__(64 * WAVES_C * WAVES_P, MINW) void chain_kernel(con
   // (landing in [ACT, ACT + WCHUNK) meanwhile) cannot overlap.
   constexpr int NPB = 3 * PBYTES <= SOFF0 ? 3 : 2, PLA = NPB - 1;
   auto pbuf = [](int i) { return NPB == 3 ? i % 3 : (i + 1) & 1; };
-  static_assert(!S2 || (NPB == 3 ? (NS - 1) % 3 == 0 : (NS - 1) % 2 == 1), "S2: the last stride-2 step must read patch buffer 0");
+  static_assert(!S2 || WIDE || (NPB == 3 ? (NS - 1) % 3 == 0 : (NS - 1) % 2 == 1), "S2: the last stride-2 step must read patch buffer 0");
+  // WIDE: items of a stride-1 step, taps of a stride-2 step, LDS distance of the two passes' runs inside a step of either kind
+  constexpr int WI = 6, NG6 = TAPS * KS / WI, WHALF = WCHUNK / 2, TH = TAPS_S / 2, WHALF_S = WSTEP_S / 2;
+  static_assert(!WIDE || (NPASS == 2 && S2 && KEEP && OOBZ && !W2 && NCONV == 3 && GT == 3 && KS == 4 && FD == 1 && 2 * WI == GT * KS && NG6 * WI == TAPS * KS),
+                "WIDE: the whole 256-channel stage, conv padding from beyond the LDS, fragment reads one item ahead");
+  // (the last stride-2 step reads buffer (NCS - 1) % 3 while the first chain step's weights land in [ACT, ACT + WCHUNK): no patch buffer reaches that far)
+  static_assert(!WIDE || (NPB == 3 && NCS >= 3 && 3 * PBYTES <= ACT), "WIDE: three patch buffers, all below the chain's ring slot 0");
+  static_assert(!WIDE || (WHALF + ((WI - 1) * CBT + WCB - 1) * 1024 < 65536 && WHALF_S + ((TH - 1) * CBT + WCB - 1) * 1024 < 65536), "WIDE: fragment offsets are ds_read immediates");
   static_assert(!S2 || (SPLIT_ROLES && RB == 2 && NS % 2 == 0 && NCH % 2 == 0 && (NCS - 1) % 2 == 1), "S2: step parities");
   static_assert(!S2 || (2 * PBYTES <= SOFF0 && SOFF0 + WSTEP_S <= ACT + WCHUNK && SOFF1 + WSTEP_S <= 160 * 1024), "S2: LDS layout");
 
@@ -165,6 +184,15 @@ __global__ __launch_bounds__(64 * WAVES_C * WAVES_P, MINW) void chain_kernel(con
     const bool s_step = S2 && r_pos < NS;
     if (ring_wave) {
       if (s_step) {
+      } else if constexpr (WIDE) {  // items [WI * r_gi, WI * r_gi + WI) of chunk r_ci, pass 0 then pass 1: NPIECE / 2 pieces each
+        const char *wsrc = (const char *)(r_cv == 0 ? a.cv[0].w : r_cv == 1 ? a.cv[1].w : a.cv[2].w);
+        char *dst = ring + slot_wr * WCHUNK;
+#pragma unroll
+        for (int k = 0; k < PPWR; ++k) {
+          const int pi = wave + k * NWR, ps = pi / (NPIECE / 2), pw = pi - ps * (NPIECE / 2);
+          static_assert(!WIDE || NPIECE % NWR == 0, "every ring wave issues PPWR pieces");
+          glds16(wsrc + (size_t)((ps * NCHUNK + r_ci) * (TAPS * KS) + r_gi * WI) * (CBT * 1024) + pw * 1024 + lane16, dst + pi * 1024);
+        }
       } else {
         const char *wsrc = (const char *)(r_cv == 0 ? a.cv[0].w : r_cv == 1 ? a.cv[1].w : a.cv[NCONV > 2 ? 2 : 1].w);
         const char *src = wsrc + (size_t)((r_ps * NCHUNK + r_ci) * TAPS + r_gi * GT) * (KS * CBT * 1024);
@@ -189,14 +217,20 @@ __global__ __launch_bounds__(64 * WAVES_C * WAVES_P, MINW) void chain_kernel(con
 #pragma unroll
       for (int k = 0; k < (NPIECE_S + NW - 1) / NW; ++k) {
         const int pi = wave + k * NW;
-        if (pi < NPIECE_S) glds16(src + pi * 1024 + lane16, dst + pi * 1024);
+        if constexpr (WIDE) {  // step r_pos = (chunk r_pos / 2, taps 0-4 | taps 5-9), pass 0 then pass 1: NPIECE_S / 2 pieces each
+          const int ps = pi / (NPIECE_S / 2), pw = pi - ps * (NPIECE_S / 2);
+          const char *srcw = (const char *)a.s2_w + (size_t)((ps * NCS + (r_pos >> 1)) * TAPS_S + (r_pos & 1) * TH) * (CBT * 1024);
+          if (pi < NPIECE_S) glds16(srcw + pw * 1024 + lane16, dst + pi * 1024);
+        } else if (pi < NPIECE_S) glds16(src + pi * 1024 + lane16, dst + pi * 1024);
       }
     }
     --steps_to_issue;
     ++ahead;
     if (!s_step) {
       if (++slot_wr == NBUF) slot_wr = 0;
-      if (++r_gi == NG) { r_gi = 0; if (++r_ci == NCHUNK) { r_ci = 0; if (++r_ps == NPASS) { r_ps = 0; if (++r_cv == NCONV) r_cv = 0; } } }
+      if constexpr (WIDE) {
+        if (++r_gi == NG6) { r_gi = 0; if (++r_ci == NCHUNK) { r_ci = 0; if (++r_cv == NCONV) r_cv = 0; } }
+      } else if (++r_gi == NG) { r_gi = 0; if (++r_ci == NCHUNK) { r_ci = 0; if (++r_ps == NPASS) { r_ps = 0; if (++r_cv == NCONV) r_cv = 0; } } }
     }
     if (++r_pos == NS + NCH) r_pos = 0;
   };
@@ -380,6 +414,95 @@ __global__ __launch_bounds__(64 * WAVES_C * WAVES_P, MINW) void chain_kernel(con
         const int cb = pass * CT + (wc * WCB + i) * 32 + 16 * qq + 8 * h;
         *(uint4v *)(smem + (cb / KC) * REGION + pj[j] * (KC * 2) + ((((cb % KC) / 8) ^ swz(pj[j])) << 4)) = w;
       };
+      if constexpr (WIDE) {
+        // both cout passes at once: 8 accumulators; step si = 2 * chunk + hf carries taps [TH * hf, TH * hf + TH) of the chunk for both passes
+        float16v acc[NPASS][WCB][WPB], accs[NPASS][WCB][WPB];
+#pragma unroll
+        for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+          for (int i = 0; i < WCB; ++i)
+#pragma unroll
+            for (int j = 0; j < WPB; ++j)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) { acc[ps][i][j][r] = 0.f; accs[ps][i][j][r] = 0.f; }
+#pragma unroll 1
+        for (int chunk = 0; chunk < NCS; ++chunk) {
+          const uint32_t pb = lds0 + pbuf(chunk) * PBYTES;
+          static_for<2>([&](auto hc) {
+            constexpr int hf = decltype(hc)::value;
+            if constexpr (hf == 0) {
+              if (chunk >= 1 && chunk + PLA < NCS) patch_dma(t, chunk + PLA);  // into the buffer chunk - 1 has finished with
+            }
+            issue_ring();
+            {
+              const uint32_t wb = lds0 + (hf ? SOFF1 : SOFF0) + (wc * WCB) * 1024 + lane16;
+              half8 fa[2][NPASS][WCB], fb[2][WPB];
+              auto issue = [&](auto ic) {
+                constexpr int tl = decltype(ic)::value, sl = tl & 1, tt = TH * hf + tl;
+                constexpr int te = tt == 9 ? 4 : tt, dy = te / 3, dx = te % 3;  // the 1x1 stride-2 shortcut reads the centre tap's pixel
+                constexpr int off = dy * PCW + (dx == 1 ? H + 1 : dx / 2);
+                static_for<NPASS * WCB>([&](auto ii) {
+                  constexpr int ps = decltype(ii)::value / WCB, i = decltype(ii)::value % WCB;
+                  lds_read128<ps * WHALF_S + (tl * CBT + i) * 1024>(fa[sl][ps][i], wb);
+                });
+                static_for<WPB>([&](auto jj) {
+                  constexpr int j = decltype(jj)::value;
+                  const int qS = bS[j] + off;
+                  lds_read128<0>(fb[sl][j], pb + qS * (KCS * 2) + ((h ^ ((qS >> 3) & 1)) << 4));
+                });
+              };
+              issue(std::integral_constant<int, 0>{});
+              static_for<TH>([&](auto ic) {
+                constexpr int tl = decltype(ic)::value, sl = tl & 1, tt = TH * hf + tl;
+                if constexpr (tl + 1 < TH) issue(std::integral_constant<int, tl + 1>{});
+                lds_wait<(tl + 1 < TH ? NPASS * WCB + WPB : 0)>();
+#pragma unroll
+                for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+                  for (int i = 0; i < WCB; ++i) lds_touch(fa[sl][ps][i]);
+#pragma unroll
+                for (int j = 0; j < WPB; ++j) lds_touch(fb[sl][j]);
+#pragma unroll
+                for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+                  for (int i = 0; i < WCB; ++i)
+#pragma unroll
+                    for (int j = 0; j < WPB; ++j) {
+                      if constexpr (tt == 9) accs[ps][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[sl][ps][i], fb[sl][j], accs[ps][i][j], 0, 0, 0);
+                      else acc[ps][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[sl][ps][i], fb[sl][j], acc[ps][i][j], 0, 0, 0);
+                    }
+              });
+            }
+            PHC_MARK(1);
+            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");  // next weight step and (first half of a chunk) the patch requested above landed
+            PHC_MARK(2);
+            --ahead;
+          });
+        }
+        // every wave is past the last step's barrier: t = relu(bn1(conv)) -> activation buffer, sc = bn(shortcut) -> residual registers of conv 0
+        static_for<NPASS>([&](auto kp) {
+          constexpr int ps = decltype(kp)::value;
+#pragma unroll
+          for (int i = 0; i < WCB; ++i) {
+            float4v b1[4], bs[4];
+            bias_rows(pb_t[ps], i, b1);
+            bias_rows(pb_sc[ps], i, bs);
+#pragma unroll
+            for (int j = 0; j < WPB; ++j)
+              static_for<2>([&](auto qc) {
+                constexpr int qq = decltype(qc)::value;
+                half4 ht[2], hc[2];
+                const half4 none{};
+                ht[0] = act_quad<2 * qq>(acc[ps][i][j], a.s2_scale, b1[2 * qq], false, none, true);
+                ht[1] = act_quad<2 * qq + 1>(acc[ps][i][j], a.s2_scale, b1[2 * qq + 1], false, none, true);
+                hc[0] = act_quad<2 * qq>(accs[ps][i][j], a.s2_scale, bs[2 * qq], false, none, false);
+                hc[1] = act_quad<2 * qq + 1>(accs[ps][i][j], a.s2_scale, bs[2 * qq + 1], false, none, false);
+                keep[ps][i][j][qq] = pair16(hc[0], hc[1]);
+                put_t(ps, i, j, qq, pair16(ht[0], ht[1]));
+              });
+          }
+        });
+      } else
       static_for<NPASS>([&](auto kp) {
         constexpr int ps = decltype(kp)::value;
         float16v acc[WCB][WPB], accs[WCB][WPB];
@@ -491,6 +614,146 @@ __global__ __launch_bounds__(64 * WAVES_C * WAVES_P, MINW) void chain_kernel(con
       constexpr bool SAVE = KEEP && NCONV == 3 && cvi == 0;
       constexpr bool RES_LATE = !KEEP;  // residual loads after the last step's MFMA loop (the fragment registers are free then)
       uint4v hold[WCB][WPB][2];  // NPASS == 2: pass 0's activated tile until pass 1 has finished reading the buffer
+      // epilogue of the stage's last conv for cout pass kp: + bias + residual, ReLU -> HBM and / or GAP sums
+      auto std_epi = [&](auto kp, float16v(&acc)[WCB][WPB], uint4v(&resv)[WCB][WPB][2]) {
+        constexpr int ps = decltype(kp)::value;
+        float4v bq[WCB][4], bsq[1][4];
+#pragma unroll
+        for (int i = 0; i < WCB; ++i) {
+          if constexpr (PBIAS) bias_rows(pb_cv[cvi][ps], i, bq[i]);
+          else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) bq[i][q] = *(const float4v *)(cv.bias + ps * CT + (wc * WCB + i) * 32 + 4 * h + 8 * q);
+          }
+        }
+        ConvArgs ea{};
+        ea.y = a.y; ea.gap = a.gap; ea.gap_slots = a.gap_slots; ea.gap_l = a.gap_l; ea.acc_scale = cv.acc_scale; ea.relu = 1;
+        ea.y_c16 = a.y_c16; ea.hout_l = HL;
+        ea.res = RES ? (const void *)a.x : nullptr;  // non-NULL = "add resv"
+        float16v acc_sc[1][1];
+        uint4v resl[1][1][2];
+        if constexpr (RES == 2) {
+#pragma unroll
+          for (int i = 0; i < WCB; ++i)
+#pragma unroll
+            for (int j = 0; j < WPB; ++j)
+#pragma unroll
+              for (int qq = 0; qq < 2; ++qq) resv[i][j][qq] = keep[ps][i][j][qq];
+        }
+        int he = h, pe = p;
+        asm volatile("" : "+v"(he), "+v"(pe));  // nothing of the epilogue's lane arithmetic is hoisted out of the tile loop
+        conv_epilogue<C, CT, WCB, WPB, false, 1>(ea, ps, wc, he, pe, opix, gidx, acc, acc_sc, bq, bsq, resv, resl);
+      };
+      if constexpr (WIDE) {
+        // both cout passes at once: 4 accumulators.  A step is items [WI * s, WI * s + WI) of the chunk's 36 (tap, k16) items; the pair of steps
+        // (2g, 2g + 1) covers taps 3g .. 3g + 2 and is unrolled statically (item = position in the pair, hf = which step of the pair)
+        float16v acc[NPASS][WCB][WPB];
+#pragma unroll
+        for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+          for (int i = 0; i < WCB; ++i)
+#pragma unroll
+            for (int j = 0; j < WPB; ++j)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) acc[ps][i][j][r] = 0.f;
+#pragma unroll 1
+        for (int chunk = 0; chunk < NCHUNK; ++chunk) {
+          const uint32_t pl = lds0 + chunk * REGION;
+#pragma unroll 1
+          for (int g = 0; g < NG; ++g) {
+            static_for<2>([&](auto hc) {
+              constexpr int hf = decltype(hc)::value;
+              issue_ring();  // the step after this one, into the slot read one step ago
+              {
+                const uint32_t wb = lds0 + ACT + slot_rd * WCHUNK + (wc * WCB) * 1024 + lane16;
+                half8 fa[2][NPASS][WCB], fb[2][WPB];
+                uint32_t rowa[WPB], hs[WPB];
+                auto issue = [&](auto ic) {
+                  constexpr int item = decltype(ic)::value, il = item - WI * hf, sl = item & 1, tt = item / KS, ks = item % KS;
+                  if constexpr (ks == 0 || il == 0) {  // a tap begins, or the step begins inside one
+                    const int tp = g * GT + tt, dy = tp / 3, dx = tp - dy * 3;
+#pragma unroll
+                    for (int j = 0; j < WPB; ++j) {
+                      const int yy = ((pj[j] >> HL) & (H - 1)) + dy - 1, xx = (pj[j] & (H - 1)) + dx - 1;
+                      const bool ok = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)H;  // else: conv padding
+                      const int q = ok ? pj[j] + (dy - 1) * H + (dx - 1) : pj[j];
+                      rowa[j] = ok ? pl + q * (KC * 2) : 0x100000u;  // beyond the LDS: the read returns zeros
+                      hs[j] = (h * 16) ^ (swz(q) << 4);
+                    }
+                  }
+                  static_for<NPASS * WCB>([&](auto ii) {
+                    constexpr int ps = decltype(ii)::value / WCB, i = decltype(ii)::value % WCB;
+                    lds_read128<ps * WHALF + (il * CBT + i) * 1024>(fa[sl][ps][i], wb);
+                  });
+                  static_for<WPB>([&](auto jj) { lds_read128<0>(fb[sl][decltype(jj)::value], rowa[decltype(jj)::value] + (hs[decltype(jj)::value] ^ (ks * 32))); });
+                };
+                issue(std::integral_constant<int, WI * hf>{});
+                static_for<WI>([&](auto ic) {
+                  constexpr int il = decltype(ic)::value, item = WI * hf + il, sl = item & 1;
+                  if constexpr (il + 1 < WI) issue(std::integral_constant<int, item + 1>{});
+                  lds_wait<(il + 1 < WI ? NPASS * WCB + WPB : 0)>();
+#pragma unroll
+                  for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+                    for (int i = 0; i < WCB; ++i) lds_touch(fa[sl][ps][i]);
+#pragma unroll
+                  for (int j = 0; j < WPB; ++j) lds_touch(fb[sl][j]);
+#pragma unroll
+                  for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+                    for (int i = 0; i < WCB; ++i)
+#pragma unroll
+                      for (int j = 0; j < WPB; ++j) acc[ps][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[sl][ps][i], fb[sl][j], acc[ps][i][j], 0, 0, 0);
+                });
+              }
+              PHC_MARK(4 + 3 * cvi);
+              if (ring_wave) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next ring step has landed
+              asm volatile("s_barrier" ::: "memory");
+              PHC_MARK(5 + 3 * cvi);
+              --ahead;
+              slot_rd ^= 1;
+            });
+          }
+        }
+        // every wave is past the last step's barrier: nobody reads the activation buffer any more
+        if constexpr (lastc) {
+          if (has_next) {  // all patch buffers of the next tile
+#pragma unroll
+            for (int i = 0; i < NPB; ++i) patch_dma(t + tstep, i);
+          }
+          out_index_late();
+          static_for<NPASS>([&](auto kp) {
+            uint4v resv[WCB][WPB][2];
+            std_epi(kp, acc[decltype(kp)::value], resv);
+          });
+          PHC_MARK(6 + 3 * cvi);
+        } else {
+          // + bias (+ residual) (ReLU) -> fp16 -> back into the activation buffer (input of the next conv), both passes
+          static_for<NPASS>([&](auto kp) {
+            constexpr int ps = decltype(kp)::value;
+#pragma unroll
+            for (int i = 0; i < WCB; ++i) {
+              float4v bi[4];
+              bias_rows(pb_cv[cvi][ps], i, bi);
+#pragma unroll
+              for (int j = 0; j < WPB; ++j)
+                static_for<2>([&](auto qc) {
+                  constexpr int qq = decltype(qc)::value;
+                  half4 ra{}, rb{}, hq[2];
+                  if constexpr (RES != 0) unpair16(keep[ps][i][j][qq], ra, rb);
+                  hq[0] = act_quad<2 * qq>(acc[ps][i][j], cv.acc_scale, bi[2 * qq], RES != 0, ra, true);
+                  hq[1] = act_quad<2 * qq + 1>(acc[ps][i][j], cv.acc_scale, bi[2 * qq + 1], RES != 0, rb, true);
+                  const uint4v w = pair16(hq[0], hq[1]);
+                  if constexpr (SAVE) keep[ps][i][j][qq] = w;
+                  const int cb = ps * CT + (wc * WCB + i) * 32 + 16 * qq + 8 * h;  // this lane: channels cb .. cb+7 of pixel pj[j]
+                  *(uint4v *)(smem + (cb / KC) * REGION + pj[j] * (KC * 2) + ((((cb % KC) / 8) ^ swz(pj[j])) << 4)) = w;
+                });
+            }
+          });
+          asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+          PHC_MARK(6 + 3 * cvi);
+        }
+      } else
       static_for<NPASS>([&](auto kp) {
         constexpr int ps = decltype(kp)::value;
         constexpr bool last = lastc && ps == NPASS - 1;  // the very last K loop over the buffer for this sample
@@ -690,34 +953,6 @@ __global__ __launch_bounds__(64 * WAVES_C * WAVES_P, MINW) void chain_kernel(con
             } else if (has_next) dma_region(t + tstep, NCHUNK - 1);
           }
           if constexpr (S2 || !KEEP) out_index_late();
-          auto std_epi = [&]() {
-          float4v bq[WCB][4], bsq[1][4];
-#pragma unroll
-          for (int i = 0; i < WCB; ++i) {
-            if constexpr (PBIAS) bias_rows(pb_cv[cvi][ps], i, bq[i]);
-            else {
-#pragma unroll
-              for (int q = 0; q < 4; ++q) bq[i][q] = *(const float4v *)(cv.bias + ps * CT + (wc * WCB + i) * 32 + 4 * h + 8 * q);
-            }
-          }
-          ConvArgs ea{};
-          ea.y = a.y; ea.gap = a.gap; ea.gap_slots = a.gap_slots; ea.gap_l = a.gap_l; ea.acc_scale = cv.acc_scale; ea.relu = 1;
-          ea.y_c16 = a.y_c16; ea.hout_l = HL;
-          ea.res = RES ? (const void *)a.x : nullptr;  // non-NULL = "add resv"
-          float16v acc_sc[1][1];
-          uint4v resl[1][1][2];
-          if constexpr (RES == 2) {
-#pragma unroll
-            for (int i = 0; i < WCB; ++i)
-#pragma unroll
-              for (int j = 0; j < WPB; ++j)
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) resv[i][j][qq] = keep[ps][i][j][qq];
-          }
-          int he = h, pe = p;
-          asm volatile("" : "+v"(he), "+v"(pe));  // nothing of the epilogue's lane arithmetic is hoisted out of the tile loop
-          conv_epilogue<C, CT, WCB, WPB, false, 1>(ea, ps, wc, he, pe, opix, gidx, acc, acc_sc, bq, bsq, resv, resl);
-          };
           // !KEEP (8 accumulators + the residual tile in registers): the same epilogue one 32-cout block at a time, so that only one
           // block's 16 bias values are live (both blocks' at once, as above, spilled)
           auto blk_epi = [&]() {
@@ -741,7 +976,7 @@ __global__ __launch_bounds__(64 * WAVES_C * WAVES_P, MINW) void chain_kernel(con
             }
           };
           if constexpr (!KEEP && PBIAS) blk_epi();
-          else std_epi();
+          else std_epi(kp, acc, resv);
           PHC_MARK(6 + 3 * cvi);
         } else {
           // + bias (+ residual) (ReLU) -> fp16 -> back into the activation buffer (input of the next conv)
@@ -802,5 +1037,15 @@ __global__ __launch_bounds__(64 * WAVES_C * WAVES_P, MINW) void chain_kernel(con
     });
   }
   PHC_FLUSH((C == 256 ? 2 : 0) + (S2 ? 1 : 0));
+}
+
+template <int C, int HL, int SPW_L, int WCB, int WPB, int WAVES_C, int WAVES_P, int GT, int RB, int FD, int MINW, int NCONV, bool SPLIT_ROLES, bool S2 = false, bool KEEP = true, bool OOBZ = false, bool W2 = false, bool LO8 = false>
+__global__ __launch_bounds__(64 * WAVES_C * WAVES_P, MINW) void chain_kernel(const ChainArgs a) {
+  chain_body<C, HL, SPW_L, WCB, WPB, WAVES_C, WAVES_P, GT, RB, FD, MINW, NCONV, SPLIT_ROLES, S2, KEEP, OOBZ, W2, LO8>(a);
+}
+// The whole 256-channel stage with both cout passes per wave (WIDE above): chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, .., 2, 3, true, true, true, true>'s
+// tiling, fragment reads one item ahead.  Padding from beyond the LDS only: devices that fail the LDS probe keep chain_kernel.
+__global__ __launch_bounds__(512, 2) void stage256_wide_kernel(const ChainArgs a) {
+  chain_body<256, 3, 1, 2, 1, 2, 4, 3, 2, 1, 2, 3, true, true, true, true, false, false, true>(a);
 }
 

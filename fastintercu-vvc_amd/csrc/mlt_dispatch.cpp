@@ -23,6 +23,7 @@ const Tuning &tuning() {
     u.no_chain = on("MLT_NO_CHAIN") || u.no_block_fusion; u.no_chain_s2 = on("MLT_NO_CHAIN_S2"); u.no_c16 = on("MLT_NO_C16"); u.chain64 = !on("MLT_NO_CHAIN64");
     u.no_l0_s5 = on("MLT_NO_L0_S5");
     u.no_xs_handoff = on("MLT_NO_XS_HANDOFF") || u.debug_dump_dir != nullptr;   // (the layer dumps are those of the sc hand-off)
+    u.no_stage256_wide = on("MLT_NO_STAGE256_WIDE");
     u.l0_stream_min = on("MLT_NO_L0_STREAM") ? 0 : (int)num("MLT_L0_STREAM_MIN", 128);
     u.l1_stream_min = on("MLT_NO_L1_STREAM") ? 0 : (int)num("MLT_L1_STREAM_MIN", 128);
     u.guard_wait_mode = on("MLT_GUARD_SPIN_WAIT") ? 1 : on("MLT_GUARD_BLOCKING_WAIT") ? 2 : 0;
@@ -344,9 +345,9 @@ int run_block32(mlt_ctx *ctx, const mlt::Block &B, int n, int h, const void *x, 
 // BasicBlock tail of a stage as ONE launch (chain_kernel): b0 = relu(bn2(conv2 t) + sc); t1 = relu(bn1(conv1 b0));
 // out = relu(bn2(conv2 t1) + b0) (+ GAP).  Fast arithmetic, stages whose whole sample fits the LDS (128 channels @ 16 x 16).
 // s2_in != NULL: the stage's stride-2 conv + shortcut run inside the same launch from the stage input s2_in ([n][2h][2h][c/2]);
-// t / sc are then unused.
+// t / sc are then unused.  wide (the whole 256-channel stage): stage256_wide_kernel, same launch name, same bits.
 int run_chain3(mlt_ctx *ctx, const mlt::Block &B0, const mlt::Block &B1, int n, int h, const void *t, const void *sc, void *y, float *gap,
-               const void *s2_in, bool x_c16, bool y_c16, void *b0_hbm, bool sc_c16) {
+               const void *s2_in, bool x_c16, bool y_c16, void *b0_hbm, bool sc_c16, bool wide) {
   const int c = B0.conv2.cout;
   ChainArgs a{};
   a.x = s2_in ? s2_in : t; a.nconv = 3; a.y = y; a.gap = gap; a.n = n; a.zero = ctx->zero_page;
@@ -381,12 +382,16 @@ int run_chain3(mlt_ctx *ctx, const mlt::Block &B0, const mlt::Block &B1, int n, 
   Launch L{ctx};
   hipEvent_t e0 = nullptr, e1 = nullptr;
   char variant[96];
-  std::snprintf(variant, sizeof variant, "%s%s%s%s%s", w2 ? "hi+lo weights" : "single pass", x_c16 ? ", x chunk-major" : "", sc_c16 ? ", sc chunk-major" : "", y_c16 ? ", y chunk-major" : "",
+  std::snprintf(variant, sizeof variant, "%s%s%s%s%s%s", wide ? "both cout passes per wave, " : "", w2 ? "hi+lo weights" : "single pass", x_c16 ? ", x chunk-major" : "", sc_c16 ? ", sc chunk-major" : "", y_c16 ? ", y chunk-major" : "",
                 gap ? ", GAP" : "");
   int rc = L.prof_begin(name, flops, bytes, e0, e1, variant);
   if (rc) return rc;
   plan_note(ctx, {{"x", a.x}, {"sc", s2_in ? nullptr : sc}, {"y", y}, {"gap", gap}, {"b0", c == 64 ? b0_hbm : nullptr}}, {{"grid", grid_x}});
-  LAUNCH_TRY(ctx, mlt_launch_chain(c, h, s2_in != nullptr, ctx->lds_oob_zero, w2, a, grid_x, ctx->stream));
+  if (wide) {  // (plan_network: the single-pass whole-stage launch of the 256 stage on a device that passed the LDS probe)
+    LAUNCH_TRY(ctx, c == 256 && h == 8 && s2_in && !w2 && ctx->lds_oob_zero ? mlt_launch_stage256_wide(a, grid_x, ctx->stream) : hipErrorInvalidValue);
+  } else {
+    LAUNCH_TRY(ctx, mlt_launch_chain(c, h, s2_in != nullptr, ctx->lds_oob_zero, w2, a, grid_x, ctx->stream));
+  }
   if ((rc = L.prof_end(e1))) return rc;
   if (y && (rc = debug_dump(ctx, name, y, (size_t)px * c * 2))) return rc;
   return MLT_OK;
@@ -507,6 +512,8 @@ NetPlan plan_network(const mlt_ctx *ctx, const NetCfg &c, unsigned cls) {
                             q2.taps == 9 && q2.kc == 64 && q2.ct == 64 && !last;
         PlanStep &st = add(stream ? PlanStep::LAYER1_STREAM : PlanStep::CHAIN, s);
         st.inside_s2 = chain_s2; st.x_c16 = cur_c16; st.sc_c16 = sc_c16; st.y_c16 = out_c16;
+        // the whole 256-channel stage: both cout passes per wave (padding from beyond the LDS only: devices that fail the probe keep chain_kernel)
+        st.wide = chain_s2 && m.planes[s] == 256 && ho == 8 && ctx->lds_oob_zero && !tn.no_stage256_wide;
         // the five-stage front followed by layer1's streaming launch, both in their shipped MFMA shapes: the front hands over the shortcut's INPUT (half
         // the bytes) and layer1's loader waves compute the shortcut (layer0_stream_xs_kernel -> layer1_stream_xs_kernel; same bits).  Every other
         // consumer of the front's sc -- the 64-channel chain -- and every other producer of layer1's sc -- the stride-2 launch -- keeps the sc hand-off.
@@ -621,7 +628,7 @@ int run_network(mlt_ctx *ctx, SizeState &st, const NetCfg &c, int n, const PassI
       break;
     case PlanStep::CHAIN:
       rc = run_chain3(ctx, mt.blocks[s][0], mt.blocks[s][1], n, ho, pool[0], pool[1], last ? nullptr : outs[s], gaps[s], ps.inside_s2 ? cur : nullptr,
-                      ps.x_c16, ps.y_c16, pool[2], ps.sc_c16);
+                      ps.x_c16, ps.y_c16, pool[2], ps.sc_c16, ps.wide);
       break;
     case PlanStep::LAYER1_STREAM:
       rc = run_layer1_stream(ctx, mt.blocks[s][0], mt.blocks[s][1], n, pool[0], pool[1], outs[s], gaps[s], ps.y_c16, ps.xs ? &c.model_of(1, 0).blocks[1][0].conv1 : nullptr);

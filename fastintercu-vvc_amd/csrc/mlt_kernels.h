@@ -181,6 +181,9 @@ struct ChainArgs {
   int n;
 };
 hipError_t mlt_launch_chain(int c, int h, bool with_s2, bool oob_zero, bool w2, const ChainArgs &a, int grid_x, hipStream_t st);  // oob_zero: see mlt_probe_lds_oob; w2: hi+lo weights (two planes, no stride-2 front conv, oob_zero only)
+// The whole 256-channel stage (8 x 8 maps, stride-2 conv + shortcut inside) with both cout passes per wave (stage256_wide_kernel): the same bits as
+// mlt_launch_chain(256, 8, true, true, false, ...), which stays the form of devices that fail the LDS probe.
+hipError_t mlt_launch_stage256_wide(const ChainArgs &a, int grid_x, hipStream_t st);
 bool mlt_chain_supported(int c, int h);
 hipError_t mlt_probe_lds_oob(int *d_ok, hipStream_t st);  // *d_ok = 1 iff DS reads beyond the LDS allocation return zeros on this device
 bool mlt_stage_supported(int c, int h);  // ... including the stage's stride-2 conv + shortcut (S2 variant)

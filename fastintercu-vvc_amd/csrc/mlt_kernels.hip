@@ -755,6 +755,11 @@ hipError_t mlt_launch_chain(int c, int h, bool with_s2, bool oob_zero, bool w2, 
   }
   return hipErrorInvalidValue;
 }
+hipError_t mlt_launch_stage256_wide(const ChainArgs &a, int grid_x, hipStream_t st) {
+  static DeviceOnce once;
+  if (a.nconv != 3 || !a.s2_w) return hipErrorInvalidValue;
+  return launch_chain_t(stage256_wide_kernel, once, a, grid_x, 512, 160 * 1024, st);
+}
 
 hipError_t mlt_launch_stem5(const Stem5Args &a, int nsplit, int grid_x, int lds, hipStream_t st) {
   if (nsplit == 3) hipLaunchKernelGGL(stem5_kernel<3>, dim3(grid_x), dim3(256), lds, st, a);

@@ -45,6 +45,7 @@ struct Tuning {
   bool l0_mfma32, l1_mfma32;       // MLT_L0_MFMA32: layer0_stream_kernel on round 5's 32x32x16 MFMAs; layer1_stream_kernel runs them unless MLT_L1_MFMA16 (same bits either way)
   bool no_chain, no_chain_s2, no_c16, chain64, no_block_fusion, no_l0_s5;   // MLT_NO_CHAIN, _CHAIN_S2, _C16, _CHAIN64, _BLOCK_FUSION, _L0_S5: knock-outs of the fused forms
   bool no_xs_handoff;              // MLT_NO_XS_HANDOFF (also set by MLT_DEBUG_DUMP_DIR): the streaming pair hands over layer1's shortcut (sc) instead of its input (xs); A/B, same bits
+  bool no_stage256_wide;           // MLT_NO_STAGE256_WIDE: the whole 256-channel stage runs chain_kernel (one cout pass at a time) instead of stage256_wide_kernel; A/B, same bits
   int l0_stream_min, l1_stream_min;        // MLT_L0_STREAM_MIN / MLT_L1_STREAM_MIN (128; MLT_NO_L0_STREAM / MLT_NO_L1_STREAM: 0 = never)
   int guard_wait_mode;             // 0 sleep-then-poll, 1 MLT_GUARD_SPIN_WAIT, 2 MLT_GUARD_BLOCKING_WAIT
   bool no_small_mix, no_mag_guard, no_graph;   // MLT_NO_SMALL_MIX, MLT_NO_MAG_GUARD, MLT_NO_GRAPH (also set by MLT_DEBUG_DUMP_DIR)
@@ -94,6 +95,7 @@ struct PlanStep {
   bool front = false;       // LAYER0_STREAM: layer1.0.conv1 + shortcut ride along
   bool xs = false;          // LAYER0_STREAM (front) + the LAYER1_STREAM behind it: pool1 carries the shortcut's INPUT (xs), layer1's launch computes the shortcut
   bool inside_s2 = false;   // CHAIN: the stage's stride-2 conv + shortcut run inside the launch
+  bool wide = false;        // CHAIN (inside_s2, 256 channels): stage256_wide_kernel -- both cout passes per wave, every input patch staged once
   bool x_c16 = false;       // CHAIN (inside_s2): the stage input is chunk-major
   bool sc_c16 = false;      // CONV_S2 writes / CHAIN, LAYER1_STREAM read the shortcut chunk-major
   bool y_c16 = false;       // the stage's output is written chunk-major (its consumer is a whole-stage launch)

@@ -37,6 +37,8 @@ def per_kernel(path, counter, steps):
                 name = f"stage_{c}_h{1 << hl}(s2+sc,conv2,conv1,conv2)"
             else:
                 name = f"chain{nconv}_s1_{c}_h{1 << hl}(conv2+conv1+conv2)"
+        elif "stage256_wide_kernel" in k:  # (the whole 256-channel stage, both cout passes per wave: the name run_chain3 profiles it under)
+            name = "stage_256_h8(s2+sc,conv2,conv1,conv2)"
         elif (m0 := re.search(r"layer0_stream(_xs)?_kernel(<true)?", k)):  # (the names run_layer0_stream profiles under -- mlt_profile_entry.name holds 47 characters: with / without layer1's stride-2 conv as a fifth stage)
             # (template arguments since round 6: <F5, M16> -- the first one says whether the fifth stage rides along; layer0_stream_xs_kernel is a five-stage form)
             name = "layer0_stream_h64(stem+layer0+layer1.0.conv1+sc)"[:47] if m0.group(1) or m0.group(2) else "layer0_stream_h64(stem+layer0.0+layer0.1)"
