@@ -557,6 +557,36 @@ class MltCnn:
         out = {k: np.zeros(*shapes[k]) for k in shapes if k in want}
         return out, lambda k: out[k].ctypes.data if k in out else None
 
+    @staticmethod
+    def _tree_entries(pairs, poc, qp):
+        """-> the pairs as a list and the MltTreePicture array of a several-pair call (poc / qp: one int for all pairs or one per pair)."""
+        pairs = list(pairs)
+        P = len(pairs)
+        poc = np.broadcast_to(np.asarray(poc, np.int32), (P,))
+        qp = np.broadcast_to(np.asarray(qp, np.int32), (P,))
+        entries = (MltTreePicture * max(P, 1))()
+        for i, (o, q) in enumerate(pairs):
+            entries[i].org, entries[i].pred, entries[i].poc, entries[i].qp = o._h, q._h, int(poc[i]), int(qp[i])
+        return pairs, entries
+
+    @staticmethod
+    def _tree_slices(first, nodes, out, union=None, per_union: int = 1) -> list:
+        """The arrays of a batched tree call cut into one dict per tree: slice s is nodes [first[s], first[s + 1]), map s and the same rows of the per-node arrays
+        (all copies) + "union_nodes": row s // per_union of `union`, where the call has one."""
+        res = []
+        for s in range(len(first) - 1):
+            lo, hi = int(first[s]), int(first[s + 1])
+            r = {"nodes": nodes[lo:hi].copy(), "first_node": lo}
+            if union is not None:
+                r["union_nodes"] = union[s // per_union].copy()
+            if "leaf_map" in out:
+                r["leaf_map"] = out["leaf_map"][s].copy()
+            for k in ("logits", "decisions", "candidates"):
+                if k in out:
+                    r[k] = out[k][lo:hi].copy()
+            res.append(r)
+        return res
+
     def predict_tree(self, org_pic: Picture, pred_pic: Picture, poc: int, qp: int, top: int = 128, min_size: int = 16, descend: dict | None = None,
                      by_candidates: bool = False, want=("leaf_map",)) -> dict:
         """The partition tree of the picture pair (mlt_predict_tree): quadtree descent on the device from `top` down to `min_size`.
@@ -582,13 +612,8 @@ class MltCnn:
         for all pairs or one per pair; the other arguments as predict_tree.
         -> one dict per pair, shaped like predict_tree's ("logits" rows are zero beyond the size's logit count) + "first_node": the pair's first index in the call's
         node array."""
-        pairs = list(pairs)
+        pairs, entries = self._tree_entries(pairs, poc, qp)
         P = len(pairs)
-        poc = np.broadcast_to(np.asarray(poc, np.int32), (P,))
-        qp = np.broadcast_to(np.asarray(qp, np.int32), (P,))
-        entries = (MltTreePicture * max(P, 1))()
-        for i, (o, q) in enumerate(pairs):
-            entries[i].org, entries[i].pred, entries[i].poc, entries[i].qp = o._h, q._h, int(poc[i]), int(qp[i])
         cfg = self._tree_config(top, min_size, descend, by_candidates)
         w, h = (pairs[0][0].width, pairs[0][0].height) if P else (0, 0)
         cap = P * tree_max_nodes(w, h, top, min_size)
@@ -597,17 +622,7 @@ class MltCnn:
         out, ptr = self._tree_outputs(want, cap, (max(P, 1), h // 16, w // 16))
         self._check(self._lib.mlt_predict_trees(self._h, P, entries, C.byref(cfg), nodes.ctypes.data, cap, first.ctypes.data, ptr("leaf_map"),
                                                 ptr("logits"), 15, ptr("decisions"), ptr("candidates")))
-        res = []
-        for p in range(P):
-            lo, hi = int(first[p]), int(first[p + 1])
-            r = {"nodes": nodes[lo:hi].copy(), "first_node": lo}
-            if "leaf_map" in out:
-                r["leaf_map"] = out["leaf_map"][p].copy()
-            for k in ("logits", "decisions", "candidates"):
-                if k in out:
-                    r[k] = out[k][lo:hi].copy()
-            res.append(r)
-        return res
+        return self._tree_slices(first, nodes, out)
 
     def predict_tree_sweep(self, org_pic: Picture, pred_pic: Picture, poc: int, qps, top: int = 128, min_size: int = 16, descend: dict | None = None,
                            by_candidates: bool = False, want=("leaf_map",)) -> list:
@@ -626,17 +641,7 @@ class MltCnn:
         out, ptr = self._tree_outputs(want, cap, (max(Q, 1), h // 16, w // 16))
         self._check(self._lib.mlt_predict_tree_sweep(self._h, org_pic._h, pred_pic._h, C.byref(cfg), qps.ctypes.data, Q, nodes.ctypes.data, cap, first.ctypes.data,
                                                      union.ctypes.data, ptr("leaf_map"), ptr("logits"), 15, ptr("decisions"), ptr("candidates")))
-        res = []
-        for q in range(Q):
-            lo, hi = int(first[q]), int(first[q + 1])
-            r = {"nodes": nodes[lo:hi].copy(), "first_node": lo, "union_nodes": union.copy()}
-            if "leaf_map" in out:
-                r["leaf_map"] = out["leaf_map"][q].copy()
-            for k in ("logits", "decisions", "candidates"):
-                if k in out:
-                    r[k] = out[k][lo:hi].copy()
-            res.append(r)
-        return res
+        return self._tree_slices(first, nodes, out, union[None], max(Q, 1))
 
     def predict_trees_sweep(self, pairs, poc, qp_offset, qps, top: int = 128, min_size: int = 16, descend: dict | None = None, by_candidates: bool = False,
                             want=("leaf_map",)) -> list:
@@ -644,15 +649,10 @@ class MltCnn:
         (mlt_predict_trees_sweep).  pairs: [(org_pic, pred_pic), ...]; poc / qp_offset: one int for all pairs or one per pair -- entry p under point q runs at
         qp_offset[p] + qps[q]; the other arguments as predict_tree.
         -> result[p][q]: a dict shaped like predict_tree_sweep's; "union_nodes" is entry p's int32 [4]."""
-        pairs = list(pairs)
+        pairs, entries = self._tree_entries(pairs, poc, qp_offset)
         P = len(pairs)
-        poc = np.broadcast_to(np.asarray(poc, np.int32), (P,))
-        off = np.broadcast_to(np.asarray(qp_offset, np.int32), (P,))
         qps = np.ascontiguousarray(qps, np.int32).reshape(-1)
         Q = qps.shape[0]
-        entries = (MltTreePicture * max(P, 1))()
-        for i, (o, q) in enumerate(pairs):
-            entries[i].org, entries[i].pred, entries[i].poc, entries[i].qp = o._h, q._h, int(poc[i]), int(off[i])
         cfg = self._tree_config(top, min_size, descend, by_candidates)
         w, h = (pairs[0][0].width, pairs[0][0].height) if P else (0, 0)
         cap = P * Q * tree_max_nodes(w, h, top, min_size)
@@ -662,21 +662,8 @@ class MltCnn:
         out, ptr = self._tree_outputs(want, cap, (max(P * Q, 1), h // 16, w // 16))
         self._check(self._lib.mlt_predict_trees_sweep(self._h, P, entries, C.byref(cfg), qps.ctypes.data, Q, nodes.ctypes.data, cap, first.ctypes.data, union.ctypes.data,
                                                       ptr("leaf_map"), ptr("logits"), 15, ptr("decisions"), ptr("candidates")))
-        res = []
-        for p in range(P):
-            row = []
-            for q in range(Q):
-                s = p * Q + q
-                lo, hi = int(first[s]), int(first[s + 1])
-                r = {"nodes": nodes[lo:hi].copy(), "first_node": lo, "union_nodes": union[p].copy()}
-                if "leaf_map" in out:
-                    r["leaf_map"] = out["leaf_map"][s].copy()
-                for k in ("logits", "decisions", "candidates"):
-                    if k in out:
-                        r[k] = out[k][lo:hi].copy()
-                row.append(r)
-            res.append(row)
-        return res
+        flat = self._tree_slices(first, nodes, out, union, max(Q, 1))
+        return [flat[p * Q:(p + 1) * Q] for p in range(P)]
 
     def synchronize(self):
         self._check(self._lib.mlt_synchronize(self._h))

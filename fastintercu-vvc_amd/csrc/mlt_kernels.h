@@ -347,25 +347,31 @@ struct TreesEntry {
 // The segment table, [MLT_TREES_LEVELS][n_pictures] each: where picture p's nodes of level l start in the arena, how many they are, and where they start in the
 // packed (picture-major) output.  Written by the expand launches (a level's rows by the launch that writes the level's nodes; pack_base by the last one).
 struct TreesSegs { int32_t *start, *n, *pack_base; };
-struct TreeExpandArgs {
+// What an expand launch of either descent (the plain one below, the union descent of the tree sweeps further down) knows of the arena, of the level just evaluated
+// and of the next one: the part the shared device helpers work on.
+struct TreeLevelArgs {
   TreeNodeRec *nodes;          // every node of the call, level-major; node_cap entries
   int32_t *xy;                 // [node_cap][2]: the nodes' positions -- a level's slice is the position list its network pass gathers from
   int32_t *pic;                // [node_cap] picture index of every node, beside xy
   int node_cap;
+  int32_t *seg_start, *seg_n;  // the segment table: a launch reads the level's rows and writes the next level's
+  int n_pictures;
   int lvl_start, lvl_n;        // the level just evaluated, as one list over all pictures: nodes [lvl_start, lvl_start + lvl_n)
   int size;                    // its CU size; the next level's is size / 2
-  int lvl, n_levels;           // its depth; lvl = -1 with lvl_n = 0 and size = 2 x top_size opens the trees; lvl == n_levels - 1: the last launch also writes pack_base and first_node
+  int lvl;                     // its depth; lvl = -1 with lvl_n = 0 and size = 2 x top_size opens the trees
+  const int32_t *next_roots;   // [n_next_roots][2] the roots EVERY picture's next segment opens with, raster order
+  int n_next_roots, root_flags;   // root_flags: their mlt_tree_node.flags (bit 0 below top_size)
+  int32_t *count;              // [1] out: the whole next level's node count = n_pictures x n_next_roots + 4 x descending nodes (NULL: not wanted)
+};
+struct TreeExpandArgs : TreeLevelArgs {
+  int n_levels;                // lvl == n_levels - 1: the last launch also writes pack_base and first_node
   const DecisionRec *dec;      // [lvl_n] the level's decision records
   const CandRec *cand;         // [lvl_n] its candidate records, or NULL: cand_mask = 1 << raw_mode, every class when a logit of the decision head is NaN
   const float *logits;         // [lvl_n][n_logits] (read only when cand == NULL)
   int n_logits, head_off, head_classes;   // the decision head inside a row of logits
   uint32_t descend_mask;       // classes of the decision head that mean "quad split"; 0: the level never descends (min_size)
   int by_candidates;           // descend on cand_mask & descend_mask instead of on split_mode
-  const int32_t *next_roots;   // [n_next_roots][2] the roots EVERY picture's next segment opens with, raster order
-  int n_next_roots, root_flags;   // root_flags: their mlt_tree_node.flags (bit 0 below top_size)
-  int32_t *count;              // [1] out: the whole next level's node count = n_pictures x n_next_roots + 4 x descending parents (NULL: not wanted)
-  TreesSegs segs;
-  int n_pictures;
+  int32_t *pack_base;          // the segment table's third part, out (last launch)
   int32_t *first_node;         // [n_pictures + 1] out (last launch)
 };
 struct TreeRasterArgs {
@@ -398,27 +404,16 @@ struct TreesPackArgs {
 // segment table: [MLT_TREES_LEVELS][n_pictures] start and count).  A union node carries pic (its entry), alive (bit q: part of the entry's tree q) and desc (bit q:
 // descends under point q); its per-point records / logits / candidate records are slab-major: element (q, i) of a level lies q * slab + i behind the level's
 // element (0, 0).
-struct TreeSweepExpandArgs {
-  TreeNodeRec *nodes;          // the union's nodes (parent / first_child: union indices; split_mode / confidence / cand_mask stay unset), node_cap entries
-  int32_t *xy;                 // [node_cap][2]
+struct TreeSweepExpandArgs : TreeLevelArgs {   // nodes: the union's (parent / first_child: union indices; split_mode / confidence / cand_mask stay unset); pic: a node's entry
   uint32_t *alive, *desc;      // [node_cap]
-  int32_t *pic;                // [node_cap] entry of every node
-  int32_t *seg_start, *seg_n;  // the segment table: this launch reads the level's rows and writes the next level's
-  int n_pictures;
-  int node_cap;
-  int lvl_start, lvl_n;        // the level just evaluated, as one list over all entries
   int next_start, next_cap;    // where the next level starts and how many nodes it may hold
-  int size, lvl;               // as TreeExpandArgs (lvl = -1, lvl_n = 0: the opening launch)
   const DecisionRec *dec;      // the level's element (0, 0) of each slab array
   const CandRec *cand;         // NULL: the default policy's mask from the logits (TreeExpandArgs.cand)
   const float *logits;
   long slab;
   int n_qps, n_logits, head_off, head_classes;
   uint32_t descend_mask;
-  int by_candidates;
-  const int32_t *next_roots;   // the border roots EVERY entry's next segment opens with: alive under every point
-  int n_next_roots, root_flags;
-  int32_t *count;              // [1] out: n_pictures x n_next_roots + 4 x nodes descending under any point (NULL: not wanted)
+  int by_candidates;           // (next_roots: alive under every point; count: 4 x the nodes descending under ANY point)
 };
 struct TreeSweepRasterArgs {
   const TreeNodeRec *nodes;

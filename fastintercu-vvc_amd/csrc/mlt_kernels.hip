@@ -874,51 +874,55 @@ hipError_t mlt_launch_guard_scatter(const GuardScatterArgs &a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// flat grid-stride launch over 16-byte items (mlt_picture_kernels.inc): enough workgroups to fill the device (256 CUs x 8 waves of 64 = 8 workgroups of 256
-// per CU), never more than there are items
-hipError_t mlt_launch_picture_gather(const PictureGatherArgs &a, hipStream_t st) {
-  const size_t items = (size_t)a.c << (2 * a.s_l - 2);   // two planes x c x S x S / 8
+// The flat grid-stride launch shape of the picture and tree kernels: workgroups of 256 over `items` work items -- enough to fill the device (256 CUs x 8 waves of
+// 64 = 8 workgroups of 256 per CU), never more than there are items.
+static dim3 flat_grid(size_t items) {
   const size_t want = (items + 255) / 256;
-  hipLaunchKernelGGL(picture_gather_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
+  return dim3((unsigned)(want < 2048 ? want : 2048));
+}
+// what lives in LDS arrays of the ABI's maxima: the per-picture ranks of the expand kernels, the slices' starts of the sweep pack
+static bool tree_counts_ok(int n_pictures, int n_qps = 1) {
+  return n_qps >= 1 && n_qps <= MLT_SWEEP_MAX_QPS_K && n_pictures >= 1 && n_pictures <= MLT_TREES_MAX_PICTURES_K;
+}
+
+// over 16-byte items (mlt_picture_kernels.inc): two planes x c x S x S / 8
+hipError_t mlt_launch_picture_gather(const PictureGatherArgs &a, hipStream_t st) {
+  hipLaunchKernelGGL(picture_gather_kernel, flat_grid((size_t)a.c << (2 * a.s_l - 2)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t mlt_launch_picture_gather_multi(const PictureGatherMultiArgs &a, hipStream_t st) {
+  const size_t items = (size_t)a.c << (2 * a.s_l - 2);
+  if (!items) return hipSuccess;
+  hipLaunchKernelGGL(picture_gather_multi_kernel, flat_grid(items), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
 // ONE workgroup: the ordered compaction carries its running base from tile to tile (mlt_tree_kernels.inc)
 hipError_t mlt_launch_tree_expand(const TreeExpandArgs &a, hipStream_t st) {
-  if (a.n_pictures < 1 || a.n_pictures > MLT_TREES_MAX_PICTURES_K) return hipErrorInvalidValue;   // the per-picture ranks live in LDS arrays of that size
+  if (!tree_counts_ok(a.n_pictures)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(tree_expand_kernel, dim3(1), dim3(MLT_TREE_TILE), 0, st, a);
   return hipGetLastError();
 }
 
-// flat grid-stride launch over the 16 x 16 blocks of the level's nodes
+// over the 16 x 16 blocks of the level's nodes
 hipError_t mlt_launch_tree_raster(const TreeRasterArgs &a, hipStream_t st) {
   const size_t items = (size_t)a.lvl_n << (2 * a.blk_l);
   if (!items) return hipSuccess;
-  const size_t want = (items + 255) / 256;
-  hipLaunchKernelGGL(tree_raster_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(tree_raster_kernel, flat_grid(items), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
-// picture_gather_kernel's launch shape
-hipError_t mlt_launch_picture_gather_multi(const PictureGatherMultiArgs &a, hipStream_t st) {
-  const size_t items = (size_t)a.c << (2 * a.s_l - 2);
-  if (!items) return hipSuccess;
-  const size_t want = (items + 255) / 256;
-  hipLaunchKernelGGL(picture_gather_multi_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-// flat grid-stride launch over the nodes of all levels
+// over the nodes of all levels
 hipError_t mlt_launch_trees_pack(const TreesPackArgs &a, hipStream_t st) {
   if (a.total <= 0) return hipSuccess;
-  const int want = (a.total + 255) / 256;
-  hipLaunchKernelGGL(tree_pack_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(tree_pack_kernel, flat_grid((size_t)a.total), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
 // tree sweeps -- ONE workgroup, as mlt_launch_tree_expand
 hipError_t mlt_launch_tree_expand_sweep(const TreeSweepExpandArgs &a, hipStream_t st) {
-  if (a.n_qps < 1 || a.n_qps > MLT_SWEEP_MAX_QPS_K || a.n_pictures < 1 || a.n_pictures > MLT_TREES_MAX_PICTURES_K) return hipErrorInvalidValue;   // (the per-entry ranks live in LDS)
+  if (!tree_counts_ok(a.n_pictures, a.n_qps)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(tree_expand_sweep_kernel, dim3(1), dim3(MLT_TREE_TILE), 0, st, a);
   return hipGetLastError();
 }
@@ -926,24 +930,23 @@ hipError_t mlt_launch_tree_expand_sweep(const TreeSweepExpandArgs &a, hipStream_
 hipError_t mlt_launch_tree_sweep_raster(const TreeSweepRasterArgs &a, hipStream_t st) {
   const size_t items = (size_t)a.lvl_n << (2 * a.blk_l);
   if (!items) return hipSuccess;
-  const size_t want = (items + 255) / 256;
-  hipLaunchKernelGGL(tree_sweep_raster_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(tree_sweep_raster_kernel, flat_grid(items), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
 // one workgroup per (entry, point)
 hipError_t mlt_launch_tree_sweep_rank(const TreeSweepPackArgs &a, hipStream_t st) {
-  if (a.n_qps < 1 || a.n_qps > MLT_SWEEP_MAX_QPS_K || a.n_pictures < 1 || a.n_pictures > MLT_TREES_MAX_PICTURES_K) return hipErrorInvalidValue;
+  if (!tree_counts_ok(a.n_pictures, a.n_qps)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(tree_sweep_rank_kernel, dim3((unsigned)(a.n_pictures * a.n_qps)), dim3(MLT_TREE_TILE), 0, st, a);
   return hipGetLastError();
 }
 
-// flat grid-stride launch over (point, union node); at least workgroup 0, which writes first_node[] and union_nodes[]
+// over (point, union node); at least workgroup 0, which writes first_node[] and union_nodes[]
 hipError_t mlt_launch_tree_sweep_pack(const TreeSweepPackArgs &a, hipStream_t st) {
-  if (a.n_qps < 1 || a.n_qps > MLT_SWEEP_MAX_QPS_K || a.n_pictures < 1 || a.n_pictures > MLT_TREES_MAX_PICTURES_K) return hipErrorInvalidValue;   // (the slices' starts live in LDS)
+  if (!tree_counts_ok(a.n_pictures, a.n_qps)) return hipErrorInvalidValue;
   size_t items = 0;
   for (int l = 0; l < a.n_levels; ++l) items += (size_t)a.lvl_n[l];
-  const size_t want = (items * (size_t)a.n_qps + 255) / 256;
-  hipLaunchKernelGGL(tree_sweep_pack_kernel, dim3((unsigned)(want < 1 ? 1 : want < 2048 ? want : 2048)), dim3(256), 0, st, a);
+  items *= (size_t)a.n_qps;
+  hipLaunchKernelGGL(tree_sweep_pack_kernel, flat_grid(items ? items : 1), dim3(256), 0, st, a);
   return hipGetLastError();
 }

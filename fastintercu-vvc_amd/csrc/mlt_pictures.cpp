@@ -8,8 +8,6 @@
 
 namespace {
 
-const int kMinDim = 16, kMaxDim = 16384;
-
 bool owns(const mlt_ctx *ctx, const mlt_picture *pic) {
   for (const mlt_picture *p : ctx->pictures)
     if (p == pic) return true;
@@ -24,6 +22,25 @@ void release(mlt_ctx *ctx, mlt_picture *pic) {
 }
 
 }  // namespace
+
+int enqueue_gather(mlt_ctx *dev, const GatherSrc &src, const int32_t *d_xy, const int32_t *d_pic, int16_t *g_org, int16_t *g_pred, int32_t *g_poc, int32_t *g_qp, int c,
+                   int size) {
+  // algorithmic bytes: both planes of every CU read once and written once (several pairs: + the CU's entry index read, its poc and qp written)
+  const double bytes = (double)c * size * size * 2 * 2 * 2;
+  if (d_pic) {
+    PictureGatherMultiArgs ga{};
+    ga.entries = src.entries; ga.n_entries = src.n_entries; ga.pic = d_pic; ga.xy = d_xy;
+    ga.g_org = g_org; ga.g_pred = g_pred; ga.g_poc = g_poc; ga.g_qp = g_qp; ga.c = c; ga.s_l = ilog2(size);
+    PROF_LAUNCH_TRY(dev, "picture_gather_multi", 0.0, bytes + (double)c * 12, mlt_launch_picture_gather_multi(ga, dev->stream));
+    return MLT_OK;
+  }
+  const AtPlanes &pl = src.pl;
+  PictureGatherArgs ga{};
+  ga.org = pl.org; ga.pred = pl.pred; ga.org_pitch = pl.org_pitch; ga.pred_pitch = pl.pred_pitch; ga.vec_org = pl.org_vec; ga.vec_pred = pl.pred_vec;
+  ga.xy = d_xy; ga.g_org = g_org; ga.g_pred = g_pred; ga.c = c; ga.s_l = ilog2(size);
+  PROF_LAUNCH_TRY(dev, "picture_gather", 0.0, bytes, mlt_launch_picture_gather(ga, dev->stream));
+  return MLT_OK;
+}
 
 // One device: CUs [0, n) of a position list from the planes this device holds (dev: the device's own context), in chunks of the pass size.  Host lists
 // (mlt_predict_at): positions, poc and qp go H2D per chunk and the results D2H.  Device lists (the tree descent: at.device): the gather reads the positions where
@@ -51,23 +68,10 @@ int predict_at_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &pl, int n, co
       HIP_TRY(dev, hipMemcpyAsync(S.d_poc, at.poc + i0, (size_t)c * 4, hipMemcpyHostToDevice, dev->stream));
       HIP_TRY(dev, hipMemcpyAsync(S.d_qp, at.qp + i0, (size_t)c * 4, hipMemcpyHostToDevice, dev->stream));
     }
-    Launch L{dev};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (at.pic) {   // the chunk's slice of the list and of its entry indices; the launch writes the chunk's poc / qp as well
-      PictureGatherMultiArgs ga{};
-      ga.entries = at.entries; ga.n_entries = at.n_entries; ga.pic = at.pic + i0; ga.xy = at.xy + 2 * (size_t)i0;
-      ga.g_org = S.d_org; ga.g_pred = S.d_pred; ga.g_poc = S.d_poc; ga.g_qp = S.d_qp; ga.c = c; ga.s_l = ilog2(size);
-      if ((rc = L.prof_begin("picture_gather_multi", 0.0, (double)c * (size * size * 2 * 2 * 2 + 12), e0, e1))) return rc;
-      LAUNCH_TRY(dev, mlt_launch_picture_gather_multi(ga, dev->stream));
-    } else {
-      PictureGatherArgs ga{};
-      ga.org = pl.org; ga.pred = pl.pred; ga.org_pitch = pl.org_pitch; ga.pred_pitch = pl.pred_pitch; ga.vec_org = pl.org_vec; ga.vec_pred = pl.pred_vec;
-      ga.xy = at.device ? at.xy + 2 * (size_t)i0 : d_xy; ga.g_org = S.d_org; ga.g_pred = S.d_pred; ga.c = c; ga.s_l = ilog2(size);
-      // algorithmic bytes: both planes of every CU read once and written once
-      if ((rc = L.prof_begin("picture_gather", 0.0, (double)c * size * size * 2 * 2 * 2, e0, e1))) return rc;
-      LAUNCH_TRY(dev, mlt_launch_picture_gather(ga, dev->stream));
-    }
-    if ((rc = L.prof_end(e1))) return rc;
+    // a device list: the chunk's slice of it and (several pairs) of its entry indices
+    if ((rc = enqueue_gather(dev, GatherSrc{pl, at.entries, at.n_entries}, at.device ? at.xy + 2 * (size_t)i0 : d_xy, at.pic ? at.pic + i0 : nullptr, S.d_org, S.d_pred,
+                             S.d_poc, S.d_qp, c, size)))
+      return rc;
     // (the guards and their exact re-run read the gathered planes; the staging pointers are 256-byte aligned: CLS_QUADS whatever the picture's alignment)
     if (at.device) {
       const PassIO io{Planes::dense(S.d_org, S.d_pred, size), S.d_poc, S.d_qp, out.split ? out.split + i0 : S.d_split, out.logits ? out.logits + (size_t)i0 * nl : nullptr,
@@ -105,14 +109,7 @@ static int predict_at_sweep_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &
     const int c = n - i0 < cap ? n - i0 : cap;
     HIP_TRY(dev, hipMemcpyAsync(d_xy, xy + 2 * (size_t)i0, (size_t)c * 8, hipMemcpyHostToDevice, dev->stream));
     HIP_TRY(dev, hipMemcpyAsync(S.d_poc, poc + i0, (size_t)c * 4, hipMemcpyHostToDevice, dev->stream));
-    Launch L{dev};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    PictureGatherArgs ga{};
-    ga.org = pl.org; ga.pred = pl.pred; ga.org_pitch = pl.org_pitch; ga.pred_pitch = pl.pred_pitch; ga.vec_org = pl.org_vec; ga.vec_pred = pl.pred_vec;
-    ga.xy = d_xy; ga.g_org = S.d_org; ga.g_pred = S.d_pred; ga.c = c; ga.s_l = ilog2(size);
-    if ((rc = L.prof_begin("picture_gather", 0.0, (double)c * size * size * 2 * 2 * 2, e0, e1))) return rc;
-    LAUNCH_TRY(dev, mlt_launch_picture_gather(ga, dev->stream));
-    if ((rc = L.prof_end(e1))) return rc;
+    if ((rc = enqueue_gather(dev, GatherSrc{pl, nullptr, 0}, d_xy, nullptr, S.d_org, S.d_pred, nullptr, nullptr, c, size))) return rc;
     const PassIO io{Planes::dense(S.d_org, S.d_pred, size), S.d_poc, nullptr, S.d_split, out.logits ? S.d_lg : nullptr, S.d_dec, S.d_cand, sw};
     if ((rc = run_checked_sweep(dev, *st, c, io))) return rc;
     for (int q = 0; q < n_qps; ++q) {
@@ -127,8 +124,9 @@ static int predict_at_sweep_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &
   return MLT_OK;
 }
 
-// What mlt_predict_at and its sweep form check of the picture pair and the positions before anything is enqueued (`who` opens the message); n > 0.
-static int check_at_pair(mlt_ctx *ctx, const char *who, const mlt_picture *org, const mlt_picture *pred) {
+// What mlt_predict_at and its sweep form (and, of the pair, the one-pair tree calls) check of the picture pair and the positions before anything is enqueued
+// (`who` opens the message); n > 0.
+int check_at_pair(mlt_ctx *ctx, const char *who, const mlt_picture *org, const mlt_picture *pred) {
   if (!owns(ctx, org) || !owns(ctx, pred)) { ctx->err = std::string(who) + ": both pictures must belong to this context"; return MLT_ERR_ARG; }
   if (org->width != pred->width || org->height != pred->height) { ctx->err = std::string(who) + ": the two pictures differ in width or height"; return MLT_ERR_ARG; }
   return MLT_OK;
@@ -159,7 +157,7 @@ extern "C" {
 
 int mlt_picture_create(mlt_ctx *ctx, int width, int height, mlt_picture **out) {
   if (!ctx) return MLT_ERR_ARG;
-  if (!out || width < kMinDim || height < kMinDim || width > kMaxDim || height > kMaxDim) { ctx->err = "mlt_picture_create: bad argument (16 <= width, height <= 16384)"; return MLT_ERR_ARG; }
+  if (!out || width < kPictureMinDim || height < kPictureMinDim || width > kPictureMaxDim || height > kPictureMaxDim) { ctx->err = "mlt_picture_create: bad argument (16 <= width, height <= 16384)"; return MLT_ERR_ARG; }
   *out = nullptr;
   mlt_picture *pic = new (std::nothrow) mlt_picture();
   if (!pic) return MLT_ERR_NOMEM;
@@ -184,7 +182,7 @@ int mlt_picture_create(mlt_ctx *ctx, int width, int height, mlt_picture **out) {
 
 int mlt_picture_wrap_device(mlt_ctx *ctx, const void *d_plane, int stride, int width, int height, mlt_picture **out) {
   if (!ctx) return MLT_ERR_ARG;
-  if (!out || !d_plane || ((uintptr_t)d_plane & 1) || width < kMinDim || height < kMinDim || width > kMaxDim || height > kMaxDim || stride < width) {
+  if (!out || !d_plane || ((uintptr_t)d_plane & 1) || width < kPictureMinDim || height < kPictureMinDim || width > kPictureMaxDim || height > kPictureMaxDim || stride < width) {
     ctx->err = "mlt_picture_wrap_device: bad argument (2-byte aligned plane, 16 <= width, height <= 16384, stride >= width)";
     return MLT_ERR_ARG;
   }

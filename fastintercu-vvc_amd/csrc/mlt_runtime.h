@@ -405,6 +405,20 @@ struct Launch {
   int prof_end(hipEvent_t e1);
 };
 
+// One launch with its profile row (plan mode: its record): prof_begin, the launch, prof_end; leaves the calling function with the code of whichever fails.
+// PROF_HIP_TRY enqueues in plan mode as well (HIP_TRY), PROF_LAUNCH_TRY does not (LAUNCH_TRY); `expr` is the launch, a hipError_t.
+#define PROF_TRY_(TRY, ctx, name, flops, bytes, expr)                                                  \
+  do {                                                                                                 \
+    Launch l__{ctx};                                                                                   \
+    hipEvent_t e0__ = nullptr, e1__ = nullptr;                                                         \
+    int rc__;                                                                                          \
+    if ((rc__ = l__.prof_begin(name, flops, bytes, e0__, e1__))) return rc__;                          \
+    TRY(ctx, expr);                                                                                    \
+    if ((rc__ = l__.prof_end(e1__))) return rc__;                                                      \
+  } while (0)
+#define PROF_HIP_TRY(ctx, name, flops, bytes, expr) PROF_TRY_(HIP_TRY, ctx, name, flops, bytes, expr)
+#define PROF_LAUNCH_TRY(ctx, name, flops, bytes, expr) PROF_TRY_(LAUNCH_TRY, ctx, name, flops, bytes, expr)
+
 // contiguous shard of n items for device g of G (fastintercu-vvc_amd/shard.py: shard_bounds)
 inline int shard_lo(int n, int g, int G) { return (int)(((long long)n * g) / G); }
 inline mlt_ctx *device_of(mlt_ctx *ctx, int i) { return i == 0 ? ctx : ctx->peers[(size_t)i - 1]; }
@@ -427,6 +441,9 @@ template <class F> int run_sharded(mlt_ctx *ctx, int n, F per_device) {
 // mlt_pictures.cpp
 void free_pictures(mlt_ctx *ctx);               // mlt_shutdown: before the peers go
 bool owns_picture(const mlt_ctx *ctx, const mlt_picture *pic);
+const int kPictureMinDim = 16, kPictureMaxDim = 16384;   // a picture's width and height (mlt_picture_create)
+// the picture pair of a one-pair call: both of this context, one geometry (`who` opens the message)
+int check_at_pair(mlt_ctx *ctx, const char *who, const mlt_picture *org, const mlt_picture *pred);
 // the picture pair as one device sees it | the CUs of a call: a host list with poc / qp per CU, a DEVICE list of positions that all take one (poc, qp) pair, or a
 // device list over the entries of a device table (mlt_predict_trees: AtPlanes is not read) |
 // where the results go (host arrays for a host list, device arrays for a device list; any may be NULL)
@@ -445,6 +462,11 @@ struct AtList {
 };
 struct AtOut { int32_t *split; float *logits; mlt_decision *dec; mlt_candidates *cand; };
 int predict_at_chunks(mlt_ctx *dev, SizeState *st, const AtPlanes &pl, int n, const AtList &at, const AtOut &out);
+// One chunk's gather, enqueued on dev's stream: the c CUs of size x size at d_xy (device) out of the pair's planes into the dense staging planes g_org / g_pred --
+// or, with d_pic, CU i out of the planes of entry d_pic[i] of the device table `entries`, its poc and qp into g_poc / g_qp besides (pl is not read).
+struct GatherSrc { AtPlanes pl; const TreesEntry *entries; int n_entries; };
+int enqueue_gather(mlt_ctx *dev, const GatherSrc &src, const int32_t *d_xy, const int32_t *d_pic, int16_t *g_org, int16_t *g_pred, int32_t *g_poc, int32_t *g_qp, int c,
+                   int size);
 // mlt_dispatch.cpp
 void release_ws(mlt_ctx *ctx);
 int run_network(mlt_ctx *ctx, SizeState &st, const NetCfg &c, int n, const PassIO &io, const GuardOut &go = GuardOut());

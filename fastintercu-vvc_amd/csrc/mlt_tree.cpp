@@ -9,12 +9,14 @@
 // arrays are slices of the arena's.  One picture's arena is already in the contract's order and mlt_predict_tree ends in a handful of D2H copies;
 // mlt_predict_trees lets tree_pack_kernel permute into the picture-major order of its contract first, then one D2H copy per requested array.
 // mlt_predict_tree_sweep (one pair, several qp) and mlt_predict_trees_sweep (several pairs, several qp each) run ONE descent of their own over the UNION of every
-// entry's trees: descend_sweep below, P = 1 for the former.
+// entry's trees: descend_sweep below, P = 1 for the former; rank and pack kernels cut the union into one slice per (entry, point): sweep_results.
+// What the two descents and the four entry points share is written once: the checks of the entries and of node_cap (check_tree_entries, check_node_cap), the
+// call's device tables (upload_tree_tables), a level's count coming back (read_level_count) and the copy of a packed result to the caller (copy_packed).  The
+// gather of a chunk is mlt_pictures.cpp's enqueue_gather in both descents.
 #include "mlt_runtime.h"
 
 namespace {
 
-const int kMinDim = 16, kMaxDim = 16384;   // a picture's geometry (mlt_picture_create)
 const int kRowLogits = Lay::TreeArena::kRow;   // floats the arena reserves per node (a level's logits are dense [n][n_logits] from the level's first row)
 
 bool tree_sizes(int &top, int &mn) {
@@ -22,7 +24,7 @@ bool tree_sizes(int &top, int &mn) {
   if (mn == 0) mn = 16;
   return size_index(top) >= 0 && size_index(mn) >= 0 && mn <= top;
 }
-bool dims_ok(int w, int h) { return w >= kMinDim && h >= kMinDim && w <= kMaxDim && h <= kMaxDim; }
+bool dims_ok(int w, int h) { return w >= kPictureMinDim && h >= kPictureMinDim && w <= kPictureMaxDim && h <= kPictureMaxDim; }
 
 // roots of level S under top: the whole grid at top; below, the complete S-aligned CUs right of / under the area the complete 2S-aligned blocks cover
 int roots_of(int w, int h, int top, int S, int32_t *xy, int cap) {
@@ -71,20 +73,100 @@ void tree_roots_of(int W, int H, int top, int L, TreeRoots &r) {
   }
 }
 
-// the picture pair of a one-pair call: both of this context, one geometry
-int tree_pair(mlt_ctx *ctx, const char *who, const mlt_picture *org, const mlt_picture *pred) {
-  if (!owns_picture(ctx, org) || !owns_picture(ctx, pred)) { ctx->err = std::string(who) + ": both pictures must belong to this context"; return MLT_ERR_ARG; }
-  if (org->width != pred->width || org->height != pred->height) { ctx->err = std::string(who) + ": the two pictures differ in width or height"; return MLT_ERR_ARG; }
+// the entries of a several-pair call: every pair given and of this context, one geometry over the call; with qps: every entry's qp offset + point fits int32
+int check_tree_entries(mlt_ctx *ctx, const char *who, int P, const mlt_tree_picture *pics, const int32_t *qps = nullptr, int Q = 0) {
+  char msg[224];
+  for (int p = 0; p < P; ++p) {
+    const mlt_picture *o = pics[p].org, *q = pics[p].pred;
+    if (!o || !q || !owns_picture(ctx, o) || !owns_picture(ctx, q)) {
+      std::snprintf(msg, sizeof msg, "%s: entry %d: both pictures must be given and belong to this context", who, p);
+      ctx->err = msg;
+      return MLT_ERR_ARG;
+    }
+    if (o->width != q->width || o->height != q->height || o->width != pics[0].org->width || o->height != pics[0].org->height) {
+      std::snprintf(msg, sizeof msg, "%s: entry %d: every picture of a call must have the width and height of entry 0's (%d x %d)", who, p, pics[0].org->width,
+                    pics[0].org->height);
+      ctx->err = msg;
+      return MLT_ERR_ARG;
+    }
+    for (int k = 0; k < Q; ++k) {   // the QP of entry p under point k
+      const long long qp = (long long)pics[p].qp + (long long)qps[k];
+      if (qp < INT32_MIN || qp > INT32_MAX) {
+        std::snprintf(msg, sizeof msg, "%s: entry %d: its qp offset %d + qps[%d] = %d does not fit int32", who, p, pics[p].qp, k, qps[k]);
+        ctx->err = msg;
+        return MLT_ERR_ARG;
+      }
+    }
+  }
   return MLT_OK;
 }
 
-// which optional outputs a tree call delivers | what a descent leaves behind: the arena, the node count over all pictures and every level's node range
-struct TreeWant { bool map, logits, dec, cand; };
+// node_cap against the call's trees (`factors`: its pictures, its points, both, or none for one tree) x mlt_tree_max_nodes of one W x H picture
+int check_node_cap(mlt_ctx *ctx, const char *who, int node_cap, std::initializer_list<int> factors, int max_nodes, int W, int H) {
+  long long cap_all = max_nodes;
+  std::string times;
+  for (int f : factors) { cap_all *= f; times += std::to_string(f) + " x "; }
+  if (node_cap >= cap_all && cap_all <= 0x7fffffff) return MLT_OK;
+  char msg[224];
+  std::snprintf(msg, sizeof msg, "%s: node_cap %d is below %smlt_tree_max_nodes = %d of a %d x %d picture", who, node_cap, times.c_str(), max_nodes, W, H);
+  ctx->err = msg;
+  return MLT_ERR_ARG;
+}
+
+// the optional outputs of a tree call as the caller gave them (NULL: not wanted) | whether the call descends on the candidate sets
+struct TreeOut { uint8_t *maps; float *logits; int logit_stride; mlt_decision *dec; mlt_candidates *cand; };
+bool by_candidates(const mlt_tree_config *cfg) { return (cfg->flags & MLT_TREE_BY_CANDIDATES) != 0; }
+
+// What either descent puts on the device before its first launch (A: its arena): the entry table of a call over several pairs -- one pair's planes, poc and qp are
+// launch arguments of the gather --, the roots of every level and the 0xFF fill of the `maps` leaf maps; the pinned word the level counts come back through.
+template <class Ptrs> int upload_tree_tables(mlt_ctx *ctx, const Ptrs &A, int P, const mlt_tree_picture *pics, const TreeRoots &tr, size_t maps, size_t map_bytes) {
+  if (!ctx->tree_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->tree_host, 64, hipHostMallocDefault));
+  if (P > 1) {
+    std::vector<TreesEntry> entries((size_t)P);
+    for (int p = 0; p < P; ++p) {
+      const AtPlanes pl = AtPlanes::of(pics[p].org, pics[p].pred, 0);
+      entries[(size_t)p] = TreesEntry{pl.org, pl.pred, pl.org_pitch, pl.pred_pitch, pl.org_vec ? 1 : 0, pl.pred_vec ? 1 : 0, pics[p].poc, pics[p].qp};
+    }
+    // (pageable sources: both copies have read them when they return)
+    HIP_TRY(ctx, hipMemcpyAsync(A.entries, entries.data(), entries.size() * sizeof(TreesEntry), hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (!tr.xy.empty()) HIP_TRY(ctx, hipMemcpyAsync(A.roots, tr.xy.data(), tr.xy.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (maps) HIP_TRY(ctx, hipMemsetAsync(A.map, 0xFF, maps * map_bytes, ctx->stream));
+  return MLT_OK;
+}
+
+// The one host synchronisation of a level beside the guards': n <- how many nodes the next level has over all pictures -- its `roots` and four per descending
+// node, `room` at most.
+template <class Ptrs> int read_level_count(mlt_ctx *ctx, const char *who, const Ptrs &A, long long roots, long long room, int &n) {
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->tree_host, A.count, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  n = ctx->tree_host[0];
+  if (n < roots || ((n - roots) & 3) || n > room) { ctx->err = std::string(who) + ": bad node count from the device"; return MLT_ERR_HIP; }
+  return MLT_OK;
+}
+
+// The packed output of an arena (A.o_*: `total` nodes, picture- or slice-major) and its `maps` leaf maps to the caller, enqueued: nodes, whole zero-padded logits
+// rows, records, candidate records, maps.
+template <class Ptrs> int copy_packed(mlt_ctx *ctx, const Ptrs &A, int total, size_t maps, size_t map_bytes, mlt_tree_node *nodes, const TreeOut &out) {
+  if (total) {
+    HIP_TRY(ctx, hipMemcpyAsync(nodes, A.o_nodes, (size_t)total * sizeof(TreeNodeRec), hipMemcpyDeviceToHost, ctx->stream));
+    if (out.logits) {
+      if (out.logit_stride == kRowLogits) HIP_TRY(ctx, hipMemcpyAsync(out.logits, A.o_logits, (size_t)total * kRowLogits * 4, hipMemcpyDeviceToHost, ctx->stream));
+      else HIP_TRY(ctx, hipMemcpy2DAsync(out.logits, (size_t)out.logit_stride * 4, A.o_logits, (size_t)kRowLogits * 4, (size_t)kRowLogits * 4, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (out.dec) HIP_TRY(ctx, hipMemcpyAsync(out.dec, A.o_dec, (size_t)total * sizeof(DecisionRec), hipMemcpyDeviceToHost, ctx->stream));
+    if (out.cand) HIP_TRY(ctx, hipMemcpyAsync(out.cand, A.o_cand, (size_t)total * sizeof(CandRec), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (out.maps) HIP_TRY(ctx, hipMemcpyAsync(out.maps, A.map, maps * map_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  return MLT_OK;
+}
+
+// what a descent leaves behind: the arena, the node count over all pictures and every level's node range
 struct Descent { Lay::TreeArena::Ptrs A; size_t map_bytes; int total, start[4], n[4]; };
 
 // The descent of the trees of pics[0 .. P) (W x H each, checked by the caller) on this context's own device; everything stays in the arena, enqueued or done.
 // packed: the arena also carries the entry table and tree_pack_kernel's picture-major output.
-int descend(mlt_ctx *ctx, const char *who, const TreeLevels &lv, int W, int H, int P, const mlt_tree_picture *pics, bool by_cand, bool packed, const TreeWant &want,
+int descend(mlt_ctx *ctx, const char *who, const TreeLevels &lv, int W, int H, int P, const mlt_tree_picture *pics, bool by_cand, bool packed, const TreeOut &want,
             Descent &d) {
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
   const int top = lv.top, L = lv.L, max_nodes = mlt_tree_max_nodes(W, H, top, lv.mn), N = P * max_nodes;
@@ -98,35 +180,20 @@ int descend(mlt_ctx *ctx, const char *who, const TreeLevels &lv, int W, int H, i
   const size_t map_bytes = d.map_bytes = (size_t)map_w * map_h;
   const Lay::TreeArena arena((size_t)P, (size_t)max_nodes, tr.xy.size() / 2, map_bytes, sizeof(TreesEntry), any_cand, packed, want.logits, want.dec, want.cand);
   if ((rc = ctx->tree_dev.reserve(ctx, arena.bytes(), who))) return rc;
-  if (!ctx->tree_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->tree_host, 64, hipHostMallocDefault));
   const Lay::TreeArena::Ptrs A = d.A = arena.at(ctx->tree_dev.p);
   // One pair: its planes, poc and qp are launch arguments of the gather (no table lookup per item).  Several: the entry table, looked up through the nodes' pic.
   const AtPlanes planes = P == 1 ? AtPlanes::of(pics[0].org, pics[0].pred, 0) : AtPlanes{};
-  if (P > 1) {
-    std::vector<TreesEntry> entries((size_t)P);
-    for (int p = 0; p < P; ++p) {
-      const AtPlanes pl = AtPlanes::of(pics[p].org, pics[p].pred, 0);
-      entries[(size_t)p] = TreesEntry{pl.org, pl.pred, pl.org_pitch, pl.pred_pitch, pl.org_vec ? 1 : 0, pl.pred_vec ? 1 : 0, pics[p].poc, pics[p].qp};
-    }
-    // (pageable sources: both copies have read them when they return)
-    HIP_TRY(ctx, hipMemcpyAsync(A.entries, entries.data(), entries.size() * sizeof(TreesEntry), hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (!tr.xy.empty()) HIP_TRY(ctx, hipMemcpyAsync(A.roots, tr.xy.data(), tr.xy.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (want.map) HIP_TRY(ctx, hipMemsetAsync(A.map, 0xFF, (size_t)P * map_bytes, ctx->stream));
-  Launch prof{ctx};
+  if ((rc = upload_tree_tables(ctx, A, P, pics, tr, want.maps ? (size_t)P : 0, map_bytes))) return rc;
   auto expand = [&](const TreeExpandArgs &ea) -> int {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int r;
     // algorithmic bytes the host knows: the level's records and picture indices read and its node fields written, every picture's next roots written, the segment
     // table's rows (the children's count is the device's)
-    if ((r = prof.prof_begin("tree_expand", 0.0, (double)ea.lvl_n * (sizeof(DecisionRec) + 20) + (double)P * ea.n_next_roots * (sizeof(TreeNodeRec) + 12) + (double)P * 8, e0, e1)))
-      return r;
-    HIP_TRY(ctx, mlt_launch_tree_expand(ea, ctx->stream));
-    return prof.prof_end(e1);
+    PROF_HIP_TRY(ctx, "tree_expand", 0.0, (double)ea.lvl_n * (sizeof(DecisionRec) + 20) + (double)P * ea.n_next_roots * (sizeof(TreeNodeRec) + 12) + (double)P * 8,
+                 mlt_launch_tree_expand(ea, ctx->stream));
+    return MLT_OK;
   };
   TreeExpandArgs ea{};
   ea.nodes = A.nodes; ea.xy = A.xy; ea.pic = A.pic; ea.node_cap = N; ea.by_candidates = by_cand ? 1 : 0;
-  ea.segs = TreesSegs{A.seg_start, A.seg_n, A.pack_base}; ea.n_pictures = P; ea.n_levels = L; ea.first_node = A.first_node;
+  ea.seg_start = A.seg_start; ea.seg_n = A.seg_n; ea.pack_base = A.pack_base; ea.n_pictures = P; ea.n_levels = L; ea.first_node = A.first_node;
   // the trees open: no parents, every picture's top-level roots
   ea.lvl_start = 0; ea.lvl_n = 0; ea.size = 2 * top; ea.lvl = -1;
   ea.next_roots = A.roots; ea.n_next_roots = tr.n[0]; ea.root_flags = 0; ea.count = nullptr;
@@ -154,23 +221,15 @@ int descend(mlt_ctx *ctx, const char *who, const TreeLevels &lv, int W, int H, i
     ea.root_flags = 1;
     ea.count = last ? nullptr : A.count;
     if ((rc = expand(ea))) return rc;
-    if (n > 0 && want.map) {
+    if (n > 0 && want.maps) {
       TreeRasterArgs ra{};
       ra.nodes = A.nodes; ra.pic = A.pic; ra.lvl_start = start; ra.lvl_n = n; ra.blk_l = ilog2(S) - 4; ra.map = A.map; ra.map_bytes = map_bytes; ra.map_w = map_w; ra.map_h = map_h;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
       // algorithmic bytes: every node record and picture index read once, one byte per block of a leaf written (at most the level's whole area)
-      if ((rc = prof.prof_begin("tree_raster", 0.0, (double)n * (sizeof(TreeNodeRec) + 4 + (double)(1 << (2 * ra.blk_l))), e0, e1))) return rc;
-      HIP_TRY(ctx, mlt_launch_tree_raster(ra, ctx->stream));
-      if ((rc = prof.prof_end(e1))) return rc;
+      PROF_HIP_TRY(ctx, "tree_raster", 0.0, (double)n * (sizeof(TreeNodeRec) + 4 + (double)(1 << (2 * ra.blk_l))), mlt_launch_tree_raster(ra, ctx->stream));
     }
     start += n;
     if (last) break;
-    // the one host synchronisation of the level beside the guards': how many nodes the next level has, over all pictures
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->tree_host, A.count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    n = ctx->tree_host[0];
-    const int nr = P * tr.n[l + 1];
-    if (n < nr || ((n - nr) & 3) || (long long)start + n > N) { ctx->err = std::string(who) + ": bad node count from the device"; return MLT_ERR_HIP; }
+    if ((rc = read_level_count(ctx, who, A, (long long)P * tr.n[l + 1], (long long)N - start, n))) return rc;
   }
   d.total = start;
   return MLT_OK;
@@ -184,7 +243,7 @@ int descend(mlt_ctx *ctx, const char *who, const TreeLevels &lv, int W, int H, i
 // the nodes' pic by picture_gather_multi_kernel, which also writes the chunk's per-CU poc and qp -- the entry's OFFSET, which the sweep heads add to every point.
 struct SweepDescent { Lay::TreeSweepArena::Ptrs A; size_t map_bytes; int n[4], start[4], cap[4]; bool has_cand[4]; };
 int descend_sweep(mlt_ctx *ctx, const char *who, const TreeLevels &lv, int W, int H, int P, const mlt_tree_picture *pics, const int32_t *qps, int Q, bool by_cand,
-                  const TreeWant &want, SweepDescent &d) {
+                  const TreeOut &want, SweepDescent &d) {
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MLT_ERR_NO_DEVICE; }
   const int top = lv.top, L = lv.L;
   int rc;
@@ -201,34 +260,20 @@ int descend_sweep(mlt_ctx *ctx, const char *who, const TreeLevels &lv, int W, in
   const int map_w = W / 16, map_h = H / 16;
   const size_t map_bytes = d.map_bytes = (size_t)map_w * map_h;
   // logits: the caller's, or what cand_mask is made from on the levels without candidate records
-  const Lay::TreeSweepArena arena((size_t)Q, L, lvl_cap, tr.xy.size() / 2, map_bytes, want.logits || !all_cand, any_cand, want.map, want.logits, want.dec, want.cand, (size_t)P,
-                                  sizeof(TreesEntry));
+  const Lay::TreeSweepArena arena((size_t)Q, L, lvl_cap, tr.xy.size() / 2, map_bytes, want.logits || !all_cand, any_cand, want.maps != nullptr, want.logits, want.dec,
+                                  want.cand, (size_t)P, sizeof(TreesEntry));
   if ((rc = ctx->tree_dev.reserve(ctx, arena.bytes(), who))) return rc;
-  if (!ctx->tree_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->tree_host, 64, hipHostMallocDefault));
   const Lay::TreeSweepArena::Ptrs A = d.A = arena.at(ctx->tree_dev.p);
   const int N = (int)arena.n;
-  const AtPlanes pl = AtPlanes::of(pics[0].org, pics[0].pred, 0);
-  if (P > 1) {
-    std::vector<TreesEntry> entries((size_t)P);
-    for (int p = 0; p < P; ++p) {
-      const AtPlanes e = AtPlanes::of(pics[p].org, pics[p].pred, 0);
-      entries[(size_t)p] = TreesEntry{e.org, e.pred, e.org_pitch, e.pred_pitch, e.org_vec ? 1 : 0, e.pred_vec ? 1 : 0, pics[p].poc, pics[p].qp};
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(A.entries, entries.data(), entries.size() * sizeof(TreesEntry), hipMemcpyHostToDevice, ctx->stream));   // (pageable: read when the copy returns)
-  }
-  if (!tr.xy.empty()) HIP_TRY(ctx, hipMemcpyAsync(A.roots, tr.xy.data(), tr.xy.size() * 4, hipMemcpyHostToDevice, ctx->stream));   // (pageable: read when the copy returns)
-  if (want.map) HIP_TRY(ctx, hipMemsetAsync(A.map, 0xFF, (size_t)P * (size_t)Q * map_bytes, ctx->stream));
-  Launch prof{ctx};
+  const GatherSrc src{AtPlanes::of(pics[0].org, pics[0].pred, 0), (const TreesEntry *)A.entries, P};
+  if ((rc = upload_tree_tables(ctx, A, P, pics, tr, want.maps ? (size_t)P * (size_t)Q : 0, map_bytes))) return rc;
   auto expand = [&](const TreeSweepExpandArgs &ea) -> int {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int r;
     // algorithmic bytes the host knows: the level's alive masks and, under every point, its records read, its node fields written, the next roots written
     // (several entries: + a picture index per node and root, the segment table's rows)
     double bytes = (double)ea.lvl_n * ((double)Q * sizeof(DecisionRec) + 16) + (double)P * ea.n_next_roots * (sizeof(TreeNodeRec) + 24);
     if (P > 1) bytes += 4.0 * ((double)ea.lvl_n + (double)P * ea.n_next_roots) + (double)P * 8;
-    if ((r = prof.prof_begin("tree_expand_sweep", 0.0, bytes, e0, e1))) return r;
-    HIP_TRY(ctx, mlt_launch_tree_expand_sweep(ea, ctx->stream));
-    return prof.prof_end(e1);
+    PROF_HIP_TRY(ctx, "tree_expand_sweep", 0.0, bytes, mlt_launch_tree_expand_sweep(ea, ctx->stream));
+    return MLT_OK;
   };
   SweepPart sw;
   sw.n_qps = Q;
@@ -259,21 +304,9 @@ int descend_sweep(mlt_ctx *ctx, const char *who, const TreeLevels &lv, int W, in
       if (P == 1) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)G.d_poc, pics[0].poc, (size_t)cap, ctx->stream));   // one poc: every chunk reads its first c entries
       for (int i0 = 0; i0 < n; i0 += cap) {
         const int c = n - i0 < cap ? n - i0 : cap;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (P == 1) {
-          PictureGatherArgs ga{};
-          ga.org = pl.org; ga.pred = pl.pred; ga.org_pitch = pl.org_pitch; ga.pred_pitch = pl.pred_pitch; ga.vec_org = pl.org_vec; ga.vec_pred = pl.pred_vec;
-          ga.xy = A.xy + 2 * ((size_t)start + (size_t)i0); ga.g_org = G.d_org; ga.g_pred = G.d_pred; ga.c = c; ga.s_l = ilog2(S);
-          if ((rc = prof.prof_begin("picture_gather", 0.0, (double)c * S * S * 2 * 2 * 2, e0, e1))) return rc;
-          LAUNCH_TRY(ctx, mlt_launch_picture_gather(ga, ctx->stream));
-        } else {   // the chunk's slice of the list and of its entry indices; the launch writes the chunk's poc and qp offsets as well
-          PictureGatherMultiArgs ga{};
-          ga.entries = (const TreesEntry *)A.entries; ga.n_entries = P; ga.pic = A.pic + start + i0; ga.xy = A.xy + 2 * ((size_t)start + (size_t)i0);
-          ga.g_org = G.d_org; ga.g_pred = G.d_pred; ga.g_poc = G.d_poc; ga.g_qp = G.d_qp; ga.c = c; ga.s_l = ilog2(S);
-          if ((rc = prof.prof_begin("picture_gather_multi", 0.0, (double)c * (S * S * 2 * 2 * 2 + 12), e0, e1))) return rc;
-          LAUNCH_TRY(ctx, mlt_launch_picture_gather_multi(ga, ctx->stream));
-        }
-        if ((rc = prof.prof_end(e1))) return rc;
+        // the chunk's slice of the list and (several entries) of its entry indices: that launch writes the chunk's poc and qp offsets as well
+        if ((rc = enqueue_gather(ctx, src, A.xy + 2 * ((size_t)start + (size_t)i0), P == 1 ? nullptr : A.pic + start + i0, G.d_org, G.d_pred, G.d_poc, G.d_qp, c, S)))
+          return rc;
         sw.active = A.alive + start + i0;
         const PassIO io{Planes::dense(G.d_org, G.d_pred, S), G.d_poc, P == 1 ? nullptr : G.d_qp, nullptr, d_lg ? d_lg + (size_t)i0 * nl : nullptr, d_dec + i0,
                         d_cand ? d_cand + i0 : nullptr, sw};
@@ -288,23 +321,16 @@ int descend_sweep(mlt_ctx *ctx, const char *who, const TreeLevels &lv, int W, in
     ea.root_flags = 1;
     ea.count = last ? nullptr : A.count;
     if ((rc = expand(ea))) return rc;
-    if (n > 0 && want.map) {
+    if (n > 0 && want.maps) {
       TreeSweepRasterArgs ra{};
       ra.nodes = A.nodes; ra.alive = A.alive; ra.desc = A.desc; ra.pic = A.pic; ra.dec = d_dec; ra.slab = sw.slab; ra.lvl_start = start; ra.lvl_n = n; ra.blk_l = ilog2(S) - 4;
       ra.n_qps = Q; ra.n_pictures = P; ra.map = A.map; ra.map_bytes = map_bytes; ra.map_w = map_w; ra.map_h = map_h;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
       // algorithmic bytes: every node record and mask pair read once, one byte per block of a leaf written under every point (at most the level's whole area each)
-      if ((rc = prof.prof_begin("tree_sweep_raster", 0.0, (double)n * (sizeof(TreeNodeRec) + 8 + (P > 1 ? 4 : 0) + (double)Q * (1 << (2 * ra.blk_l))), e0, e1))) return rc;
-      HIP_TRY(ctx, mlt_launch_tree_sweep_raster(ra, ctx->stream));
-      if ((rc = prof.prof_end(e1))) return rc;
+      PROF_HIP_TRY(ctx, "tree_sweep_raster", 0.0, (double)n * (sizeof(TreeNodeRec) + 8 + (P > 1 ? 4 : 0) + (double)Q * (1 << (2 * ra.blk_l))),
+                   mlt_launch_tree_sweep_raster(ra, ctx->stream));
     }
     if (last) break;
-    // the one host synchronisation of the level beside the guards': how many nodes the unions' next level has, over all entries
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->tree_host, A.count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    n = ctx->tree_host[0];
-    const long long nr = (long long)P * tr.n[l + 1];
-    if (n < nr || ((n - nr) & 3) || (size_t)n > arena.cap[l + 1]) { ctx->err = std::string(who) + ": bad node count from the device"; return MLT_ERR_HIP; }
+    if ((rc = read_level_count(ctx, who, A, (long long)P * tr.n[l + 1], (long long)arena.cap[l + 1], n))) return rc;
   }
   for (int l = L; l < 4; ++l) { d.start[l] = 0; d.n[l] = 0; d.cap[l] = 0; d.has_cand[l] = false; }
   return MLT_OK;
@@ -313,11 +339,10 @@ int descend_sweep(mlt_ctx *ctx, const char *who, const TreeLevels &lv, int W, in
 // What follows a union descent: rank and pack -- one slice per (entry, point), slice p * Q + q -- then everything the caller asked for and one synchronisation.
 // max_nodes: mlt_tree_max_nodes of one picture.
 int sweep_results(mlt_ctx *ctx, const char *who, const TreeLevels &lv, const SweepDescent &d, int P, int Q, int max_nodes, mlt_tree_node *nodes, int32_t *first_node,
-                  int32_t *union_nodes_opt, uint8_t *leaf_maps_opt, float *logits_opt, int logit_stride, mlt_decision *dec_opt, mlt_candidates *cand_opt) {
+                  int32_t *union_nodes_opt, const TreeOut &out) {
   const Lay::TreeSweepArena::Ptrs &A = d.A;
   const long long cap_all = (long long)P * Q * max_nodes;
   const size_t PQ = (size_t)P * (size_t)Q;
-  int rc;
   TreeSweepPackArgs pa{};
   pa.nodes = A.nodes; pa.alive = A.alive; pa.desc = A.desc; pa.dec = A.dec; pa.logits = A.logits; pa.cand = A.cand;
   pa.pic = A.pic; pa.seg_start = A.seg_start; pa.seg_n = A.seg_n; pa.n_pictures = P;
@@ -330,19 +355,11 @@ int sweep_results(mlt_ctx *ctx, const char *who, const TreeLevels &lv, const Swe
     pa.n_logits[l] = lv.st[l]->model.n_logits; pa.head_off[l] = lv.st[l]->head_off(); pa.head_classes[l] = lv.st[l]->head_classes();
     un += d.n[l];
   }
-  {
-    Launch prof{ctx};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    // algorithmic bytes: the alive mask of every union node read and its index written under every point | per (point, node) at most one node record, its slab
-    // record and the requested rows and records, read and written
-    if ((rc = prof.prof_begin("tree_sweep_rank", 0.0, (double)Q * (double)un * 8, e0, e1))) return rc;
-    HIP_TRY(ctx, mlt_launch_tree_sweep_rank(pa, ctx->stream));
-    if ((rc = prof.prof_end(e1))) return rc;
-    const double per = 2.0 * sizeof(TreeNodeRec) + 12 + sizeof(DecisionRec) + (logits_opt ? 2.0 * kRowLogits * 4 : 0) + (dec_opt ? sizeof(DecisionRec) : 0) + (cand_opt ? 2.0 * sizeof(CandRec) : 0);
-    if ((rc = prof.prof_begin("tree_sweep_pack", 0.0, (double)Q * (double)un * per, e0, e1))) return rc;
-    HIP_TRY(ctx, mlt_launch_tree_sweep_pack(pa, ctx->stream));
-    if ((rc = prof.prof_end(e1))) return rc;
-  }
+  // algorithmic bytes: the alive mask of every union node read and its index written under every point | per (point, node) at most one node record, its slab
+  // record and the requested rows and records, read and written
+  const double per = 2.0 * sizeof(TreeNodeRec) + 12 + sizeof(DecisionRec) + (out.logits ? 2.0 * kRowLogits * 4 : 0) + (out.dec ? sizeof(DecisionRec) : 0) + (out.cand ? 2.0 * sizeof(CandRec) : 0);
+  PROF_HIP_TRY(ctx, "tree_sweep_rank", 0.0, (double)Q * (double)un * 8, mlt_launch_tree_sweep_rank(pa, ctx->stream));
+  PROF_HIP_TRY(ctx, "tree_sweep_pack", 0.0, (double)Q * (double)un * per, mlt_launch_tree_sweep_pack(pa, ctx->stream));
   // the slices' sizes first: the copies below take exactly the packed nodes (the caller's arrays stay untouched behind them)
   std::vector<int32_t> first(PQ + 1), un_l((size_t)P * 4);
   HIP_TRY(ctx, hipMemcpyAsync(first.data(), A.first_node, (PQ + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -352,16 +369,7 @@ int sweep_results(mlt_ctx *ctx, const char *who, const TreeLevels &lv, const Swe
   bool ok = first[0] == 0 && total >= 0 && total <= cap_all;
   for (size_t s = 0; s < PQ && ok; ++s) ok = first[s + 1] >= first[s];
   if (!ok) { ctx->err = std::string(who) + ": bad node count from the device"; return MLT_ERR_HIP; }
-  if (total) {
-    HIP_TRY(ctx, hipMemcpyAsync(nodes, A.o_nodes, (size_t)total * sizeof(TreeNodeRec), hipMemcpyDeviceToHost, ctx->stream));
-    if (logits_opt) {   // whole zero-padded rows
-      if (logit_stride == kRowLogits) HIP_TRY(ctx, hipMemcpyAsync(logits_opt, A.o_logits, (size_t)total * kRowLogits * 4, hipMemcpyDeviceToHost, ctx->stream));
-      else HIP_TRY(ctx, hipMemcpy2DAsync(logits_opt, (size_t)logit_stride * 4, A.o_logits, (size_t)kRowLogits * 4, (size_t)kRowLogits * 4, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (dec_opt) HIP_TRY(ctx, hipMemcpyAsync(dec_opt, A.o_dec, (size_t)total * sizeof(DecisionRec), hipMemcpyDeviceToHost, ctx->stream));
-    if (cand_opt) HIP_TRY(ctx, hipMemcpyAsync(cand_opt, A.o_cand, (size_t)total * sizeof(CandRec), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (leaf_maps_opt) HIP_TRY(ctx, hipMemcpyAsync(leaf_maps_opt, A.map, PQ * d.map_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (int rc = copy_packed(ctx, A, total, PQ, d.map_bytes, nodes, out)) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   std::memcpy(first_node, first.data(), (PQ + 1) * 4);
   if (union_nodes_opt) std::memcpy(union_nodes_opt, un_l.data(), (size_t)P * 16);
@@ -397,21 +405,14 @@ int mlt_predict_tree(mlt_ctx *ctx, const mlt_picture *org, const mlt_picture *pr
   TreeLevels lv;
   int rc;
   if ((rc = tree_levels(ctx, "mlt_predict_tree", cfg, lv))) return rc;
-  if ((rc = tree_pair(ctx, "mlt_predict_tree", org, pred))) return rc;
+  if ((rc = check_at_pair(ctx, "mlt_predict_tree", org, pred))) return rc;
   const int W = org->width, H = org->height;
   const int max_nodes = mlt_tree_max_nodes(W, H, lv.top, lv.mn);
-  if (node_cap < max_nodes) {
-    char msg[160];
-    std::snprintf(msg, sizeof msg, "mlt_predict_tree: node_cap %d is below mlt_tree_max_nodes = %d of a %d x %d picture", node_cap, max_nodes, W, H);
-    ctx->err = msg;
-    return MLT_ERR_ARG;
-  }
+  if ((rc = check_node_cap(ctx, "mlt_predict_tree", node_cap, {}, max_nodes, W, H))) return rc;
   // ---- arguments are good: the tree runs on this context's own device (devices[0] of a multi-device context) ----
   const mlt_tree_picture one{org, pred, cfg->poc, cfg->qp};
   Descent d;
-  if ((rc = descend(ctx, "mlt_predict_tree", lv, W, H, 1, &one, (cfg->flags & MLT_TREE_BY_CANDIDATES) != 0, false,
-                    TreeWant{leaf_map_opt != nullptr, logits_opt != nullptr, dec_opt != nullptr, cand_opt != nullptr}, d)))
-    return rc;
+  if ((rc = descend(ctx, "mlt_predict_tree", lv, W, H, 1, &one, by_candidates(cfg), false, TreeOut{leaf_map_opt, logits_opt, logit_stride, dec_opt, cand_opt}, d))) return rc;
   // ---- results: one picture's arena is in the contract's order; everything the caller asked for, then one synchronisation ----
   const Lay::TreeArena::Ptrs &A = d.A;
   if (d.total) HIP_TRY(ctx, hipMemcpyAsync(nodes, A.nodes, (size_t)d.total * sizeof(TreeNodeRec), hipMemcpyDeviceToHost, ctx->stream));
@@ -443,35 +444,14 @@ int mlt_predict_trees(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture *pics
   int rc;
   if ((rc = tree_levels(ctx, "mlt_predict_trees", cfg, lv))) return rc;
   const int P = n_pictures;
-  for (int p = 0; p < P; ++p) {
-    const mlt_picture *o = pics[p].org, *q = pics[p].pred;
-    char msg[192];
-    if (!o || !q || !owns_picture(ctx, o) || !owns_picture(ctx, q)) {
-      std::snprintf(msg, sizeof msg, "mlt_predict_trees: entry %d: both pictures must be given and belong to this context", p);
-      ctx->err = msg;
-      return MLT_ERR_ARG;
-    }
-    if (o->width != q->width || o->height != q->height || o->width != pics[0].org->width || o->height != pics[0].org->height) {
-      std::snprintf(msg, sizeof msg, "mlt_predict_trees: entry %d: every picture of a call must have the width and height of entry 0's (%d x %d)", p, pics[0].org->width,
-                    pics[0].org->height);
-      ctx->err = msg;
-      return MLT_ERR_ARG;
-    }
-  }
+  if ((rc = check_tree_entries(ctx, "mlt_predict_trees", P, pics))) return rc;
   const int W = pics[0].org->width, H = pics[0].org->height;
   const int max_nodes = mlt_tree_max_nodes(W, H, lv.top, lv.mn);
-  const long long cap_all = (long long)P * max_nodes;
-  if (node_cap < cap_all || cap_all > 0x7fffffff) {
-    char msg[192];
-    std::snprintf(msg, sizeof msg, "mlt_predict_trees: node_cap %d is below %d x mlt_tree_max_nodes = %d of a %d x %d picture", node_cap, P, max_nodes, W, H);
-    ctx->err = msg;
-    return MLT_ERR_ARG;
-  }
+  if ((rc = check_node_cap(ctx, "mlt_predict_trees", node_cap, {P}, max_nodes, W, H))) return rc;
   // ---- arguments are good: the trees run on this context's own device (devices[0] of a multi-device context) ----
+  const TreeOut out{leaf_maps_opt, logits_opt, logit_stride, dec_opt, cand_opt};
   Descent d;
-  if ((rc = descend(ctx, "mlt_predict_trees", lv, W, H, P, pics, (cfg->flags & MLT_TREE_BY_CANDIDATES) != 0, true,
-                    TreeWant{leaf_maps_opt != nullptr, logits_opt != nullptr, dec_opt != nullptr, cand_opt != nullptr}, d)))
-    return rc;
+  if ((rc = descend(ctx, "mlt_predict_trees", lv, W, H, P, pics, by_candidates(cfg), true, out, d))) return rc;
   // ---- level-major -> picture-major, then everything the caller asked for and one synchronisation ----
   const Lay::TreeArena::Ptrs &A = d.A;
   const int total = d.total;
@@ -481,21 +461,10 @@ int mlt_predict_trees(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture *pics
     pa.o_nodes = A.o_nodes; pa.o_logits = A.o_logits; pa.o_dec = A.o_dec; pa.o_cand = A.o_cand;
     pa.segs = TreesSegs{A.seg_start, A.seg_n, A.pack_base}; pa.first_node = A.first_node; pa.n_pictures = P; pa.n_levels = lv.L; pa.total = total;
     for (int l = 0; l < lv.L; ++l) { pa.lvl_start[l] = d.start[l]; pa.n_logits[l] = lv.st[l]->model.n_logits; }
-    Launch prof{ctx};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     const double per_node = 2.0 * sizeof(TreeNodeRec) + 4 + (logits_opt ? 2.0 * kRowLogits * 4 : 0) + (dec_opt ? 2.0 * sizeof(DecisionRec) : 0) + (cand_opt ? 2.0 * sizeof(CandRec) : 0);
-    if ((rc = prof.prof_begin("tree_pack", 0.0, (double)total * per_node, e0, e1))) return rc;
-    HIP_TRY(ctx, mlt_launch_trees_pack(pa, ctx->stream));
-    if ((rc = prof.prof_end(e1))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(nodes, A.o_nodes, (size_t)total * sizeof(TreeNodeRec), hipMemcpyDeviceToHost, ctx->stream));
-    if (logits_opt) {   // whole zero-padded rows
-      if (logit_stride == kRowLogits) HIP_TRY(ctx, hipMemcpyAsync(logits_opt, A.o_logits, (size_t)total * kRowLogits * 4, hipMemcpyDeviceToHost, ctx->stream));
-      else HIP_TRY(ctx, hipMemcpy2DAsync(logits_opt, (size_t)logit_stride * 4, A.o_logits, (size_t)kRowLogits * 4, (size_t)kRowLogits * 4, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (dec_opt) HIP_TRY(ctx, hipMemcpyAsync(dec_opt, A.o_dec, (size_t)total * sizeof(DecisionRec), hipMemcpyDeviceToHost, ctx->stream));
-    if (cand_opt) HIP_TRY(ctx, hipMemcpyAsync(cand_opt, A.o_cand, (size_t)total * sizeof(CandRec), hipMemcpyDeviceToHost, ctx->stream));
+    PROF_HIP_TRY(ctx, "tree_pack", 0.0, (double)total * per_node, mlt_launch_trees_pack(pa, ctx->stream));
   }
-  if (leaf_maps_opt) HIP_TRY(ctx, hipMemcpyAsync(leaf_maps_opt, A.map, (size_t)P * d.map_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = copy_packed(ctx, A, total, (size_t)P, d.map_bytes, nodes, out))) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(first_node, A.first_node, ((size_t)P + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (first_node[P] != total) { ctx->err = "mlt_predict_trees: bad node count from the device"; return MLT_ERR_HIP; }
@@ -514,23 +483,16 @@ int mlt_predict_tree_sweep(mlt_ctx *ctx, const mlt_picture *org, const mlt_pictu
   TreeLevels lv;
   int rc;
   if ((rc = tree_levels(ctx, "mlt_predict_tree_sweep", cfg, lv))) return rc;
-  if ((rc = tree_pair(ctx, "mlt_predict_tree_sweep", org, pred))) return rc;
+  if ((rc = check_at_pair(ctx, "mlt_predict_tree_sweep", org, pred))) return rc;
   const int W = org->width, H = org->height, Q = n_qps;
   const int max_nodes = mlt_tree_max_nodes(W, H, lv.top, lv.mn);
-  const long long cap_all = (long long)Q * max_nodes;
-  if (node_cap < cap_all || cap_all > 0x7fffffff) {
-    char msg[192];
-    std::snprintf(msg, sizeof msg, "mlt_predict_tree_sweep: node_cap %d is below %d x mlt_tree_max_nodes = %d of a %d x %d picture", node_cap, Q, max_nodes, W, H);
-    ctx->err = msg;
-    return MLT_ERR_ARG;
-  }
+  if ((rc = check_node_cap(ctx, "mlt_predict_tree_sweep", node_cap, {Q}, max_nodes, W, H))) return rc;
   // ---- arguments are good: the union descent runs on this context's own device (devices[0] of a multi-device context) ----
   const mlt_tree_picture one{org, pred, cfg->poc, 0};
+  const TreeOut out{leaf_maps_opt, logits_opt, logit_stride, dec_opt, cand_opt};
   SweepDescent d;
-  if ((rc = descend_sweep(ctx, "mlt_predict_tree_sweep", lv, W, H, 1, &one, qps, Q, (cfg->flags & MLT_TREE_BY_CANDIDATES) != 0,
-                          TreeWant{leaf_maps_opt != nullptr, logits_opt != nullptr, dec_opt != nullptr, cand_opt != nullptr}, d)))
-    return rc;
-  return sweep_results(ctx, "mlt_predict_tree_sweep", lv, d, 1, Q, max_nodes, nodes, first_node, union_nodes_opt, leaf_maps_opt, logits_opt, logit_stride, dec_opt, cand_opt);
+  if ((rc = descend_sweep(ctx, "mlt_predict_tree_sweep", lv, W, H, 1, &one, qps, Q, by_candidates(cfg), out, d))) return rc;
+  return sweep_results(ctx, "mlt_predict_tree_sweep", lv, d, 1, Q, max_nodes, nodes, first_node, union_nodes_opt, out);
 }
 
 int mlt_predict_trees_sweep(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture *pics, const mlt_tree_config *cfg, const int32_t *qps, int n_qps, mlt_tree_node *nodes,
@@ -547,47 +509,18 @@ int mlt_predict_trees_sweep(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture
   int rc;
   if ((rc = tree_levels(ctx, "mlt_predict_trees_sweep", cfg, lv))) return rc;
   const int P = n_pictures, Q = n_qps;
-  for (int p = 0; p < P; ++p) {
-    const mlt_picture *o = pics[p].org, *q = pics[p].pred;
-    char msg[192];
-    if (!o || !q || !owns_picture(ctx, o) || !owns_picture(ctx, q)) {
-      std::snprintf(msg, sizeof msg, "mlt_predict_trees_sweep: entry %d: both pictures must be given and belong to this context", p);
-      ctx->err = msg;
-      return MLT_ERR_ARG;
-    }
-    if (o->width != q->width || o->height != q->height || o->width != pics[0].org->width || o->height != pics[0].org->height) {
-      std::snprintf(msg, sizeof msg, "mlt_predict_trees_sweep: entry %d: every picture of a call must have the width and height of entry 0's (%d x %d)", p,
-                    pics[0].org->width, pics[0].org->height);
-      ctx->err = msg;
-      return MLT_ERR_ARG;
-    }
-    for (int k = 0; k < Q; ++k) {   // the QP of entry p under point k
-      const long long qp = (long long)pics[p].qp + (long long)qps[k];
-      if (qp < INT32_MIN || qp > INT32_MAX) {
-        std::snprintf(msg, sizeof msg, "mlt_predict_trees_sweep: entry %d: its qp offset %d + qps[%d] = %d does not fit int32", p, pics[p].qp, k, qps[k]);
-        ctx->err = msg;
-        return MLT_ERR_ARG;
-      }
-    }
-  }
+  if ((rc = check_tree_entries(ctx, "mlt_predict_trees_sweep", P, pics, qps, Q))) return rc;
   const int W = pics[0].org->width, H = pics[0].org->height;
   const int max_nodes = mlt_tree_max_nodes(W, H, lv.top, lv.mn);
-  const long long cap_all = (long long)P * Q * max_nodes;
-  if (node_cap < cap_all || cap_all > 0x7fffffff) {
-    char msg[192];
-    std::snprintf(msg, sizeof msg, "mlt_predict_trees_sweep: node_cap %d is below %d x %d x mlt_tree_max_nodes = %d of a %d x %d picture", node_cap, P, Q, max_nodes, W, H);
-    ctx->err = msg;
-    return MLT_ERR_ARG;
-  }
+  if ((rc = check_node_cap(ctx, "mlt_predict_trees_sweep", node_cap, {P, Q}, max_nodes, W, H))) return rc;
   // ---- arguments are good: the union descent runs on this context's own device (devices[0] of a multi-device context) ----
   // one entry: its offset goes into the points (integers, as the sweep heads would add it) and the descent is mlt_predict_tree_sweep's
   int32_t folded[MLT_SWEEP_MAX_QPS];
   for (int k = 0; k < Q; ++k) folded[k] = P == 1 ? (int32_t)((long long)pics[0].qp + qps[k]) : qps[k];
+  const TreeOut out{leaf_maps_opt, logits_opt, logit_stride, dec_opt, cand_opt};
   SweepDescent d;
-  if ((rc = descend_sweep(ctx, "mlt_predict_trees_sweep", lv, W, H, P, pics, folded, Q, (cfg->flags & MLT_TREE_BY_CANDIDATES) != 0,
-                          TreeWant{leaf_maps_opt != nullptr, logits_opt != nullptr, dec_opt != nullptr, cand_opt != nullptr}, d)))
-    return rc;
-  return sweep_results(ctx, "mlt_predict_trees_sweep", lv, d, P, Q, max_nodes, nodes, first_node, union_nodes_opt, leaf_maps_opt, logits_opt, logit_stride, dec_opt, cand_opt);
+  if ((rc = descend_sweep(ctx, "mlt_predict_trees_sweep", lv, W, H, P, pics, folded, Q, by_candidates(cfg), out, d))) return rc;
+  return sweep_results(ctx, "mlt_predict_trees_sweep", lv, d, P, Q, max_nodes, nodes, first_node, union_nodes_opt, out);
 }
 
 #pragma GCC visibility pop

@@ -22,12 +22,47 @@
 // its rank as D_p; an EMPTY segment (no roots at that level and nothing descended into it) has no node to do so and takes the rank of the first non-empty segment
 // behind it, or the level's total.  With one picture D_0 = 0: the roots sit at next_start, the children behind them.  Everything is written with ordinary vector
 // stores; no atomics are needed (the order is the scan's and every output word has exactly one writer).
+//
+// What the plain and the union descent share is written once, ahead of the kernels: tree_tile_scan (the scan of one tile -- both expand kernels and
+// tree_sweep_rank_kernel), tree_point_cmask (a node's cand_mask), tree_write_node (a new node's record, position and picture; the union's overload adds its masks)
+// and tree_open_next_level (D_p, the next level's rows of the segment table, the border roots and the count, behind the scan of either expand kernel).
 
 #define MLT_TREE_TILE 1024
 #define MLT_TREES_MAX_PICTURES_K 256   // include/mltcnn.h: MLT_TREES_MAX_PICTURES (the per-picture ranks live in LDS)
+// (selected, not indexed: a dynamically indexed argument array would be copied to scratch or LDS)
+#define MLT_TREE_SEL(v, l) ((l) == 0 ? (v)[0] : (l) == 1 ? (v)[1] : (l) == 2 ? (v)[2] : (v)[3])
 
-__device__ __forceinline__ void tree_write_node(const TreeExpandArgs &a, int idx, int pic, int x, int y, int size, int depth, int flags, int parent) {
-  if (idx < 0 || idx >= a.node_cap) return;   // (the host sizes the arena for trees that descend everywhere: never taken)
+// One tile of the ordered scan, called by all MLT_TREE_TILE threads of the workgroup: -> how many threads before this one hold `on`, total <- how many of the tile
+// do.  Ballot + popcount inside a wave, the 16 wave totals through wave_total[MLT_TREE_TILE / 64] (LDS); the second barrier keeps the next tile's totals off this
+// tile's reads.  The caller carries the base from tile to tile.
+__device__ __forceinline__ int tree_tile_scan(bool on, int *wave_total, int &total) {
+  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+  const unsigned long long b = __ballot(on);
+  if (lane == 0) wave_total[wave] = __popcll(b);
+  __syncthreads();
+  int woff = 0;
+  total = 0;
+  for (int w = 0; w < MLT_TREE_TILE / 64; ++w) {
+    const int s = wave_total[w];
+    woff += w < wave ? s : 0;
+    total += s;
+  }
+  __syncthreads();   // (the next tile overwrites wave_total)
+  return woff + __popcll(b & ((1ull << lane) - 1ull));
+}
+
+// cand_mask of one evaluated element: the candidate record's, or the default policy's without asking the heads launch for one -- the argmax alone, every class when
+// a logit of the decision head is NaN (head_candidates)
+__device__ __forceinline__ uint32_t tree_point_cmask(const DecisionRec &d, const CandRec *cand, const float *logits, size_t e, int n_logits, int head_off, int head_classes) {
+  if (cand) return cand[e].mask;
+  const float *l = logits + e * (size_t)n_logits + head_off;
+  bool nan = false;
+  for (int k = 0; k < head_classes; ++k) nan = nan || (l[k] != l[k]);
+  return nan ? (1u << head_classes) - 1u : 1u << d.raw_mode;
+}
+
+__device__ __forceinline__ void tree_write_node(const TreeLevelArgs &a, int idx, int pic, int x, int y, int size, int depth, int flags, int parent) {
+  if (idx < 0 || idx >= a.node_cap) return;   // (the host sizes the arena for trees -- unions -- that descend everywhere: never taken)
   TreeNodeRec r;
   r.x = x; r.y = y; r.size = (int16_t)size; r.depth = (int8_t)depth; r.flags = (uint8_t)flags;
   r.parent = parent; r.first_child = -1; r.split_mode = -1; r.confidence = 0.f; r.cand_mask = 0u;
@@ -36,15 +71,48 @@ __device__ __forceinline__ void tree_write_node(const TreeExpandArgs &a, int idx
   a.xy[2 * (size_t)idx + 1] = y;
   a.pic[idx] = pic;
 }
+// a node of the union descent: + the points it is alive under, descending under none yet
+__device__ __forceinline__ void tree_write_node(const TreeSweepExpandArgs &a, int idx, int pic, int x, int y, int size, int depth, int flags, int parent, uint32_t alive) {
+  if (idx < 0 || idx >= a.node_cap) return;
+  tree_write_node(static_cast<const TreeLevelArgs &>(a), idx, pic, x, y, size, depth, flags, parent);
+  a.alive[idx] = alive;
+  a.desc[idx] = 0u;
+}
+
+// Behind the scan of a level (base: its descending nodes; seg_rank[p]: D_p as the first node of picture p's segment published it): seg_first <- D_p of every
+// picture -- its own first node's rank, or (empty segment) that of the first non-empty segment behind it, [n_pictures] the level's total --, the next level's rows
+// of the segment table, every picture's border roots (host-known, raster order, the same for all pictures) through write_root(k, p, x, y), k counted from the next
+// level's first node, and the next level's count.  Called by the whole workgroup.
+template <class WriteRoot>
+__device__ __forceinline__ void tree_open_next_level(const TreeLevelArgs &a, const int *seg_rank, int *seg_first, int base, int next_start, WriteRoot write_root) {
+  const int tid = (int)threadIdx.x, P = a.n_pictures, nr = a.n_next_roots;
+  const int32_t *cur_n = a.seg_n + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P;
+  __syncthreads();   // seg_rank is complete
+  if (tid <= P) {
+    int q = tid;
+    while (q < P && (a.lvl < 0 || cur_n[q] == 0)) ++q;
+    seg_first[tid] = q < P ? seg_rank[q] : base;
+  }
+  __syncthreads();
+  if (tid < P) {
+    a.seg_start[(size_t)(a.lvl + 1) * P + tid] = next_start + tid * nr + 4 * seg_first[tid];
+    a.seg_n[(size_t)(a.lvl + 1) * P + tid] = nr + 4 * (seg_first[tid + 1] - seg_first[tid]);
+  }
+  for (int i = tid; i < P * nr; i += MLT_TREE_TILE) {
+    const int p = i / nr, r = i - p * nr;
+    write_root(p * nr + 4 * seg_first[p] + r, p, a.next_roots[2 * r], a.next_roots[2 * r + 1]);
+  }
+  if (tid == 0 && a.count) a.count[0] = P * nr + 4 * base;
+}
 
 __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_kernel(const TreeExpandArgs a) {
   __shared__ int wave_total[MLT_TREE_TILE / 64];
   __shared__ int seg_rank[MLT_TREES_MAX_PICTURES_K];       // D_p as published by the first node of a non-empty segment
   __shared__ int seg_first[MLT_TREES_MAX_PICTURES_K + 1];  // D_p of every picture; [n_pictures] = the level's total
   __shared__ int pic_total[MLT_TREES_MAX_PICTURES_K];      // last launch: nodes of picture p over all levels
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, P = a.n_pictures, nr = a.n_next_roots;
+  const int tid = (int)threadIdx.x, P = a.n_pictures, nr = a.n_next_roots;
   const int next_start = a.lvl_start + a.lvl_n, child_size = a.size >> 1;
-  const int32_t *cur_start = a.segs.start + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P, *cur_n = a.segs.n + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P;
+  const int32_t *cur_start = a.seg_start + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P;
   int base = 0;   // descending parents of the tiles before this one (the same value in every thread)
   for (int t0 = 0; t0 < a.lvl_n; t0 += MLT_TREE_TILE) {
     const int i = t0 + tid;
@@ -60,29 +128,12 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_kernel(const TreeEx
       const DecisionRec &d = a.dec[i];
       split = d.split_mode;
       conf = d.confidence;
-      if (a.cand) cmask = a.cand[i].mask;
-      else {
-        // the default policy's record without asking the heads launch for it: the argmax alone, every class when a logit of the decision head is NaN (head_candidates)
-        const float *l = a.logits + (size_t)i * a.n_logits + a.head_off;
-        bool nan = false;
-        for (int k = 0; k < a.head_classes; ++k) nan = nan || (l[k] != l[k]);
-        cmask = nan ? (1u << a.head_classes) - 1u : 1u << d.raw_mode;
-      }
+      cmask = tree_point_cmask(d, a.cand, a.logits, (size_t)i, a.n_logits, a.head_off, a.head_classes);
       desc = a.by_candidates ? (cmask & a.descend_mask) != 0u : (split >= 0 && ((a.descend_mask >> split) & 1u) != 0u);
     }
-    const unsigned long long b = __ballot(desc);
-    const int before = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_total[wave] = __popcll(b);
-    __syncthreads();
-    int woff = 0, total = 0;
-    for (int w = 0; w < MLT_TREE_TILE / 64; ++w) {
-      const int s = wave_total[w];
-      woff += w < wave ? s : 0;
-      total += s;
-    }
-    __syncthreads();   // (the next tile overwrites wave_total)
+    int total;
+    const int rank = base + tree_tile_scan(desc, wave_total, total);
     if (in) {
-      const int rank = base + woff + before;
       if ((unsigned)p < (unsigned)P && node == cur_start[p]) seg_rank[p] = rank;   // the segment's first node: one writer per picture
       int first_child = -1;
       if (desc) {
@@ -98,33 +149,15 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_kernel(const TreeEx
     }
     base += total;
   }
-  __syncthreads();   // seg_rank is complete
-  // D_p of every picture: its own first node's rank, or (empty segment) that of the first non-empty segment behind it
-  if (tid <= P) {
-    int q = tid;
-    while (q < P && (a.lvl < 0 || cur_n[q] == 0)) ++q;
-    seg_first[tid] = q < P ? seg_rank[q] : base;
-  }
-  __syncthreads();
-  const bool last = a.lvl == a.n_levels - 1;
-  if (!last) {
-    int32_t *nx_start = a.segs.start + (size_t)(a.lvl + 1) * P, *nx_n = a.segs.n + (size_t)(a.lvl + 1) * P;
-    if (tid < P) {
-      nx_start[tid] = next_start + tid * nr + 4 * seg_first[tid];
-      nx_n[tid] = nr + 4 * (seg_first[tid + 1] - seg_first[tid]);
-    }
-    // every picture's next segment opens with the border roots (host-known, raster order, the same for all pictures)
-    for (int i = tid; i < P * nr; i += MLT_TREE_TILE) {
-      const int p = i / nr, r = i - p * nr;
-      tree_write_node(a, next_start + p * nr + 4 * seg_first[p] + r, p, a.next_roots[2 * r], a.next_roots[2 * r + 1], child_size, a.lvl + 1, a.root_flags, -1);
-    }
-    if (tid == 0 && a.count) a.count[0] = P * nr + 4 * base;
+  if (a.lvl != a.n_levels - 1) {
+    tree_open_next_level(a, seg_rank, seg_first, base, next_start,
+                         [&](int k, int p, int x, int y) { tree_write_node(a, next_start + k, p, x, y, child_size, a.lvl + 1, a.root_flags, -1); });
     return;
   }
   // the last level: where every (level, picture) segment starts in the picture-major output, and first_node[]
   if (tid < P) {
     int s = 0;
-    for (int l = 0; l < a.n_levels; ++l) s += a.segs.n[(size_t)l * P + tid];
+    for (int l = 0; l < a.n_levels; ++l) s += a.seg_n[(size_t)l * P + tid];
     pic_total[tid] = s;
   }
   __syncthreads();
@@ -134,8 +167,8 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_kernel(const TreeEx
     a.first_node[tid] = first;
     if (tid < P)
       for (int l = 0; l < a.n_levels; ++l) {
-        a.segs.pack_base[(size_t)l * P + tid] = first;
-        first += a.segs.n[(size_t)l * P + tid];
+        a.pack_base[(size_t)l * P + tid] = first;
+        first += a.seg_n[(size_t)l * P + tid];
       }
   }
 }
@@ -169,9 +202,7 @@ __global__ __launch_bounds__(256) void tree_pack_kernel(const TreesPackArgs a) {
     if (r.first_child >= 0 && l + 1 < a.n_levels) r.first_child = a.segs.pack_base[at + P] + (r.first_child - a.segs.start[at + P]) - first;
     a.o_nodes[dst] = r;
     if (a.o_logits) {
-      // (selected, not indexed: a dynamically indexed argument array would be copied to scratch or LDS)
-      const int nl = l == 0 ? a.n_logits[0] : l == 1 ? a.n_logits[1] : l == 2 ? a.n_logits[2] : a.n_logits[3];
-      const int ls = l == 0 ? a.lvl_start[0] : l == 1 ? a.lvl_start[1] : l == 2 ? a.lvl_start[2] : a.lvl_start[3];
+      const int nl = MLT_TREE_SEL(a.n_logits, l), ls = MLT_TREE_SEL(a.lvl_start, l);
       const float *src = a.logits + (size_t)ls * MLT_TREES_ROW + (size_t)(g - ls) * nl;
       float *o = a.o_logits + (size_t)dst * MLT_TREES_ROW;
       for (int k = 0; k < MLT_TREES_ROW; ++k) o[k] = k < nl ? src[k] : 0.f;
@@ -196,32 +227,6 @@ __global__ __launch_bounds__(256) void tree_pack_kernel(const TreesPackArgs a) {
 // Plain vector stores, one writer per output word, no atomics.
 // ---------------------------------------------------------------------------------------------
 
-// (selected, not indexed: a dynamically indexed argument array would be copied to scratch or LDS)
-#define MLT_TREE_SEL(v, l) ((l) == 0 ? (v)[0] : (l) == 1 ? (v)[1] : (l) == 2 ? (v)[2] : (v)[3])
-
-// cand_mask of one evaluated element: the candidate record's, or the default policy's without one -- the argmax alone, every class when a logit of the decision
-// head is NaN (tree_expand_kernel's rule)
-__device__ __forceinline__ uint32_t tree_point_cmask(const DecisionRec &d, const CandRec *cand, const float *logits, size_t e, int n_logits, int head_off, int head_classes) {
-  if (cand) return cand[e].mask;
-  const float *l = logits + e * (size_t)n_logits + head_off;
-  bool nan = false;
-  for (int k = 0; k < head_classes; ++k) nan = nan || (l[k] != l[k]);
-  return nan ? (1u << head_classes) - 1u : 1u << d.raw_mode;
-}
-
-__device__ __forceinline__ void tree_sweep_write_node(const TreeSweepExpandArgs &a, int idx, int pic, int x, int y, int size, int depth, int flags, int parent, uint32_t alive) {
-  if (idx < 0 || idx >= a.node_cap) return;   // (the host sizes every level for a union that descends everywhere: never taken)
-  TreeNodeRec r;
-  r.x = x; r.y = y; r.size = (int16_t)size; r.depth = (int8_t)depth; r.flags = (uint8_t)flags;
-  r.parent = parent; r.first_child = -1; r.split_mode = -1; r.confidence = 0.f; r.cand_mask = 0u;
-  a.nodes[idx] = r;
-  a.xy[2 * (size_t)idx] = x;
-  a.xy[2 * (size_t)idx + 1] = y;
-  a.pic[idx] = pic;
-  a.alive[idx] = alive;
-  a.desc[idx] = 0u;
-}
-
 // The next level of the union of n_pictures entries is tree_expand_kernel's: with nr roots per entry, R_i the exclusive rank of descending node i over the WHOLE
 // level and D_p the rank at the start of entry p's segment, entry p's segment starts at next_start + p nr + 4 D_p and node i's children at
 // next_start + (p_i + 1) nr + 4 R_i; an empty segment takes the rank of the first non-empty segment behind it, or the level's total.  One entry: D_0 = 0.
@@ -229,9 +234,9 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_sweep_kernel(const 
   __shared__ int wave_total[MLT_TREE_TILE / 64];
   __shared__ int seg_rank[MLT_TREES_MAX_PICTURES_K];       // D_p as published by the first node of a non-empty segment
   __shared__ int seg_first[MLT_TREES_MAX_PICTURES_K + 1];  // D_p of every entry; [n_pictures] = the level's total
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, Q = a.n_qps, P = a.n_pictures, nr = a.n_next_roots, child_size = a.size >> 1;
+  const int tid = (int)threadIdx.x, Q = a.n_qps, P = a.n_pictures, nr = a.n_next_roots, child_size = a.size >> 1;
   const uint32_t all = Q >= 32 ? 0xFFFFFFFFu : (1u << Q) - 1u;
-  const int32_t *cur_start = a.seg_start + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P, *cur_n = a.seg_n + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P;
+  const int32_t *cur_start = a.seg_start + (size_t)(a.lvl < 0 ? 0 : a.lvl) * P;
   int base = 0;   // descending nodes of the tiles before this one (the same value in every thread)
   for (int t0 = 0; t0 < a.lvl_n; t0 += MLT_TREE_TILE) {
     const int i = t0 + tid;
@@ -254,19 +259,9 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_sweep_kernel(const 
       }
     }
     const bool desc = dm != 0u;
-    const unsigned long long b = __ballot(desc);
-    const int before = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_total[wave] = __popcll(b);
-    __syncthreads();
-    int woff = 0, total = 0;
-    for (int w = 0; w < MLT_TREE_TILE / 64; ++w) {
-      const int s = wave_total[w];
-      woff += w < wave ? s : 0;
-      total += s;
-    }
-    __syncthreads();   // (the next tile overwrites wave_total)
+    int total;
+    const int rank = base + tree_tile_scan(desc, wave_total, total);
     if (in) {
-      const int rank = base + woff + before;
       const bool p_ok = (unsigned)p < (unsigned)P;
       if (p_ok && node == cur_start[p]) seg_rank[p] = rank;   // the segment's first node: one writer per entry
       int first_child = -1;
@@ -275,7 +270,7 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_sweep_kernel(const 
         if (k + 3 < a.next_cap && a.next_start + k + 3 < a.node_cap) {
           const int fc = first_child = a.next_start + k;
           const int x = a.xy[2 * (size_t)node], y = a.xy[2 * (size_t)node + 1];
-          for (int j = 0; j < 4; ++j) tree_sweep_write_node(a, fc + j, p, x + (j & 1) * child_size, y + (j >> 1) * child_size, child_size, a.lvl + 1, 0, node, dm);
+          for (int j = 0; j < 4; ++j) tree_write_node(a, fc + j, p, x + (j & 1) * child_size, y + (j >> 1) * child_size, child_size, a.lvl + 1, 0, node, dm);
         }
       }
       a.nodes[node].first_child = first_child;
@@ -284,23 +279,10 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void tree_expand_sweep_kernel(const 
     base += total;
   }
   if (!a.next_roots && !a.count) return;   // the last level
-  __syncthreads();   // seg_rank is complete
-  if (tid <= P) {
-    int q = tid;
-    while (q < P && (a.lvl < 0 || cur_n[q] == 0)) ++q;
-    seg_first[tid] = q < P ? seg_rank[q] : base;
-  }
-  __syncthreads();
-  if (tid < P) {   // the next level's rows of the segment table
-    a.seg_start[(size_t)(a.lvl + 1) * P + tid] = a.next_start + tid * nr + 4 * seg_first[tid];
-    a.seg_n[(size_t)(a.lvl + 1) * P + tid] = nr + 4 * (seg_first[tid + 1] - seg_first[tid]);
-  }
-  // every entry's next segment opens with the border roots (host-known, raster order): part of every tree
-  for (int i = tid; i < P * nr; i += MLT_TREE_TILE) {
-    const int p = i / nr, r = i - p * nr, k = p * nr + 4 * seg_first[p] + r;
-    if (k < a.next_cap) tree_sweep_write_node(a, a.next_start + k, p, a.next_roots[2 * r], a.next_roots[2 * r + 1], child_size, a.lvl + 1, a.root_flags, -1, all);
-  }
-  if (tid == 0 && a.count) a.count[0] = P * nr + 4 * base;
+  // the border roots are part of every tree of their entry
+  tree_open_next_level(a, seg_rank, seg_first, base, a.next_start, [&](int k, int p, int x, int y) {
+    if (k < a.next_cap) tree_write_node(a, a.next_start + k, p, x, y, child_size, a.lvl + 1, a.root_flags, -1, all);
+  });
 }
 
 // One work item per 16 x 16 block of every union node of the level; under a point the leaves are disjoint, and every (entry, point) has a map of its own.
@@ -325,7 +307,7 @@ __global__ __launch_bounds__(256) void tree_sweep_raster_kernel(const TreeSweepR
 // base carried on).  Every union node belongs to one entry, so idx[q][node] has one writer.
 __global__ __launch_bounds__(MLT_TREE_TILE) void tree_sweep_rank_kernel(const TreeSweepPackArgs a) {
   __shared__ int wave_total[MLT_TREE_TILE / 64];
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, P = a.n_pictures;
+  const int tid = (int)threadIdx.x, P = a.n_pictures;
   if ((int)blockIdx.x >= P * a.n_qps) return;
   const int p = (int)blockIdx.x / a.n_qps, q = (int)blockIdx.x - p * a.n_qps;
   int32_t *idx = a.idx + (size_t)q * (size_t)a.node_cap;
@@ -336,18 +318,9 @@ __global__ __launch_bounds__(MLT_TREE_TILE) void tree_sweep_rank_kernel(const Tr
       const int i = t0 + tid, node = start + i;
       const bool in = i < n && node >= 0 && node < a.node_cap;
       const bool on = in && ((a.alive[node] >> q) & 1u) != 0u;
-      const unsigned long long b = __ballot(on);
-      const int before = __popcll(b & ((1ull << lane) - 1ull));
-      if (lane == 0) wave_total[wave] = __popcll(b);
-      __syncthreads();
-      int woff = 0, total = 0;
-      for (int w = 0; w < MLT_TREE_TILE / 64; ++w) {
-        const int s = wave_total[w];
-        woff += w < wave ? s : 0;
-        total += s;
-      }
-      __syncthreads();
-      if (in) idx[node] = on ? base + woff + before : -1;
+      int total;
+      const int rank = base + tree_tile_scan(on, wave_total, total);
+      if (in) idx[node] = on ? rank : -1;
       base += total;
     }
   }

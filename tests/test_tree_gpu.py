@@ -17,55 +17,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tree_host import SIZES, host_tree, reruns as _reruns, same as _same   # the host descent (build_tree over predict_at)
+from tree_gpu_common import (LOGIT_TOL, MLT_ERR_ARG, MLT_ERR_SIZE_DISABLED, SIZES, TREE_ALL, UNDECIDABLE, H, W, blobs as _blobs, contexts, cut, gpu,   # noqa: F401  (fixtures)
+                             natural_picture, open_context as _open, reruns as _reruns, same as _same)
+from tree_host import host_tree   # the host descent (build_tree over predict_at)
 
 pytestmark = pytest.mark.gpu
-LOGIT_TOL, UNDECIDABLE, CONF_TOL = 1e-3, 4e-5, 5e-4
-W, H = 424, 280
-MLT_ERR_ARG, MLT_ERR_SIZE_DISABLED = 1, 4
-TREE_ALL = ("leaf_map", "logits", "decisions", "candidates")
+CONF_TOL = 5e-4
 #        pic seed, weight seed
 CASES = {"A": (8, 13), "B": (7, 12), "C": (7, 13)}
-
-
-@pytest.fixture(scope="module")
-def gpu(pkg):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    pkg.build.build_lib()
-    return pkg
-
-
-def _blobs(pkg, seed, sizes=SIZES):
-    return {s: pkg.weights.synthetic_blob(pkg.synth.ARCH_CTU if s == 128 else pkg.synth.ARCH_CU, seed) for s in sizes}
-
-
-def _open(pkg, seed, sizes=SIZES, **kw):
-    return pkg.MltCnn(device=0, sizes=sizes, blobs=_blobs(pkg, seed, sizes), head_index={s: 0 for s in sizes}, **kw)
-
-
-@pytest.fixture(scope="module")
-def contexts(gpu):
-    """One context per weight seed, shared by the tests of the module (a test that sets a gate or a policy puts the default back)."""
-    made = {}
-
-    def get(seed):
-        if seed not in made:
-            made[seed] = _open(gpu, seed)
-        return made[seed]
-    yield get
-    for m in made.values():
-        m.close()
-
-
-def natural_picture(pkg, pic_seed):
-    org, pred = pkg.synth.natural_patches(128, 12, pic_seed)
-    tile = lambda p: np.ascontiguousarray(p.reshape(3, 4, 128, 128).transpose(0, 2, 1, 3).reshape(384, 512)[:H, :W])
-    return tile(org), tile(pred)
-
-
-def cut(pic, xy, S):
-    return np.stack([pic[y:y + S, x:x + S] for x, y in xy])
 
 
 def device_tree(m, p_org, p_pred, want=TREE_ALL, sizes=SIZES, **kw):

@@ -11,86 +11,15 @@ import numpy as np
 import pytest
 
 from tree_host import host_tree   # the descent driven from the host (build_tree over predict_at)
+from tree_gpu_common import (LOGIT_TOL, MLT_ERR_ARG, MLT_ERR_SIZE_DISABLED, SIZES, TREE_ALL, UNDECIDABLE, H, W, contexts, gpu, naturals, oracle_level,   # noqa: F401  (fixtures)
+                             open_context as _open, reruns as _reruns, same as _same)
 
 pytestmark = pytest.mark.gpu
-SIZES = (128, 64, 32, 16)
-W, H = 424, 280
-LOGIT_TOL = 1e-3     # the logit contract (tests/test_hip_parity.py)
-UNDECIDABLE = 4e-5   # tests/test_tree_gpu.py: a reference top-2 margin at or below it is a tie of the reference's own arithmetic
-MLT_ERR_ARG, MLT_ERR_SIZE_DISABLED = 1, 4
-TREE_ALL = ("leaf_map", "logits", "decisions", "candidates")
 POC_QP = list(itertools.product((0, 1, 2), (0, 1)))
 # 24 distinct picture seeds for the 424 x 280 cases; picture i carries POC_QP[i % 6].  The seeded 128 model's head 0 says QT for a natural patch unless the patch is
 # dark (mean below ~285 ten-bit steps): seeds 34791 and 41262 are the first two whose six whole 128 patches are all dark -- no QT among their 128 nodes, so their
 # 64 segment is EMPTY (424 x 280 has no 64 roots); every other seed has 2 .. 6 QT nodes.  Found by the CPU oracle; the test asserts it from the oracle again.
 PIC_SEEDS = [34791, 41262] + list(range(1, 23))
-
-
-@pytest.fixture(scope="module")
-def gpu(pkg):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    pkg.build.build_lib()
-    return pkg
-
-
-def _blobs(pkg, seed, sizes=SIZES):
-    return {s: pkg.weights.synthetic_blob(pkg.synth.ARCH_CTU if s == 128 else pkg.synth.ARCH_CU, seed) for s in sizes}
-
-
-def _open(pkg, seed, sizes=SIZES, **kw):
-    return pkg.MltCnn(device=0, sizes=sizes, blobs=_blobs(pkg, seed, sizes), head_index={s: 0 for s in sizes}, **kw)
-
-
-@pytest.fixture(scope="module")
-def contexts(gpu):
-    """One context per (weight seed, sizes), shared by the tests of the module (a test that sets a gate or a policy puts the default back)."""
-    made = {}
-
-    def get(seed, sizes=SIZES):
-        if (seed, sizes) not in made:
-            made[(seed, sizes)] = _open(gpu, seed, sizes)
-        return made[(seed, sizes)]
-    yield get
-    for m in made.values():
-        m.close()
-
-
-def natural_picture(pkg, pic_seed):
-    """tests/test_tree_gpu.py's: twelve natural patches of 128 x 128 tiled 4 x 3 and cropped to 424 x 280."""
-    org, pred = pkg.synth.natural_patches(128, 12, pic_seed)
-    tile = lambda p: np.ascontiguousarray(p.reshape(3, 4, 128, 128).transpose(0, 2, 1, 3).reshape(384, 512)[:H, :W])
-    return tile(org), tile(pred)
-
-
-@pytest.fixture(scope="module")
-def naturals(gpu):
-    """The 24 natural pictures, made once: [(org, pred)] in PIC_SEEDS' order."""
-    return [natural_picture(gpu, s) for s in PIC_SEEDS]
-
-
-def cut(pic, xy, S):
-    return np.stack([pic[y:y + S, x:x + S] for x, y in xy])
-
-
-def _same(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def _reruns(m, sizes):
-    return sum(m.arithmetic(s)["guard_reruns"] for s in sizes)
-
-
-def oracle_level(pkg, weight_seed, size, org, pred, xy, poc, qp):
-    """The CPU oracle on the CUs at xy of one picture -> (split, top-2 margin of the decision head)."""
-    import oracle
-    net = oracle_level.nets.setdefault((weight_seed, size), oracle.Oracle(_blobs(pkg, weight_seed, (size,))[size]))
-    n = len(xy)
-    logits, split = net.forward(cut(org, xy, size), cut(pred, xy, size), np.full(n, poc, np.int32), np.full(n, qp, np.int32), head_index=0)
-    return split, pkg.decisions.from_logits(size, logits, head_index=0)["margin"]
-
-
-oracle_level.nets = {}
 
 
 def check_batched_is_singles(m, pairs, poc, qp, what, want=TREE_ALL, **kw):
@@ -137,7 +66,7 @@ def test_mixed_decisions_with_the_streaming_threshold_crossed_at_128(gpu, contex
     roots = pkg.capi.tree_roots(W, H, 128, 128)
     assert len(roots) == 6 and len(pkg.capi.tree_roots(W, H, 128, 64)) == 0
     qt, clear = [], []
-    for i, (org, pred) in enumerate(naturals):
+    for i, (org, pred) in enumerate(naturals(s) for s in PIC_SEEDS):
         split, margin = oracle_level(pkg, 13, 128, org, pred, roots, int(poc[i]), int(qp[i]))
         assert float(margin.min()) > UNDECIDABLE, (i, PIC_SEEDS[i], float(margin.min()))
         qt.append(int((split == 1).sum()))
@@ -148,7 +77,7 @@ def test_mixed_decisions_with_the_streaming_threshold_crossed_at_128(gpu, contex
     assert any(qt[i] == 0 for i in zero) and any(qt[i] > 0 for i in zero), [qt[i] for i in zero]
     assert any(q == 0 and c for q, c in zip(qt, clear)), "no picture without QT at 128 whose margins clear the logit contract"
     m = contexts(13)
-    pairs = upload_all(m, naturals)
+    pairs = upload_all(m, [naturals(s) for s in PIC_SEEDS])
     try:
         got = check_batched_is_singles(m, pairs, poc, qp, "mixed")
         # the device agrees with the oracle about which pictures descend at 128 wherever the margins clear the logit contract, so the empty 64 segments were
@@ -170,7 +99,7 @@ def test_the_streaming_threshold_on_the_single_pass_tier(gpu, contexts, naturals
     assert a["exact"] == 0 and a["w2_units"] == 0 and a["x_units"] == 0 and a["w2_stages"] == 0 and a["x_stages"] == 0, a   # the single pass
     poc = np.array([POC_QP[i % 6][0] for i in range(24)], np.int32)
     qp = np.array([POC_QP[i % 6][1] for i in range(24)], np.int32)
-    pairs = upload_all(m, naturals)
+    pairs = upload_all(m, [naturals(s) for s in PIC_SEEDS])
     try:
         check_batched_is_singles(m, pairs, poc, qp, "single pass", top=128, min_size=128)
         m.profile_enable(True)
@@ -250,7 +179,7 @@ def test_content_that_the_guards_take(gpu, contexts, naturals):
     const = (np.full((H, W), 512, np.int16), np.full((H, W), 508, np.int16))
     d_org = (600 + rng.integers(-1, 2, size=(H, W))).astype(np.int16)
     dither = (d_org, (d_org + rng.integers(-1, 2, size=(H, W))).astype(np.int16))
-    pictures = [naturals[2], const, naturals[0], naturals[9], dither, naturals[5]]
+    pictures = [naturals(PIC_SEEDS[2]), const, naturals(PIC_SEEDS[0]), naturals(PIC_SEEDS[9]), dither, naturals(PIC_SEEDS[5])]
     poc, qp = np.zeros(6, np.int32), np.zeros(6, np.int32)
     m = contexts(13)
     pairs = upload_all(m, pictures)
@@ -295,7 +224,7 @@ def test_sources_of_different_alignment_in_one_call(gpu, contexts, naturals):
     """Entry 1: wrapped planes, odd stride, base 2 bytes off a 16-byte boundary (element path).  Entry 3: wrapped planes with both ends on 16 bytes (vector
     paths).  The others are library-owned.  Entries 0 and 4 share one org picture against different preds."""
     m = contexts(13)
-    (o0, p0), (o1, p1), (o2, p2), (o3, p3), (_, p4) = naturals[3:8]
+    (o0, p0), (o1, p1), (o2, p2), (o3, p3), (_, p4) = (naturals(s) for s in PIC_SEEDS[3:8])
     # both ends on 16 bytes: (H - 1) pitch + W = 0 mod 8 elements; H - 1 is odd and W = 0 mod 8, so the pitch is a multiple of 8 (no odd stride can do it here)
     pitch = W + 8
     assert ((H - 1) * pitch + W) % 8 == 0
@@ -316,7 +245,7 @@ def test_sources_of_different_alignment_in_one_call(gpu, contexts, naturals):
 
 def test_one_picture_is_predict_tree(gpu, contexts, naturals):
     m = contexts(13)
-    pairs = upload_all(m, naturals[4:5])
+    pairs = upload_all(m, [naturals(s) for s in PIC_SEEDS[4:5]])
     try:
         full = check_batched_is_singles(m, pairs, np.array([1], np.int32), np.array([0], np.int32), "P = 1")
         lean = check_batched_is_singles(m, pairs, np.array([1], np.int32), np.array([0], np.int32), "P = 1, lean", want=("leaf_map",))
@@ -330,10 +259,10 @@ def test_bad_arguments_launch_nothing(gpu, contexts, naturals):
     pkg = gpu
     m = contexts(13)
     other = _open(pkg, 13, sizes=(64, 16))   # 32 is missing between 64 and 16, and 128 above
-    pairs = upload_all(m, naturals[6:9])
-    smaller = m.picture(W, H - 16).upload(naturals[6][1][:H - 16])
-    smaller_o = m.picture(W, H - 16).upload(naturals[6][0][:H - 16])
-    foreign = upload_all(other, naturals[6:9])
+    pairs = upload_all(m, [naturals(s) for s in PIC_SEEDS[6:9]])
+    smaller = m.picture(W, H - 16).upload(naturals(PIC_SEEDS[6])[1][:H - 16])
+    smaller_o = m.picture(W, H - 16).upload(naturals(PIC_SEEDS[6])[0][:H - 16])
+    foreign = upload_all(other, [naturals(s) for s in PIC_SEEDS[6:9]])
     per = pkg.capi.tree_max_nodes(W, H)
     assert per == 576
     P = 3

@@ -10,74 +10,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tree_gpu_common import (CHUNK, LOGIT_TOL, MLT_ERR_ARG, MLT_ERR_SIZE_DISABLED, SIZES, TREE_ALL, H, W, Pair, blobs as _blobs, contexts, cut, gpu, naturals,   # noqa: F401  (fixtures)
+                             open_context as _open, reruns as _reruns, same as _same)
+
 pytestmark = pytest.mark.gpu
-SIZES = (128, 64, 32, 16)
-W, H = 424, 280      # six 128 roots, no 64 roots, 8 roots at 32, 26 at 16; 576 nodes at most
-LOGIT_TOL = 1e-3     # the logit contract (tests/test_hip_parity.py)
-MLT_ERR_ARG, MLT_ERR_SIZE_DISABLED = 1, 4
-TREE_ALL = ("leaf_map", "logits", "decisions", "candidates")
-CHUNK = 4096         # the context's pass size
 INT32_MAX, INT32_MIN = 2 ** 31 - 1, -2 ** 31
-
-
-@pytest.fixture(scope="module")
-def gpu(pkg):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    pkg.build.build_lib()
-    return pkg
-
-
-def _blobs(pkg, seed, sizes=SIZES):
-    return {s: pkg.weights.synthetic_blob(pkg.synth.ARCH_CTU if s == 128 else pkg.synth.ARCH_CU, seed) for s in sizes}
-
-
-def _open(pkg, seed, sizes=SIZES, **kw):
-    return pkg.MltCnn(device=0, sizes=sizes, blobs=_blobs(pkg, seed, sizes), head_index={s: 0 for s in sizes}, **kw)
-
-
-@pytest.fixture(scope="module")
-def contexts(gpu):
-    """One context per (weight seed, sizes, flags), shared by the tests of the module (a test that sets a gate or a policy puts the default back)."""
-    made = {}
-
-    def get(seed, sizes=SIZES, flags=0):
-        if (seed, sizes, flags) not in made:
-            made[(seed, sizes, flags)] = _open(gpu, seed, sizes, flags=flags)
-        return made[(seed, sizes, flags)]
-    yield get
-    for m in made.values():
-        m.close()
-
-
-def natural_picture(pkg, pic_seed):
-    """tests/test_tree_sweep_gpu.py's: twelve natural patches of 128 x 128 tiled 4 x 3 and cropped to 424 x 280."""
-    org, pred = pkg.synth.natural_patches(128, 12, pic_seed)
-    tile = lambda p: np.ascontiguousarray(p.reshape(3, 4, 128, 128).transpose(0, 2, 1, 3).reshape(384, 512)[:H, :W])
-    return tile(org), tile(pred)
-
-
-@pytest.fixture(scope="module")
-def naturals(gpu):
-    made = {}
-
-    def get(seed):
-        if seed not in made:
-            made[seed] = natural_picture(gpu, seed)
-        return made[seed]
-    return get
-
-
-def cut(pic, xy, S):
-    return np.stack([pic[y:y + S, x:x + S] for x, y in xy])
-
-
-def _same(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def _reruns(m, sizes):
-    return sum(m.arithmetic(s)["guard_reruns"] for s in sizes)
 
 
 def oracle_roots(pkg, weight_seed, org, pred, poc, qp):
@@ -94,20 +31,6 @@ def oracle_roots(pkg, weight_seed, org, pred, poc, qp):
 
 oracle_roots.nets, oracle_roots.done = {}, {}
 CLEAR = 4 * LOGIT_TOL   # two logits within LOGIT_TOL of the reference cannot swap over such a margin
-
-
-class Pair:
-    """An uploaded picture pair, closed on exit."""
-    def __init__(self, m, org, pred):
-        h, w = org.shape
-        self.o, self.p = m.picture(w, h).upload(org), m.picture(w, h).upload(pred)
-
-    def __enter__(self):
-        return self.o, self.p
-
-    def __exit__(self, *exc):
-        self.o.close()
-        self.p.close()
 
 
 def check(m, entries, qps, what, want=TREE_ALL, singles=True, **kw):

@@ -2,16 +2,9 @@
 (tests/test_tree_gpu.py) and slices of mlt_predict_trees (tests/test_trees_gpu.py) are compared with byte for byte.  Needs the MI355X through its callers."""
 import numpy as np
 
-SIZES = (128, 64, 32, 16)
+from tree_gpu_common import SIZES, reruns
+
 ALL = ("split", "logits", "decisions", "candidates")
-
-
-def same(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def reruns(m, sizes=SIZES):
-    return sum(m.arithmetic(s)["guard_reruns"] for s in sizes)
 
 
 def host_tree(pkg, m, p_org, p_pred, width, height, top=128, min_size=16, descend=None, by_candidates=False, poc=0, qp=0):
