@@ -34,7 +34,8 @@ EXPORTS = ["mlt_abi_version", "mlt_build_signature", "mlt_init", "mlt_num_device
            "mlt_predict_batch_device_candidates", "mlt_wait_candidates",
            "mlt_picture_create", "mlt_picture_upload", "mlt_picture_wrap_device", "mlt_picture_destroy", "mlt_predict_at", "mlt_grid_positions",
            "mlt_tree_max_nodes", "mlt_tree_roots", "mlt_predict_tree", "mlt_predict_trees",
-           "mlt_predict_batch_device_sweep", "mlt_predict_at_sweep", "mlt_predict_tree_sweep", "mlt_predict_trees_sweep"]
+           "mlt_predict_batch_device_sweep", "mlt_predict_at_sweep", "mlt_predict_tree_sweep", "mlt_predict_trees_sweep",
+           "mlt_debug_conv_table"]
 SWEEP_MAX_QPS = 32  # MLT_SWEEP_MAX_QPS
 TREES_MAX_PICTURES = 256  # MLT_TREES_MAX_PICTURES
 TREE_BY_CANDIDATES = 0x1  # mlt_tree_config.flags: descend on cand_mask & descend_mask instead of on split_mode

@@ -177,10 +177,10 @@ int run_conv(mlt_ctx *ctx, const mlt::PackedConv &pc, int n, int hin, const Conv
   // 160 KiB (round 4: the 128 -> 256 stride-2 layer on 8 x 8 maps needs 96 KiB for TWO samples per tile; with one, half of the tile's waves idled)
   size_t patch_budget = 64 * 1024;
   if (nsplit == 2 || nsplit == 6) {
-    const int tt = pc.taps + (pc.has_sc ? 1 : 0), nbuf = tt / pc.gt > 1 ? 2 : 1;
-    const size_t ring = (size_t)nbuf * 2 * pc.gt * (pc.kc / 16) * (pc.ct / 32) * 1024;
+    // (of the layer's throughput tiling, whose ring is the largest: the latency variants cut the same tiles, so that both compute a CU in the same tile)
+    const int ring = mlt_conv_ring_bytes(pc.cin, pc.cout, pc.stride, nsplit, pc.taps == 1 ? MLT_CONV_CENTRE : MLT_CONV_DEFAULT);
     const bool big = tuning().exact_patch_big;
-    if (big && ring + 64 * 1024 < 160 * 1024) patch_budget = 160 * 1024 - ring;
+    if (big && ring >= 0 && ring + 64 * 1024 < 160 * 1024) patch_budget = 160 * 1024 - (size_t)ring;   // (ring < 0: no kernel for the key -- the launch below reports it)
   }
   while (spw > 1 && (((size_t)spw * ph * rp * PS + 1023) / 1024 * 1024) * act_planes > patch_budget) spw /= 2;
   a.tw_l = ilog2(tw); a.th_l = ilog2(th); a.spw_l = ilog2(spw);

@@ -455,6 +455,7 @@ enum { MLT_CONV_DEFAULT = 0, MLT_CONV_DMA = 1, MLT_CONV_LATENCY = 2, MLT_CONV_CE
 bool mlt_conv_has_centre_variant(int cin, int cout);  // 1x1 (centre-tap) instantiation for stride-1 layers on 1x1 maps
 hipError_t mlt_launch_conv(int cin, int cout, int stride, int nsplit, int variant, const ConvArgs &a, int grid_x, int extra_lds, hipStream_t st);  // nsplit: 1 fast, 2 exact, 3 weights hi+lo only (exact tiling), 4 weights hi+lo on the FAST tiling (MLT_MODEL_W2)
 bool mlt_conv_cfg(int cin, int cout, int stride, int exact, ConvCfg *out);
+int mlt_conv_ring_bytes(int cin, int cout, int stride, int nsplit, int variant);  // LDS bytes of the weight ring of the kernel mlt_launch_conv selects for the key (-1: none)
 hipError_t mlt_launch_stem5(const Stem5Args &a, int nsplit, int grid_x, int lds, hipStream_t st);  // nsplit as mlt_launch_conv
 hipError_t mlt_launch_block32(const Block32Args &a, bool w2, int grid_x, hipStream_t st);     // w2: hi+lo weights (8 x 32 tiles)
 hipError_t mlt_launch_stem_block(const StemBlockArgs &a, bool w2, int grid_x, hipStream_t st);

@@ -18,6 +18,8 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <cstdio>
+#include <initializer_list>
 #include <utility>
 
 #include "mlt_kernels.h"
@@ -296,379 +298,294 @@ struct DeviceOnce {
   }
   void done(int dev) { mask[(dev >> 6) & 3].fetch_or(1ull << (dev & 63), std::memory_order_release); }
 };
-template <class K> static hipError_t ensure_big_lds(K kern, DeviceOnce &once) {
+constexpr int kBigLds = 160 * 1024;  // all of a CU's LDS
+// THE launch path of every kernel that needs more than the default 64 KiB of LDS: raise the kernel's limit once per device, launch, report.
+template <class K, class ARGS> static hipError_t launch_big_lds(K kern, DeviceOnce &once, dim3 grid, dim3 block, int lds, hipStream_t st, const ARGS &a) {
   int dev = 0;
-  if (!once.need(&dev)) return hipSuccess;
-  hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e == hipSuccess) once.done(dev);
-  return e;
-}
-template <int CIN, int COUT, int STRIDE, int TAPS, bool SC, int KC, int NSPLIT, int WCB, int WPB, int WAVES_C, int WAVES_P, int GT, int RB, int UN, int MINW, bool DMA, int CBP = 0, bool KMAJ = false>
-static hipError_t launch_conv_t(const ConvArgs &a, int grid_x, int extra_lds, hipStream_t st) {
-  auto kern = conv_mfma_kernel<CIN, COUT, STRIDE, TAPS, SC, KC, NSPLIT, WCB, WPB, WAVES_C, WAVES_P, GT, RB, UN, MINW, DMA, CBP, KMAJ>;
-  constexpr int CBT = WCB * WAVES_C;
-  constexpr int TT = TAPS + (SC ? 1 : 0);
-  constexpr int NBUF = (TT / GT) > 1 ? RB : 1;
-  const int patch_lds = (DMA ? 2 : ((NSPLIT == 2 || NSPLIT == 6) ? 2 : 1)) * a.patch_bytes;
-  // (NSPLIT == 5: + the FP8 lo plane of every ring step and the e4m3 copy of the patch, 80 bytes per pixel of the fp16 patch's KC * 2 + 16)
-  const int patch8 = NSPLIT == 5 ? ((a.patch_bytes / (KC * 2 + 16) + 1) * (KC + 16) + 1023) / 1024 * 1024 : 0;
-  const int lds = patch_lds + NBUF * ((NSPLIT == 2 || NSPLIT == 3 || NSPLIT == 6 ? 2 : 1) * GT * (KC / 16) * CBT * 1024 + (NSPLIT == 5 ? GT * CBT * 2048 : 0)) + patch8 + extra_lds;
-  static DeviceOnce once;
-  if (hipError_t e = ensure_big_lds(kern, once); e != hipSuccess) return e;
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  dim3 grid(grid_x, COUT / (32 * CBT));
-  hipLaunchKernelGGL(kern, grid, dim3(64 * WAVES_C * WAVES_P), lds, st, a);
-  return hipGetLastError();
-}
-
-template <int CIN, int COUT, int STRIDE, bool SC, int KC, int WCB, int WPB, int WAVES_C, int WAVES_P, int GT, int RB, int UNP, int MINW, int NWL, int FD>
-static hipError_t launch_ring_dma_t(const ConvArgs &a, int grid_x, hipStream_t st) {
-  auto kern = conv_ring_dma_kernel<CIN, COUT, STRIDE, SC, KC, WCB, WPB, WAVES_C, WAVES_P, GT, RB, UNP, MINW, NWL, FD>;
-  constexpr int CBT = WCB * WAVES_C, NW = WAVES_C * WAVES_P;
-  constexpr int NWP = NWL ? NWL - NWL / 2 : NW - NW / 2;
-  const int lds = 2 * a.patch_bytes + RB * GT * (KC / 16) * CBT * 1024 + (NWL ? 32 * CBT * 4 * (SC ? 2 : 1) : 0);
-  static DeviceOnce once;
-  if (hipError_t e = ensure_big_lds(kern, once); e != hipSuccess) return e;
-  if (lds > 160 * 1024 || (a.patch_bytes >> 10) > UNP * NWP) return hipErrorInvalidValue;
-  dim3 grid(grid_x, COUT / (32 * CBT));
-  hipLaunchKernelGGL(kern, grid, dim3(64 * (NW + NWL)), lds, st, a);
-  return hipGetLastError();
-}
-
-// Per layer shape: cin chunk (KC), wave tiling and taps per weight step.  mlt_conv_cfg() is the single
-// table both the launcher and the host (packing, patch sizing) read.
-// build-time tuning knobs (scripts/sweep_cfg.py): taps per weight step / ring depth of selected kernels
-#ifndef CFG_3264_GT
-#define CFG_3264_GT 10
-#endif
-#ifndef CFG_3264_RB
-#define CFG_3264_RB 1
-#endif
-#ifndef CFG_S1_RB
-#define CFG_S1_RB 2
-#endif
-#ifndef CFG_64_WPB   // 64@32 stride-1: pixel blocks per wave / waves along pixels
-#define CFG_64_WPB 1
-#endif
-#ifndef CFG_64_WP
-#define CFG_64_WP 8
-#endif
-#ifndef CFG_64_WCB
-#define CFG_64_WCB 2
-#endif
-#ifndef CFG_64_WC
-#define CFG_64_WC 1
-#endif
-#ifndef CFG_S2BIG_WCB
-#define CFG_S2BIG_WCB 2
-#endif
-#ifndef CFG_S2BIG_WC
-#define CFG_S2BIG_WC 2
-#endif
-#ifndef CFG_BIG_WPB  // 128@16, 256@8 stride-1
-#define CFG_BIG_WPB 1
-#endif
-#ifndef CFG_BIG_WP   // 8: one 16-wave workgroup per CU on 256-pixel tiles (with 3 taps per weight step: 128@16 0.405 -> 0.389 ms,
-#define CFG_BIG_WP 8 // 256@8 0.340 -> 0.317 ms vs two 8-wave workgroups on 128-pixel tiles with 1 tap per step)
-#endif
-#ifndef CFG_GTE_S1   // exact arithmetic: taps per weight step, stride-1 (9 taps: 1, 3) / stride-2 + shortcut (10: 1, 2, 5)
-#define CFG_GTE_S1 1
-#endif
-#ifndef CFG_GTE_S2   // round 4 sweep (profiles/r04h_sweep_exact*.txt): 2 taps per step -> 128->256 s2 1.57 -> 1.25 ms, 32->64 s2 1.46 -> 1.33 ms (exact 128 model
-#define CFG_GTE_S2 2 // +2 %), 64x64 model 958 k -> 1.00 M CU/s, 16x16 +3 %; 5 taps do not fit the LDS beside two activation planes
-#endif
-#ifndef CFG_UNE_32   // exact arithmetic: patch items per lane prefetched in registers (two planes each); a patch with more items per lane takes a
-#define CFG_UNE_32 5  // synchronous tail at the top of the tile (the 128 model's tiles have 4.4 - 4.8 items per lane: phase stamps, commit 36 - 45 %);
-                      // round 4 sweep (profiles/r04m_sweep_exact_prefetch.txt): 32 -> 32 1.57 -> 1.49 ms, 32 -> 64 s2 1.33 -> 1.27; the 64 / 128-channel
-                      // stride-2 layers LOSE with 5 (1.02 -> 1.09, 0.84 -> 0.87) and keep 3
-#endif
-#ifndef CFG_UNE_64
-#define CFG_UNE_64 3
-#endif
-#ifndef CFG_UNE_S2
-#define CFG_UNE_S2 3
-#endif
-#ifndef CFG_BIG_WP_EXACT  // ... exact arithmetic (small-CU models, maps of 1..16 pixels): 128-pixel tiles, 8 waves
-#define CFG_BIG_WP_EXACT 4
-#endif
-#ifndef CFG_BIG_WCB
-#define CFG_BIG_WCB 2
-#endif
-#ifndef CFG_128_WPB    // 128@16 stride-1 pixel blocks per wave (256@8 uses CFG_BIG_WPB)
-#define CFG_128_WPB CFG_BIG_WPB
-#endif
-#ifndef CFG_S2BIG_WPB  // 64->128, 128->256 stride-2 (+shortcut)
-#define CFG_S2BIG_WPB 1
-#endif
-#ifndef CFG_S2BIG_WP
-#define CFG_S2BIG_WP 4
-#endif
-#ifndef CFG_3264_WP    // 32->64 stride-2 (+shortcut): waves along pixels (tile = 32 * WP pixels) and patch items per lane in registers
-#define CFG_3264_WP 4
-#endif
-#ifndef CFG_3264_UN
-#define CFG_3264_UN 5
-#endif
-#ifndef CFG_3264_WCB   // 32->64 stride-2 (+shortcut)
-#define CFG_3264_WCB 1
-#endif
-#ifndef CFG_3264_WC
-#define CFG_3264_WC 2
-#endif
-#ifndef CFG_32_WPB     // 32@64 stride-1
-#define CFG_32_WPB 2
-#endif
-#ifndef CFG_32_WP
-#define CFG_32_WP 8
-#endif
-#ifndef CFG_64_GT      // taps per weight step, 64@32 stride-1 (9 = all weights resident in LDS)
-#define CFG_64_GT 9
-#endif
-#ifndef CFG_BIG_GT     // 128@16 / 256@8 stride-1: taps per weight step (48 KiB steps, 6 barriers per 64-channel chunk instead of 18)
-#define CFG_BIG_GT 3
-#endif
-#ifndef CFG_S1_MINW   // min waves / SIMD of the 64..256-channel stride-1 kernels (VGPR cap)
-#define CFG_S1_MINW 1
-#endif
-#ifndef CFG_S2_MINW
-#define CFG_S2_MINW 1
-#endif
-#ifndef CFG_32_MINW
-#define CFG_32_MINW 1
-#endif
-#ifndef CFG_BIG_WC
-#define CFG_BIG_WC 2
-#endif
-#ifndef CFG_64_DMA     // 64@32 stride-1: LDS-DMA double-buffered patch staging (fast arithmetic, maps >= 16 x 16)
-#define CFG_64_DMA 1
-#endif
-#ifndef CFG_64_DMA_UN  // LDS-DMA instructions per wave and tile: 10 x 34 pixels x 8 slots / (8 waves x 64 lanes) = 5.3
-#define CFG_64_DMA_UN 6
-#endif
-#ifndef CFG_BIG_DMA     // 128@16, 256@8 stride-1: ring kernel with LDS-DMA patch staging (conv_ring_dma_kernel), maps >= 8 x 8
-#define CFG_BIG_DMA 0
-#endif
-#ifndef CFG_BIG_DMA_WP  // ... waves along pixels (x CFG_BIG_WC = waves per workgroup): 4 -> 128-pixel tiles, 8 -> 256
-#define CFG_BIG_DMA_WP 4
-#endif
-#ifndef CFG_BIG_DMA_WPB
-#define CFG_BIG_DMA_WPB 1
-#endif
-#ifndef CFG_BIG_DMA_UNP   // patch pieces per patch wave and stage (upper bound, checked at launch)
-#define CFG_BIG_DMA_UNP 7
-#endif
-#ifndef CFG_BIG_DMA_NWL   // extra loader waves (0: the compute waves issue the LDS-DMA themselves)
-#define CFG_BIG_DMA_NWL 0
-#endif
-#ifndef CFG_BIG_DMA_FD    // fragment prefetch distance (items)
-#define CFG_BIG_DMA_FD 2
-#endif
-#ifndef CFG_BIG_DMA_MINW  // min waves per SIMD (VGPR cap)
-#define CFG_BIG_DMA_MINW 4
-#endif
-#ifndef CFG_BIG_DMA_RB  // ring depth, 128@16
-#define CFG_BIG_DMA_RB 2
-#endif
-#ifndef CFG_256_DMA_RB  // ring depth, 256@8 (its 4-sample patch buffers leave room for 3 slots at most)
-#define CFG_256_DMA_RB (CFG_BIG_DMA_RB > 3 ? 3 : CFG_BIG_DMA_RB)
-#endif
-#ifndef CFG_S2A_DMA      // 64->128 stride-2 (+shortcut) on conv_ring_dma_kernel: 0.51 -> 0.47 ms (one workgroup per CU, ring depth 3)
-#define CFG_S2A_DMA 1
-#endif
-#ifndef CFG_S2B_DMA      // 128->256 stride-2 (+shortcut): with 5 taps per weight step 0.41 -> 0.345 ms (register-staged kernel at 5 taps: 0.365)
-#define CFG_S2B_DMA 1
-#endif
-#ifndef CFG_S2_DMA_RB
-#define CFG_S2_DMA_RB 2
-#endif
-#ifndef CFG_S2A_GT       // taps per weight step of the 64->128 ring-DMA kernel (10 weight taps: 1, 2, 5); 5 with ring depth 2: 0.46 -> 0.41 ms
-#define CFG_S2A_GT 5
-#endif
-#ifndef CFG_S2B_GT       // ... of the 128->256 kernel (either variant)
-#define CFG_S2B_GT 5
-#endif
-#ifndef CFG_S2_DMA_NWL
-#define CFG_S2_DMA_NWL 0
-#endif
-#ifndef CFG_S2_DMA_MINW
-#define CFG_S2_DMA_MINW 2
-#endif
-// dma (fast arithmetic only): 0 none, 1 resident-weights DMA mode of conv_mfma_kernel, 2 conv_ring_dma_kernel with
-// its own pixel tiling {wpb, wp}_dma (the cout tiling, KC and GT -- i.e. the weight packing -- are shared)
-#ifndef CFG_LAT        // small-batch ("latency") variants of the >= 128-channel layers: 32-cout tiles, 4 waves, 128 pixels
-#define CFG_LAT 1
-#endif
-#ifndef CFG_LAT_GT     // taps per weight step, stride-1 latency variants (9 taps: 1, 3 or 9); batch-1 sweep: 9 is fastest
-#define CFG_LAT_GT 9
-#endif
-#ifndef CFG_LAT_GT2    // stride-2 (+shortcut, 10 weight taps: 1, 2, 5 or 10)
-#define CFG_LAT_GT2 10
-#endif
-struct CfgRow { int cin, cout, stride, kc[2], wcb, wpb, wc, wp, gt[2], dma, wpb_dma, wp_dma, lat; };  // lat: has a latency variant (fast arithmetic)
-static const CfgRow kCfg[] = {
-    //cin cout s   KC{fast,exact} WCB WPB WC WP  GT{fast,exact}
-    {32, 32, 1, {32, 32}, 1, CFG_32_WPB, 1, CFG_32_WP, {9, 3}},
-    {32, 64, 2, {32, 32}, CFG_3264_WCB, 1, CFG_3264_WC, CFG_3264_WP, {CFG_3264_GT, CFG_GTE_S2}},
-    {64, 64, 1, {64, 32}, CFG_64_WCB, CFG_64_WPB, CFG_64_WC, CFG_64_WP, {CFG_64_GT, CFG_GTE_S1}, CFG_64_DMA, 0, 0, CFG_LAT},
-    {64, 128, 2, {32, 32}, CFG_S2BIG_WCB, CFG_S2BIG_WPB, CFG_S2BIG_WC, CFG_S2BIG_WP, {2, CFG_GTE_S2}, CFG_S2A_DMA ? 2 : 0, CFG_S2BIG_WPB, CFG_S2BIG_WP, CFG_LAT},
-    {128, 128, 1, {64, 32}, CFG_BIG_WCB, CFG_128_WPB, CFG_BIG_WC, CFG_BIG_WP, {CFG_BIG_GT, CFG_GTE_S1}, CFG_BIG_DMA ? 2 : 0, CFG_BIG_DMA_WPB, CFG_BIG_DMA_WP, CFG_LAT},
-    {128, 256, 2, {32, 32}, CFG_S2BIG_WCB, CFG_S2BIG_WPB, CFG_S2BIG_WC, CFG_S2BIG_WP, {CFG_S2B_GT, CFG_GTE_S2}, CFG_S2B_DMA ? 2 : 0, CFG_S2BIG_WPB, CFG_S2BIG_WP, CFG_LAT},
-    {256, 256, 1, {64, 32}, CFG_BIG_WCB, CFG_BIG_WPB, CFG_BIG_WC, CFG_BIG_WP, {CFG_BIG_GT, CFG_GTE_S1}, CFG_BIG_DMA ? 2 : 0, CFG_BIG_DMA_WPB, CFG_BIG_DMA_WP, CFG_LAT},
-    // CU model (planes 32/64/96/128/256)
-    {64, 96, 2, {32, 32}, 3, 1, 1, 4, {1, CFG_GTE_S2}},
-    {96, 96, 1, {32, 32}, 3, 1, 1, 4, {3, CFG_GTE_S1}},
-    {96, 128, 2, {32, 32}, 2, 2, 2, 2, {2, CFG_GTE_S2}},
-};
-
-// hi+lo-WEIGHTS tier (NSPLIT = 3) on the exact packing: layers whose cin chunk is 32 in both packings run the FAST tiling's taps per step --
-// all taps resident + persistent workgroups for the 32-channel layers, 2 taps per ring step for the two big stride-2 layers (two weight
-// planes: 5 taps would not fit the ring) -- instead of the exact tiling's one / three taps, which is sized for the small models' maps
-// (round 3: 32->32 0.83 -> ... ms per launch in this tier).  Must mirror the nsplit == 3 branches of mlt_launch_conv.
-static int w2_gt(int cin, int cout, int stride, int gt_exact) {
-  if (cin == 32 && cout == 32 && stride == 1) return 9;
-  if (cin == 32 && cout == 64 && stride == 2) return CFG_3264_GT;
-  if (cin == 64 && cout == 128 && stride == 2) return 2;
-  if (cin == 128 && cout == 256 && stride == 2) return 2;
-  return gt_exact;
-}
-
-bool mlt_conv_cfg(int cin, int cout, int stride, int exact, ConvCfg *out) {
-  for (const CfgRow &r : kCfg)
-    if (r.cin == cin && r.cout == cout && r.stride == stride) {
-      out->kc = r.kc[exact ? 1 : 0];
-      out->ct = 32 * r.wcb * r.wc;
-      out->dma = exact ? 0 : r.dma;
-      out->mt = 32 * r.wpb * ((exact && r.cin >= 128 && r.stride == 1) ? CFG_BIG_WP_EXACT : r.wp);
-      out->mt_dma = r.dma == 2 ? 32 * r.wpb_dma * r.wp_dma : out->mt;
-      // the variants assume weights packed for 128-cout tiles (64 for the 64-channel layer)
-      out->lat = (r.lat && r.wcb * r.wc == (r.cout == 64 ? 2 : 4)) ? 1 : 0;  // (round 4: the exact arithmetic has its latency variants too)
-      out->gt = r.gt[exact ? 1 : 0];
-      out->gt_w2 = w2_gt(r.cin, r.cout, r.stride, r.gt[1]);
-      return true;
-    }
-  return false;
-}
-
-// RBF / RBE: weight-ring depth (fast / exact).  Must mirror kCfg.
-// UNF / UNE: patch items per lane prefetched in registers (fast / exact), sized for the 128x128 model's tiles
-// WPF / WPE: waves along pixels, fast / exact (the exact kernels serve the small-CU models, whose maps are tiny)
-#define CONV_CASE2(CIN, COUT, STRIDE, SCF, KCF, KCE, WCB, WPB, WC, WPF, WPE, GTF, GTE, RBF, RBE, UNF, UNE, MWF)                              \
-  if (cin == CIN && cout == COUT && stride == STRIDE) {                                                                             \
-    if (!exact) return launch_conv_t<CIN, COUT, STRIDE, 9, SCF, KCF, 1, WCB, WPB, WC, WPF, GTF, RBF, UNF, MWF, false>(a, grid_x, extra_lds, st); \
-    if (nsplit == 3) return launch_conv_t<CIN, COUT, STRIDE, 9, SCF, KCE, 3, WCB, WPB, WC, WPE, GTE, RBE, UNE, 1, false>(a, grid_x, extra_lds, st); \
-    if (nsplit == 6) return launch_conv_t<CIN, COUT, STRIDE, 9, SCF, KCE, 6, WCB, WPB, WC, WPE, GTE, RBE, UNE, 1, false>(a, grid_x, extra_lds, st); \
-    return launch_conv_t<CIN, COUT, STRIDE, 9, SCF, KCE, 2, WCB, WPB, WC, WPE, GTE, RBE, UNE, 1, false>(a, grid_x, extra_lds, st);          \
+  if (once.need(&dev)) {
+    if (hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kBigLds); e != hipSuccess) return e;
+    once.done(dev);
   }
-#define CONV_CASE(CIN, COUT, STRIDE, SCF, KCF, KCE, WCB, WPB, WC, WP, GTF, GTE, RBF, RBE, UNF, UNE, MWF) \
-  CONV_CASE2(CIN, COUT, STRIDE, SCF, KCF, KCE, WCB, WPB, WC, WP, WP, GTF, GTE, RBF, RBE, UNF, UNE, MWF)
+  hipLaunchKernelGGL(kern, grid, block, lds, st, a);
+  return hipGetLastError();
+}
+// ... with the once-flag as the kernel's own: this function, and its static with it, is instantiated per kernel, so no call site numbers a flag
+template <auto KERN, class ARGS> static hipError_t launch_big_lds(dim3 grid, dim3 block, int lds, hipStream_t st, const ARGS &a) {
+  static DeviceOnce once;
+  return launch_big_lds(KERN, once, grid, block, lds, st, a);
+}
 
+// ---- the per-conv kernels: ONE row per instantiation of conv_mfma_kernel / conv_ring_dma_kernel ----
+// A row is the key mlt_launch_conv selects it by and the kernel's template arguments, in the kernel's parameter order.  Everything else is derived
+// from the row: the selection (select_row), the launch geometry (row_threads / row_grid_y / row_lds / row_accepts), the host's view of a layer's
+// packing and tiling (mlt_conv_cfg), the ring bytes the dispatcher budgets patches against (mlt_conv_ring_bytes) and the text of
+// mlt_debug_conv_table.  A tiling that several instantiations share is one description (add_fast / add_exact below); what a row must share with the rows
+// the host reads and is not copied from them, table_consistent() checks at compile time.
+// Measurement history of the tilings: docs/KERNEL_NOTES.md ("Per-conv tilings").
+struct ConvRow {
+  int cin, cout, stride, nsplit, variant;  // key.  nsplit: 1 fast, 2 exact (weights and activations hi+lo), 3 weights hi+lo on the exact packing,
+                                           // 4 weights hi+lo on the FAST packing (MLT_MODEL_W2), 6 exact-lite; variant: MLT_CONV_*
+  bool ring;                               // conv_ring_dma_kernel (else conv_mfma_kernel)
+  int taps; bool sc; int kc, kn, wcb, wpb, wc, wp, gt, rb, un, minw; bool dma; int cbp; bool kmaj;  // TAPS SC KC NSPLIT WCB WPB WAVES_C WAVES_P GT RB UN|UNP MINW DMA CBP KMAJ
+  int nwl, fd;                             // ring only: NWL FD
+  constexpr int cbt() const { return wcb * wc; }        // 32-cout blocks per workgroup tile
+  constexpr int mt() const { return 32 * wpb * wp; }    // pixels per workgroup tile
+};
+constexpr ConvRow mfma_row(int cin, int cout, int stride, int nsplit, int variant, int taps, bool sc, int kc, int kn, int wcb, int wpb, int wc, int wp, int gt, int rb, int un,
+                           int minw, bool dma = false, int cbp = 0, bool kmaj = false) {
+  return {cin, cout, stride, nsplit, variant, false, taps, sc, kc, kn, wcb, wpb, wc, wp, gt, rb, un, minw, dma, cbp, kmaj, 0, 0};
+}
+constexpr ConvRow ring_row(int cin, int cout, int stride, int nsplit, int variant, bool sc, int kc, int wcb, int wpb, int wc, int wp, int gt, int rb, int unp, int minw, int nwl, int fd) {
+  return {cin, cout, stride, nsplit, variant, true, 9, sc, kc, 1, wcb, wpb, wc, wp, gt, rb, unp, minw, true, 0, false, nwl, fd};
+}
+constexpr int DEF = MLT_CONV_DEFAULT, DMA = MLT_CONV_DMA, LAT = MLT_CONV_LATENCY, CEN = MLT_CONV_CENTRE;
 // stride-2 convs always carry their block's projection shortcut (layer0.0's lives in stem5_kernel).
-bool mlt_conv_has_centre_variant(int cin, int cout) { return (cin == cout && (cin == 128 || cin == 256)) || (cin == 128 && cout == 256); }
+// A tiling that several instantiations share is written ONCE and copied by add_fast / add_exact:
+//  - the exact tiling of a layer (nsplit 2) also runs exact-lite (6) and hi+lo weights on the exact packing (3): the host sizes tiles and patches of all three
+//    from the nsplit-2 row, so they are one description;
+//  - the hi+lo-weights tier of a layer whose cin chunk is 32 in both packings has a DEFAULT row with the FAST tiling (all taps resident + persistent workgroups for
+//    the 32-channel layers; w2_gt taps per ring step for the two big stride-2 layers: two weight planes, 5 would not fit the ring) -- the host sizes its tiles from
+//    the fast row; the exact tiling's nsplit-3 copy of such a layer is then keyed under DMA (what (nsplit 3, DMA | LATENCY) selects; no plan asks for it).
+struct ConvTable {
+  ConvRow r[80] = {};  // (make_table fills 71)
+  int n = 0;
+  constexpr void add(ConvRow x) { r[n++] = x; }
+  constexpr const ConvRow *begin() const { return r; }
+  constexpr const ConvRow *end() const { return r + n; }
+  constexpr void add_as(ConvRow x, int nsplit, int variant) { x.nsplit = x.kn = nsplit; x.variant = variant; add(x); }
+  constexpr void add_fast(ConvRow x, int w2_gt = 0) {  // x: the nsplit-1 DEFAULT row; w2_gt > 0: + the hi+lo-weights tier on this tiling
+    add(x);
+    if (w2_gt) { x.gt = w2_gt; add_as(x, 3, MLT_CONV_DEFAULT); }
+  }
+  constexpr void add_exact(ConvRow x, int v3 = MLT_CONV_DEFAULT) {  // x: the nsplit-2 row (DEFAULT or LATENCY); v3: the key of the nsplit-3 copy of a DEFAULT row
+    add(x);
+    add_as(x, 6, x.variant);
+    if (x.variant == MLT_CONV_DEFAULT) add_as(x, 3, v3);
+  }
+};
+constexpr ConvTable make_table() {
+  ConvTable t;
+  // ---- throughput tilings.  Fast: the layer's own tiling.  Exact: 32-channel chunks, two-deep ring; the >= 128-channel stride-1 layers on 128-pixel tiles
+  // (these kernels serve the small-CU models, whose maps are tiny).
+  //                  cin cout s  ns var TAPS SC    KC NS WCB WPB WC WP GT RB UN MINW   w2_gt | v3
+  t.add_fast(mfma_row(32, 32, 1, 1, DEF, 9, false, 32, 1, 1, 2, 1, 8, 9, 1, 5, 1), 9);       // all nine taps resident, persistent workgroups
+  t.add_exact(mfma_row(32, 32, 1, 2, DEF, 9, false, 32, 2, 1, 2, 1, 8, 3, 2, 5, 1), DMA);    // UN 5: the 128 model's tiles have 4.4 - 4.8 patch items per lane
+  t.add_fast(mfma_row(32, 64, 2, 1, DEF, 9, true, 32, 1, 1, 1, 2, 4, 10, 1, 5, 1), 10);      // all ten weight taps resident
+  t.add_exact(mfma_row(32, 64, 2, 2, DEF, 9, true, 32, 2, 1, 1, 2, 4, 2, 2, 5, 1), DMA);     // 2 taps per step: 5 do not fit the LDS beside two activation planes
+  t.add_fast(mfma_row(64, 64, 1, 1, DEF, 9, false, 64, 1, 2, 1, 1, 8, 9, 2, 6, 1));          // all weights of a 64-channel chunk resident (chain_kernel<64> reads this packing)
+  t.add_exact(mfma_row(64, 64, 1, 2, DEF, 9, false, 32, 2, 2, 1, 1, 8, 1, 2, 3, 1));
+  t.add_fast(mfma_row(64, 128, 2, 1, DEF, 9, true, 32, 1, 2, 1, 2, 4, 2, 2, 5, 1), 2);
+  t.add_exact(mfma_row(64, 128, 2, 2, DEF, 9, true, 32, 2, 2, 1, 2, 4, 2, 2, 3, 1), DMA);    // UN 3: the 64 / 128-channel stride-2 layers lose with 5
+  t.add_fast(mfma_row(128, 128, 1, 1, DEF, 9, false, 64, 1, 2, 1, 2, 8, 3, 2, 3, 1));        // one 16-wave workgroup per CU on 256-pixel tiles, 48 KiB weight steps (chain_kernel<128> reads this packing)
+  t.add_exact(mfma_row(128, 128, 1, 2, DEF, 9, false, 32, 2, 2, 1, 2, 4, 1, 2, 2, 1));
+  t.add_fast(mfma_row(128, 256, 2, 1, DEF, 9, true, 32, 1, 2, 1, 2, 4, 5, 2, 5, 1), 2);
+  t.add_exact(mfma_row(128, 256, 2, 2, DEF, 9, true, 32, 2, 2, 1, 2, 4, 2, 2, 3, 1), DMA);
+  t.add_fast(mfma_row(256, 256, 1, 1, DEF, 9, false, 64, 1, 2, 1, 2, 8, 3, 2, 4, 1));        // (chain_kernel<256> reads this packing)
+  t.add_exact(mfma_row(256, 256, 1, 2, DEF, 9, false, 32, 2, 2, 1, 2, 4, 1, 2, 2, 1));
+  // CU model (planes 32 / 64 / 96 / 128 / 256)
+  t.add_fast(mfma_row(64, 96, 2, 1, DEF, 9, true, 32, 1, 3, 1, 1, 4, 1, 2, 5, 1));
+  t.add_exact(mfma_row(64, 96, 2, 2, DEF, 9, true, 32, 2, 3, 1, 1, 4, 2, 2, 3, 1));
+  t.add_fast(mfma_row(96, 96, 1, 1, DEF, 9, false, 32, 1, 3, 1, 1, 4, 3, 2, 3, 1));
+  t.add_exact(mfma_row(96, 96, 1, 2, DEF, 9, false, 32, 2, 3, 1, 1, 4, 1, 2, 2, 1));
+  t.add_fast(mfma_row(96, 128, 2, 1, DEF, 9, true, 32, 1, 2, 2, 2, 2, 2, 2, 5, 1));
+  t.add_exact(mfma_row(96, 128, 2, 2, DEF, 9, true, 32, 2, 2, 2, 2, 2, 2, 2, 3, 1));
+  // ---- LDS-DMA patch staging (fast arithmetic): resident weights for 64@32 on the tiles of its DEFAULT row, conv_ring_dma_kernel for the two big stride-2
+  // layers (one workgroup per CU, its own pixel tiling: mlt_conv_cfg's mt_dma)
+  //                                                                                     DMA
+  t.add(mfma_row(64, 64, 1, 1, DMA, 9, false, 64, 1, 2, 1, 1, 8, 9, 1, 6, 1, true));   // UN 6: 10 x 34 pixels x 8 slots / (8 waves x 64 lanes) = 5.3 LDS-DMA instructions per wave and tile
+  //             cin cout  s ns var SC    KC WCB WPB WC WP GT RB UNP MINW NWL FD
+  t.add(ring_row(64, 128, 2, 1, DMA, true, 32, 2, 1, 2, 4, 5, 2, 20, 2, 0, 2));
+  t.add(ring_row(128, 256, 2, 1, DMA, true, 32, 2, 1, 2, 4, 5, 2, 20, 2, 0, 2));
+  // ---- latency variants (small launches): 32 couts x 128 pixels per 4-wave workgroup -- 4x the workgroups, a quarter of the weight bytes each -- on the
+  // weights as the throughput row packs them (CBP: its 32-cout blocks per tile).  Per accumulator the order of the large tiles, so the same bits.
+  //                                                                             DMA   CBP KMAJ
+  t.add(mfma_row(64, 64, 1, 1, LAT, 9, false, 64, 1, 1, 1, 1, 4, 9, 1, 6, 1, false, 2));
+  t.add(mfma_row(128, 128, 1, 1, LAT, 9, false, 64, 1, 1, 1, 1, 4, 9, 2, 6, 1, false, 4));   // GT 9: fastest of 1 / 3 / 9 in the batch-1 sweep
+  t.add(mfma_row(256, 256, 1, 1, LAT, 9, false, 64, 1, 1, 1, 1, 4, 9, 2, 6, 1, false, 4));
+  t.add(mfma_row(64, 128, 2, 1, LAT, 9, true, 32, 1, 1, 1, 1, 4, 10, 2, 10, 1, false, 4, true));   // all 10 weight taps of a chunk per step, k-step-major: the whole-stage kernel's accumulation order
+  t.add(mfma_row(128, 256, 2, 1, LAT, 9, true, 32, 1, 1, 1, 1, 4, 10, 2, 10, 1, false, 4, true));
+  t.add_exact(mfma_row(64, 64, 1, 2, LAT, 9, false, 32, 2, 1, 1, 1, 4, 1, 2, 4, 1, false, 2));
+  t.add_exact(mfma_row(128, 128, 1, 2, LAT, 9, false, 32, 2, 1, 1, 1, 4, 1, 2, 4, 1, false, 4));
+  t.add_exact(mfma_row(256, 256, 1, 2, LAT, 9, false, 32, 2, 1, 1, 1, 4, 1, 2, 4, 1, false, 4));
+  t.add_exact(mfma_row(64, 128, 2, 2, LAT, 9, true, 32, 2, 1, 1, 1, 4, 2, 2, 5, 1, false, 4));
+  t.add_exact(mfma_row(128, 256, 2, 2, LAT, 9, true, 32, 2, 1, 1, 1, 4, 2, 2, 5, 1, false, 4));
+  // hi+lo weights on the FAST packing: the stride-1 layers with >= 64 channels (kc = 64) have this ONE per-conv form at any launch size -- large launches go
+  // through chain_kernel<..., W2>, and this is its bit-identical per-conv form.  Kernel NSPLIT 3: fp16 lo plane (mlt_model.cpp), 5: FP8 lo plane
+  t.add(mfma_row(64, 64, 1, 4, LAT, 9, false, 64, 3, 1, 1, 1, 4, 9, 1, 6, 1, false, 2));
+  t.add(mfma_row(128, 128, 1, 4, LAT, 9, false, 64, 5, 1, 1, 1, 4, 3, 2, 6, 1, false, 4));
+  t.add(mfma_row(256, 256, 1, 4, LAT, 9, false, 64, 5, 1, 1, 1, 4, 3, 2, 6, 1, false, 4));
+  // ---- centre tap only (TAPS = 1): the small-CU models' layers on 1x1 maps, 128 samples per tile; stride 2: centre tap + projection shortcut on the same pixel
+  t.add(mfma_row(128, 128, 1, 1, CEN, 1, false, 64, 1, 2, 1, 2, 8, 1, 1, 2, 1));
+  t.add(mfma_row(128, 128, 1, 2, CEN, 1, false, 32, 2, 2, 1, 2, 4, 1, 1, 2, 1));
+  t.add(mfma_row(128, 256, 2, 1, CEN, 1, true, 32, 1, 2, 1, 2, 4, 1, 2, 5, 1));
+  t.add(mfma_row(128, 256, 2, 2, CEN, 1, true, 32, 2, 2, 1, 2, 4, 1, 2, 3, 1));
+  t.add(mfma_row(256, 256, 1, 1, CEN, 1, false, 64, 1, 2, 1, 2, 8, 1, 1, 2, 1));
+  t.add(mfma_row(256, 256, 1, 2, CEN, 1, false, 32, 2, 2, 1, 2, 4, 1, 1, 2, 1));
+  return t;
+}
+constexpr ConvTable kTable = make_table();
+constexpr int kNumRows = kTable.n;
+constexpr const ConvRow (&kRows)[80] = kTable.r;  // (rows kNumRows .. 79 are unused)
 
-// nsplit: 1 fast, 2 exact (weights and activations hi+lo), 3 weights hi+lo only (the tiling of the exact kernels, 2 MFMAs, single activation planes)
-hipError_t mlt_launch_conv(int cin, int cout, int stride, int nsplit, int variant, const ConvArgs &a, int grid_x, int extra_lds, hipStream_t st) {
-  if (nsplit == 4) {
-    // hi+lo weights on the FAST tiling (MLT_MODEL_W2).  The stride-2 and 32-channel layers have ONE tiling for both packings (same kc / ct), so
-    // their bytes are those of the exact packing and they run the nsplit == 3 kernels below; the stride-1 layers with >= 64 channels (kc = 64)
-    // run the 32-cout x 128-pixel variants on any launch size -- large launches of those layers go through chain_kernel<..., W2>, and this is
-    // its bit-identical per-conv form: (chunk, tap, k-step, hi, lo) per accumulator.
-    if (stride == 1 && cin == cout && cin >= 64) {
-      if (variant != MLT_CONV_LATENCY) return hipErrorInvalidValue;
-      // (NSPLIT = 5: hi fp16 plane + FP8 lo plane, the packing of these layers in the MLT_MODEL_W2 model)
-      if (cin == 64) return launch_conv_t<64, 64, 1, 9, false, 64, 3, 1, 1, 1, 4, 9, 1, 6, 1, false, 2>(a, grid_x, extra_lds, st);   // (fp16 lo plane: see mlt_model.cpp)
-      if (cin == 128) return launch_conv_t<128, 128, 1, 9, false, 64, 5, 1, 1, 1, 4, 3, 2, 6, 1, false, 4>(a, grid_x, extra_lds, st);
-      if (cin == 256) return launch_conv_t<256, 256, 1, 9, false, 64, 5, 1, 1, 1, 4, 3, 2, 6, 1, false, 4>(a, grid_x, extra_lds, st);
-      return hipErrorInvalidValue;
-    }
-    if (variant != MLT_CONV_DEFAULT) return hipErrorInvalidValue;
+constexpr int find_row(int cin, int cout, int stride, int nsplit, int variant) {
+  for (int i = 0; i < kNumRows; ++i)
+    if (kRows[i].cin == cin && kRows[i].cout == cout && kRows[i].stride == stride && kRows[i].nsplit == nsplit && kRows[i].variant == variant) return i;
+  return -1;
+}
+// hi+lo weights on the fast packing: every layer but the stride-1 ones with >= 64 channels has ONE tiling for both packings (same kc / ct), so its
+// bytes are those of the exact packing and it runs that tier's (nsplit 3) row
+constexpr bool w2_runs_exact_tier(int cin, int cout, int stride) { return !(stride == 1 && cin == cout && cin >= 64); }
+// The row of a key, or -1: a pure function of the key.  A variant without a row of its own for the key is refused, except that DMA -- and, for nsplit 3,
+// LATENCY, which asks as DMA does -- falls back to the DEFAULT row.
+constexpr int select_row(int cin, int cout, int stride, int nsplit, int variant) {
+  if (nsplit == 4 && w2_runs_exact_tier(cin, cout, stride)) {
+    if (variant != MLT_CONV_DEFAULT) return -1;
     nsplit = 3;
   }
-  const bool exact = nsplit >= 2;
-  const bool dma = variant == MLT_CONV_DMA;
-  if (variant == MLT_CONV_CENTRE && (nsplit == 3 || nsplit == 6)) return hipErrorInvalidValue;  // (1x1 maps: small-CU models only, which do not use this tier)
-  if (variant == MLT_CONV_CENTRE) {  // stride-1 layers of the small-CU models on 1x1 maps: centre tap only (TAPS = 1), 128 samples per tile
-    if (cin == 128 && cout == 128 && stride == 1)
-      return exact ? launch_conv_t<128, 128, 1, 1, false, 32, 2, CFG_BIG_WCB, 1, CFG_BIG_WC, CFG_BIG_WP_EXACT, 1, 1, 2, 1, false>(a, grid_x, extra_lds, st)
-                   : launch_conv_t<128, 128, 1, 1, false, 64, 1, CFG_BIG_WCB, 1, CFG_BIG_WC, CFG_BIG_WP, 1, 1, 2, 1, false>(a, grid_x, extra_lds, st);
-    if (cin == 128 && cout == 256 && stride == 2)  // 1x1 input: centre tap + projection shortcut, both 1x1 on the same pixel
-      return exact ? launch_conv_t<128, 256, 2, 1, true, 32, 2, CFG_S2BIG_WCB, CFG_S2BIG_WPB, CFG_S2BIG_WC, CFG_S2BIG_WP, 1, 2, 3, 1, false>(a, grid_x, extra_lds, st)
-                   : launch_conv_t<128, 256, 2, 1, true, 32, 1, CFG_S2BIG_WCB, CFG_S2BIG_WPB, CFG_S2BIG_WC, CFG_S2BIG_WP, 1, 2, 5, 1, false>(a, grid_x, extra_lds, st);
-    if (cin == 256 && cout == 256 && stride == 1)
-      return exact ? launch_conv_t<256, 256, 1, 1, false, 32, 2, CFG_BIG_WCB, 1, CFG_BIG_WC, CFG_BIG_WP_EXACT, 1, 1, 2, 1, false>(a, grid_x, extra_lds, st)
-                   : launch_conv_t<256, 256, 1, 1, false, 64, 1, CFG_BIG_WCB, 1, CFG_BIG_WC, CFG_BIG_WP, 1, 1, 2, 1, false>(a, grid_x, extra_lds, st);
-    return hipErrorInvalidValue;
-  }
-#if CFG_LAT
-  if (variant == MLT_CONV_LATENCY && nsplit == 6) {  // exact-lite, small launches: the geometry of the exact arithmetic's latency variants (same per-accumulator order as the large tiles)
-    if (cin == 64 && cout == 64 && stride == 1) return launch_conv_t<64, 64, 1, 9, false, 32, 6, 1, 1, 1, 4, CFG_GTE_S1, 2, 4, 1, false, 2>(a, grid_x, extra_lds, st);
-    if (cin == 128 && cout == 128 && stride == 1) return launch_conv_t<128, 128, 1, 9, false, 32, 6, 1, 1, 1, 4, CFG_GTE_S1, 2, 4, 1, false, 4>(a, grid_x, extra_lds, st);
-    if (cin == 256 && cout == 256 && stride == 1) return launch_conv_t<256, 256, 1, 9, false, 32, 6, 1, 1, 1, 4, CFG_GTE_S1, 2, 4, 1, false, 4>(a, grid_x, extra_lds, st);
-    if (cin == 64 && cout == 128 && stride == 2) return launch_conv_t<64, 128, 2, 9, true, 32, 6, 1, 1, 1, 4, CFG_GTE_S2, 2, 5, 1, false, 4>(a, grid_x, extra_lds, st);
-    if (cin == 128 && cout == 256 && stride == 2) return launch_conv_t<128, 256, 2, 9, true, 32, 6, 1, 1, 1, 4, CFG_GTE_S2, 2, 5, 1, false, 4>(a, grid_x, extra_lds, st);
-    return hipErrorInvalidValue;
-  }
-  if (variant == MLT_CONV_LATENCY && nsplit == 2) {
-    // Exact arithmetic, small launches (round 4: the guards' re-runs of a few flagged CUs, one-CU calls of the exact / exact-stage tiers, small
-    // batches of the small models): the same 32-cout x 128-pixel tiles on the exact packing (4x the workgroups, a quarter of the weight
-    // bytes each); per accumulator the order of the large tiles (chunk, tap, k-step: Wh Xh, Wh Xl, Wl Xh), so the results are the same bits.
-    if (cin == 64 && cout == 64 && stride == 1) return launch_conv_t<64, 64, 1, 9, false, 32, 2, 1, 1, 1, 4, CFG_GTE_S1, 2, 4, 1, false, 2>(a, grid_x, extra_lds, st);
-    if (cin == 128 && cout == 128 && stride == 1) return launch_conv_t<128, 128, 1, 9, false, 32, 2, 1, 1, 1, 4, CFG_GTE_S1, 2, 4, 1, false, 4>(a, grid_x, extra_lds, st);
-    if (cin == 256 && cout == 256 && stride == 1) return launch_conv_t<256, 256, 1, 9, false, 32, 2, 1, 1, 1, 4, CFG_GTE_S1, 2, 4, 1, false, 4>(a, grid_x, extra_lds, st);
-    if (cin == 64 && cout == 128 && stride == 2) return launch_conv_t<64, 128, 2, 9, true, 32, 2, 1, 1, 1, 4, CFG_GTE_S2, 2, 5, 1, false, 4>(a, grid_x, extra_lds, st);
-    if (cin == 128 && cout == 256 && stride == 2) return launch_conv_t<128, 256, 2, 9, true, 32, 2, 1, 1, 1, 4, CFG_GTE_S2, 2, 5, 1, false, 4>(a, grid_x, extra_lds, st);
-    return hipErrorInvalidValue;
-  }
-  if (variant == MLT_CONV_LATENCY && !exact) {  // 32 couts x 128 pixels per 4-wave workgroup, weights packed for CBP = 4
-    if (cin == 64 && cout == 64 && stride == 1) return launch_conv_t<64, 64, 1, 9, false, 64, 1, 1, 1, 1, 4, 9, 1, 6, 1, false, 2>(a, grid_x, extra_lds, st);
-    if (cin == 128 && cout == 128 && stride == 1) return launch_conv_t<128, 128, 1, 9, false, 64, 1, 1, 1, 1, 4, CFG_LAT_GT, 2, 6, 1, false, 4>(a, grid_x, extra_lds, st);
-    if (cin == 256 && cout == 256 && stride == 1) return launch_conv_t<256, 256, 1, 9, false, 64, 1, 1, 1, 1, 4, CFG_LAT_GT, 2, 6, 1, false, 4>(a, grid_x, extra_lds, st);
-    // (k-step-major items: the accumulation order of the whole-stage kernel, see KMAJ)
-    static_assert(CFG_LAT_GT2 == 10, "the stride-2 latency variants take all 10 weight taps of a chunk per step");
-    if (cin == 64 && cout == 128 && stride == 2) return launch_conv_t<64, 128, 2, 9, true, 32, 1, 1, 1, 1, 4, CFG_LAT_GT2, 2, 10, 1, false, 4, true>(a, grid_x, extra_lds, st);
-    if (cin == 128 && cout == 256 && stride == 2) return launch_conv_t<128, 256, 2, 9, true, 32, 1, 1, 1, 1, 4, CFG_LAT_GT2, 2, 10, 1, false, 4, true>(a, grid_x, extra_lds, st);
-    return hipErrorInvalidValue;
-  }
-#endif
-#if CFG_BIG_DMA
-  if (dma && !exact && cin == 128 && cout == 128 && stride == 1)
-    return launch_ring_dma_t<128, 128, 1, false, 64, CFG_BIG_WCB, CFG_BIG_DMA_WPB, CFG_BIG_WC, CFG_BIG_DMA_WP, CFG_BIG_GT, CFG_BIG_DMA_RB, CFG_BIG_DMA_UNP, CFG_BIG_DMA_MINW, CFG_BIG_DMA_NWL, CFG_BIG_DMA_FD>(a, grid_x, st);
-  if (dma && !exact && cin == 256 && cout == 256 && stride == 1)
-    return launch_ring_dma_t<256, 256, 1, false, 64, CFG_BIG_WCB, CFG_BIG_DMA_WPB, CFG_BIG_WC, CFG_BIG_DMA_WP, CFG_BIG_GT, CFG_256_DMA_RB, CFG_BIG_DMA_UNP, CFG_BIG_DMA_MINW, CFG_BIG_DMA_NWL, CFG_BIG_DMA_FD>(a, grid_x, st);
-#endif
-#if CFG_S2A_DMA
-  if (dma && !exact && cin == 64 && cout == 128 && stride == 2)
-    return launch_ring_dma_t<64, 128, 2, true, 32, CFG_S2BIG_WCB, CFG_S2BIG_WPB, CFG_S2BIG_WC, CFG_S2BIG_WP, CFG_S2A_GT, CFG_S2_DMA_RB, 20, CFG_S2_DMA_MINW, CFG_S2_DMA_NWL, 2>(a, grid_x, st);
-#endif
-#if CFG_S2B_DMA
-  if (dma && !exact && cin == 128 && cout == 256 && stride == 2)
-    return launch_ring_dma_t<128, 256, 2, true, 32, CFG_S2BIG_WCB, CFG_S2BIG_WPB, CFG_S2BIG_WC, CFG_S2BIG_WP, CFG_S2B_GT, CFG_S2_DMA_RB, 20, CFG_S2_DMA_MINW, CFG_S2_DMA_NWL, 2>(a, grid_x, st);
-#endif
-#if CFG_64_DMA
-  if (dma && !exact && cin == 64 && cout == 64 && stride == 1)
-    return launch_conv_t<64, 64, 1, 9, false, 64, 1, CFG_64_WCB, CFG_64_WPB, CFG_64_WC, CFG_64_WP, 9, 1, CFG_64_DMA_UN, CFG_S1_MINW, true>(a, grid_x, extra_lds, st);
-#endif
-  if (nsplit == 3 && variant == MLT_CONV_DEFAULT) {  // hi+lo-weights tier with its own tiling (w2_gt above)
-    static_assert(CFG_3264_GT == 10, "32->64 stride-2: all ten weight taps resident");
-    if (cin == 32 && cout == 32 && stride == 1) return launch_conv_t<32, 32, 1, 9, false, 32, 3, 1, CFG_32_WPB, 1, CFG_32_WP, 9, 1, 5, 1, false>(a, grid_x, extra_lds, st);
-    if (cin == 32 && cout == 64 && stride == 2) return launch_conv_t<32, 64, 2, 9, true, 32, 3, CFG_3264_WCB, 1, CFG_3264_WC, CFG_3264_WP, CFG_3264_GT, 1, CFG_3264_UN, 1, false>(a, grid_x, extra_lds, st);
-    if (cin == 64 && cout == 128 && stride == 2) return launch_conv_t<64, 128, 2, 9, true, 32, 3, CFG_S2BIG_WCB, CFG_S2BIG_WPB, CFG_S2BIG_WC, CFG_S2BIG_WP, 2, 2, 5, 1, false>(a, grid_x, extra_lds, st);
-    if (cin == 128 && cout == 256 && stride == 2) return launch_conv_t<128, 256, 2, 9, true, 32, 3, CFG_S2BIG_WCB, CFG_S2BIG_WPB, CFG_S2BIG_WC, CFG_S2BIG_WP, 2, 2, 5, 1, false>(a, grid_x, extra_lds, st);
-  }
-  CONV_CASE(32, 32, 1, false, 32, 32, 1, CFG_32_WPB, 1, CFG_32_WP, 9, 3, 1, 2, 5, CFG_UNE_32, CFG_32_MINW)
-  CONV_CASE(32, 64, 2, true, 32, 32, CFG_3264_WCB, 1, CFG_3264_WC, CFG_3264_WP, CFG_3264_GT, CFG_GTE_S2, CFG_3264_RB, 2, CFG_3264_UN, CFG_UNE_32, CFG_32_MINW)
-  CONV_CASE(64, 64, 1, false, 64, 32, CFG_64_WCB, CFG_64_WPB, CFG_64_WC, CFG_64_WP, CFG_64_GT, CFG_GTE_S1, CFG_S1_RB, 2, 6, CFG_UNE_64, CFG_S1_MINW)
-  CONV_CASE(64, 128, 2, true, 32, 32, CFG_S2BIG_WCB, CFG_S2BIG_WPB, CFG_S2BIG_WC, CFG_S2BIG_WP, 2, CFG_GTE_S2, 2, 2, 5, CFG_UNE_S2, CFG_S2_MINW)
-  CONV_CASE2(128, 128, 1, false, 64, 32, CFG_BIG_WCB, CFG_128_WPB, CFG_BIG_WC, CFG_BIG_WP, CFG_BIG_WP_EXACT, CFG_BIG_GT, CFG_GTE_S1, CFG_S1_RB, 2, 3, 2, CFG_S1_MINW)
-  CONV_CASE(128, 256, 2, true, 32, 32, CFG_S2BIG_WCB, CFG_S2BIG_WPB, CFG_S2BIG_WC, CFG_S2BIG_WP, CFG_S2B_GT, CFG_GTE_S2, 2, 2, 5, CFG_UNE_S2, CFG_S2_MINW)
-  CONV_CASE2(256, 256, 1, false, 64, 32, CFG_BIG_WCB, CFG_BIG_WPB, CFG_BIG_WC, CFG_BIG_WP, CFG_BIG_WP_EXACT, CFG_BIG_GT, CFG_GTE_S1, CFG_S1_RB, 2, 4, 2, CFG_S1_MINW)
-  CONV_CASE(64, 96, 2, true, 32, 32, 3, 1, 1, 4, 1, CFG_GTE_S2, 2, 2, 5, 3, 1)
-  CONV_CASE(96, 96, 1, false, 32, 32, 3, 1, 1, 4, 3, CFG_GTE_S1, 2, 2, 3, 2, 1)
-  CONV_CASE(96, 128, 2, true, 32, 32, 2, 2, 2, 2, 2, CFG_GTE_S2, 2, 2, 5, 3, 1)
-  return hipErrorInvalidValue;
+  if (nsplit == 3 && variant == MLT_CONV_LATENCY) variant = MLT_CONV_DMA;
+  const int i = find_row(cin, cout, stride, nsplit, variant);
+  return (i < 0 && variant == MLT_CONV_DMA) ? find_row(cin, cout, stride, nsplit, MLT_CONV_DEFAULT) : i;
 }
 
-// fused chain kernels: (channels, map height) -> instantiation.  128@16: one sample per 16-wave workgroup, weights packed for
-// 128-cout tiles / 64-channel chunks / 3 taps per step (the stand-alone layer's packing).
+// launch geometry of a row
+constexpr int row_threads(const ConvRow &r) { return 64 * (r.wc * r.wp + r.nwl); }
+constexpr int row_grid_y(const ConvRow &r) { return r.cout / (32 * r.cbt()); }
+constexpr int row_ring_bytes(const ConvRow &r) {  // the weight ring: slots x (weight planes of one step [+ the FP8 lo plane])
+  const int plane = r.gt * (r.kc / 16) * r.cbt() * 1024;
+  if (r.ring) return r.rb * plane;
+  const int nbuf = (r.taps + (r.sc ? 1 : 0)) / r.gt > 1 ? r.rb : 1;
+  return nbuf * ((r.kn == 2 || r.kn == 3 || r.kn == 6 ? 2 : 1) * plane + (r.kn == 5 ? r.gt * r.cbt() * 2048 : 0));
+}
+constexpr int row_lds(const ConvRow &r, int patch_bytes, int extra_lds) {
+  if (r.ring) return 2 * patch_bytes + row_ring_bytes(r) + (r.nwl ? 32 * r.cbt() * 4 * (r.sc ? 2 : 1) : 0);
+  // (kernel NSPLIT 5: + the e4m3 copy of the patch, 80 bytes per pixel of the fp16 patch's KC * 2 + 16)
+  const int patch8 = r.kn == 5 ? ((patch_bytes / (r.kc * 2 + 16) + 1) * (r.kc + 16) + 1023) / 1024 * 1024 : 0;
+  return ((r.dma || r.kn == 2 || r.kn == 6) ? 2 : 1) * patch_bytes + row_ring_bytes(r) + patch8 + extra_lds;
+}
+constexpr bool row_accepts(const ConvRow &r, int patch_bytes, int extra_lds) {
+  if (row_lds(r, patch_bytes, extra_lds) > kBigLds) return false;
+  const int nw = r.wc * r.wp, nwp = r.nwl ? r.nwl - r.nwl / 2 : nw - nw / 2;  // ring: the patch waves issue at most UNP 1 KiB pieces each per stage
+  return !r.ring || (patch_bytes >> 10) <= r.un * nwp;
+}
+
+// What the compiler checks for a new or edited row.  The host (mlt_conv_cfg -> PackedConv -> run_conv) reads the packing and the tile of a layer from its
+// nsplit-1 / nsplit-2 DEFAULT rows only and uses that view for every other row of the layer; whatever a row shares with them and is not copied by
+// add_fast / add_exact is held equal here:
+constexpr bool weights_resident(const ConvRow &r, int gt) { return gt == r.taps + (r.sc ? 1 : 0) && r.cin == r.kc; }  // (the kernels' W_RESIDENT: persistent workgroups)
+constexpr bool table_consistent() {
+  for (const ConvRow &r : kTable) {
+    // -- the weights: every row reads them as the DEFAULT row of its packing (fast: nsplit 1 and 4; exact: 2, 3 and 6) tiles them -- same cin chunk, same
+    //    32-cout blocks per tile; a latency row's narrower tile names the packed tile's blocks in CBP (128-cout tiles, 64 for the 64-channel layer)
+    const bool fast_packing = r.nsplit == 1 || r.nsplit == 4;
+    const int b = find_row(r.cin, r.cout, r.stride, fast_packing ? 1 : 2, MLT_CONV_DEFAULT);
+    if (b < 0 || r.kc != kRows[b].kc || (r.cbp ? r.cbp : r.cbt()) != kRows[b].cbt()) return false;
+    if (r.cout % (32 * r.cbt()) != 0 || r.cin % r.kc != 0 || (r.taps + (r.sc ? 1 : 0)) % r.gt != 0) return false;
+    // -- the tile and the persistence decision: run_conv cuts tiles of pc.mt pixels (128 for a latency launch, mt_dma = the ring row's own for ring-DMA) and
+    //    caps the grid when pc.gt says the weights are resident (centre tap: gt 1)
+    if (r.variant == MLT_CONV_LATENCY) {
+      if (r.mt() != 128 || weights_resident(r, r.gt) != weights_resident(r, kRows[b].gt)) return false;
+    } else if (r.variant == MLT_CONV_CENTRE) {
+      const int d = find_row(r.cin, r.cout, r.stride, r.nsplit, MLT_CONV_DEFAULT);
+      if (d < 0 || r.gt != 1 || r.mt() != kRows[d].mt()) return false;
+    } else if (!r.ring) {
+      // (nsplit 3 is asked for through nsplit 4 -- hi+lo weights on the fast packing --, so its tiles are the fast row's; its taps per step reach the host
+      //  as gt_w2, read from the row itself)
+      const int v = find_row(r.cin, r.cout, r.stride, r.nsplit == 6 ? 2 : (r.nsplit == 3 && w2_runs_exact_tier(r.cin, r.cout, r.stride)) ? 1 : fast_packing ? 1 : 2, MLT_CONV_DEFAULT);
+      if (v < 0 || r.mt() != kRows[v].mt() || (r.nsplit != 3 && r.gt != kRows[v].gt)) return false;
+    }
+    if (r.variant == MLT_CONV_DEFAULT && r.nsplit == 1) {
+      // -- every layer has all four arithmetics, and the hi+lo-weights tier of the fast packing (nsplit 4 -> 3) finds the bytes it expects
+      const int e = find_row(r.cin, r.cout, r.stride, 2, MLT_CONV_DEFAULT), w = select_row(r.cin, r.cout, r.stride, 3, MLT_CONV_DEFAULT);
+      if (e < 0 || w < 0 || find_row(r.cin, r.cout, r.stride, 6, MLT_CONV_DEFAULT) < 0) return false;
+      if (w2_runs_exact_tier(r.cin, r.cout, r.stride) && (r.kc != kRows[e].kc || r.cbt() != kRows[e].cbt())) return false;
+    }
+  }
+  return true;
+}
+static_assert(table_consistent(), "a conv row disagrees with the packing or the tile of the rows the host reads for its layer (see table_consistent)");
+
+template <int I> static hipError_t launch_row(const ConvArgs &a, int grid_x, int extra_lds, hipStream_t st) {
+  constexpr ConvRow r = kRows[I];
+  if (!row_accepts(r, a.patch_bytes, extra_lds)) return hipErrorInvalidValue;
+  const dim3 grid(grid_x, row_grid_y(r)), block(row_threads(r));
+  const int lds = row_lds(r, a.patch_bytes, extra_lds);
+  if constexpr (r.ring)
+    return launch_big_lds<conv_ring_dma_kernel<r.cin, r.cout, r.stride, r.sc, r.kc, r.wcb, r.wpb, r.wc, r.wp, r.gt, r.rb, r.un, r.minw, r.nwl, r.fd>>(grid, block, lds, st, a);
+  else
+    return launch_big_lds<conv_mfma_kernel<r.cin, r.cout, r.stride, r.taps, r.sc, r.kc, r.kn, r.wcb, r.wpb, r.wc, r.wp, r.gt, r.rb, r.un, r.minw, r.dma, r.cbp, r.kmaj>>(grid, block, lds, st, a);
+}
+template <size_t... I> static hipError_t launch_rows(int row, std::index_sequence<I...>, const ConvArgs &a, int grid_x, int extra_lds, hipStream_t st) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)((row == (int)I && ((e = launch_row<(int)I>(a, grid_x, extra_lds, st)), true)) || ...);
+  return e;
+}
+hipError_t mlt_launch_conv(int cin, int cout, int stride, int nsplit, int variant, const ConvArgs &a, int grid_x, int extra_lds, hipStream_t st) {
+  return launch_rows(select_row(cin, cout, stride, nsplit, variant), std::make_index_sequence<kNumRows>(), a, grid_x, extra_lds, st);
+}
+
+bool mlt_conv_has_centre_variant(int cin, int cout) {
+  for (const ConvRow &r : kTable)
+    if (r.variant == MLT_CONV_CENTRE && r.cin == cin && r.cout == cout) return true;
+  return false;
+}
+int mlt_conv_ring_bytes(int cin, int cout, int stride, int nsplit, int variant) {
+  const int i = select_row(cin, cout, stride, nsplit, variant);
+  return i < 0 ? -1 : row_ring_bytes(kRows[i]);
+}
+// The host's view of a layer (packing, patch sizing): read off the rows the launcher selects
+bool mlt_conv_cfg(int cin, int cout, int stride, int exact, ConvCfg *out) {
+  const int ns = exact ? 2 : 1, i = find_row(cin, cout, stride, ns, MLT_CONV_DEFAULT);
+  if (i < 0) return false;
+  const ConvRow &r = kRows[i];
+  const int d = find_row(cin, cout, stride, 1, MLT_CONV_DMA);  // LDS-DMA staging (fast arithmetic only): 1 resident weights (conv_mfma_kernel), 2 conv_ring_dma_kernel
+  out->kc = r.kc; out->ct = 32 * r.cbt(); out->mt = r.mt(); out->gt = r.gt;
+  out->dma = (exact || d < 0) ? 0 : kRows[d].ring ? 2 : 1;
+  out->mt_dma = (d >= 0 && kRows[d].ring) ? kRows[d].mt() : out->mt;
+  out->lat = find_row(cin, cout, stride, ns, MLT_CONV_LATENCY) >= 0 ? 1 : 0;
+  out->gt_w2 = kRows[select_row(cin, cout, stride, 3, MLT_CONV_DEFAULT)].gt;  // taps per step of the row the hi+lo-weights tier launches
+  return true;
+}
+
+// Host-only hook (not a product entry; no HIP call, no device): the table as text -- for the ten layer shapes, nsplit 1 / 2 / 3 / 4 / 6 and the four variants what
+// mlt_launch_conv selects (kernel family <template arguments in parameter order>, threads per workgroup, grid.y, dynamic LDS bytes at patch_bytes 1024 / 32768,
+// ring kernels: the largest patch_bytes, in KiB steps, the launcher accepts) or "rejected", and mlt_conv_cfg's view per shape.  tests/test_conv_table_cpu.py
+// compares it with the text the launchers produced before they were table-driven.  Returns the length, or -1 when `cap` is too small.
+extern "C" __attribute__((visibility("default"))) int mlt_debug_conv_table(char *out, size_t cap) {
+  static const char *const kVariant[] = {"default", "dma", "latency", "centre"};
+  size_t pos = 0;
+  bool ok = out != nullptr;
+  auto put = [&](const char *fmt, auto... v) {
+    const int k = ok ? std::snprintf(out + pos, cap - pos, fmt, v...) : -1;
+    if (k < 0 || (size_t)k >= cap - pos) ok = false; else pos += (size_t)k;
+  };
+  for (const ConvRow &s : kTable) {
+    if (s.nsplit != 1 || s.variant != MLT_CONV_DEFAULT) continue;  // one fast DEFAULT row per layer shape
+    for (int exact = 0; exact < 2; ++exact) {
+      ConvCfg c{};
+      mlt_conv_cfg(s.cin, s.cout, s.stride, exact, &c);
+      put("cfg %d->%d s%d exact=%d: kc=%d ct=%d mt=%d mt_dma=%d gt=%d gt_w2=%d dma=%d lat=%d\n", s.cin, s.cout, s.stride, exact, c.kc, c.ct, c.mt, c.mt_dma, c.gt, c.gt_w2, c.dma, c.lat);
+    }
+    for (int nsplit : {1, 2, 3, 4, 6})
+      for (int variant : {MLT_CONV_DEFAULT, MLT_CONV_DMA, MLT_CONV_LATENCY, MLT_CONV_CENTRE}) {
+        put("conv %d->%d s%d nsplit=%d %s: ", s.cin, s.cout, s.stride, nsplit, kVariant[variant]);
+        const int i = select_row(s.cin, s.cout, s.stride, nsplit, variant);
+        if (i < 0) { put("%s", "rejected\n"); continue; }
+        const ConvRow &r = kRows[i];
+        if (r.ring) put("ring<%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d>", r.cin, r.cout, r.stride, (int)r.sc, r.kc, r.wcb, r.wpb, r.wc, r.wp, r.gt, r.rb, r.un, r.minw, r.nwl, r.fd);
+        else put("mfma<%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d>", r.cin, r.cout, r.stride, r.taps, (int)r.sc, r.kc, r.kn, r.wcb, r.wpb, r.wc, r.wp, r.gt, r.rb, r.un, r.minw, (int)r.dma, r.cbp, (int)r.kmaj);
+        put(" threads=%d grid_y=%d lds=%d/%d", row_threads(r), row_grid_y(r), row_lds(r, 1024, 0), row_lds(r, 32768, 0));
+        if (r.ring) {
+          int kib = kBigLds / 1024;
+          while (kib > 0 && !row_accepts(r, kib * 1024, 0)) --kib;
+          put(" max_patch=%d", kib * 1024);
+        }
+        put("%s", "\n");
+      }
+  }
+  if (!ok) return -1;
+  return (int)pos;
+}
+
 // ---- LDS out-of-range probe: chain_kernel<..., OOBZ = true> lets a tap outside the map read beyond the LDS allocation and relies on
 // the hardware returning zeros for such a DS read.  One workgroup with the chain kernels' full 160 KiB allocation reads where they do;
 // *ok = 1 iff every lane saw zeros.  Run once per context at mlt_init: a device that answers differently gets the masked kernels. ----
@@ -686,72 +603,56 @@ __global__ __launch_bounds__(64) void lds_oob_probe_kernel(int *ok) {
   const unsigned long long all = __ballot(zero);
   if (lane == 0) *ok = all == ~0ull ? 1 : 0;
 }
-hipError_t mlt_probe_lds_oob(int *d_ok, hipStream_t st) {
-  static DeviceOnce once;
-  hipError_t e = ensure_big_lds(lds_oob_probe_kernel, once);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(lds_oob_probe_kernel, dim3(1), dim3(64), 160 * 1024, st, d_ok);
-  return hipGetLastError();
-}
+hipError_t mlt_probe_lds_oob(int *d_ok, hipStream_t st) { return launch_big_lds<lds_oob_probe_kernel>(dim3(1), dim3(64), kBigLds, st, d_ok); }
 
 bool mlt_chain_supported(int c, int h) { return (c == 64 && h == 32) || (c == 128 && h == 16) || (c == 256 && h == 8); }
 bool mlt_stage_supported(int c, int h) { return (c == 128 && h == 16) || (c == 256 && h == 8); }  // whole-stage (S2) variant
 
-#ifndef CFG_CHAIN64_GT   // taps per weight step of the 64-channel chain: 1 (4-deep ring of 8 KiB steps, 9 barriers per conv) or 2 (2 x 16 KiB, 5 barriers)
-#define CFG_CHAIN64_GT 2
-#endif
-#ifndef CFG_CHAIN_FD     // fragment prefetch distance of chain_kernel (items)
-#define CFG_CHAIN_FD 2
-#endif
-#ifndef CFG_CHAIN_SPLIT  // 1: ring DMA on the first half of the waves, activation DMA on the second; 0: every wave issues both
-#define CFG_CHAIN_SPLIT 1
-#endif
-#ifndef CFG_CHAINW2_RB   // ring depth of the hi+lo-weights stage chains (32 KiB steps beside a 64 KiB sample: 2 or 3)
-#define CFG_CHAINW2_RB 3
-#endif
+// fused chain kernels: (channels, map height) -> instantiation; 512 threads, one workgroup per sample (256 channels: per two samples)
 template <class K> static hipError_t launch_chain_t(K kern, DeviceOnce &once, const ChainArgs &a, int grid_x, int threads, int lds, hipStream_t st) {
-  if (hipError_t e = ensure_big_lds(kern, once); e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid_x), dim3(threads), lds, st, a);
-  return hipGetLastError();
+  return launch_big_lds(kern, once, dim3(grid_x), dim3(threads), lds, st, a);
 }
+template <auto KERN> static hipError_t launch_chain_t(const ChainArgs &a, int grid_x, int lds, hipStream_t st) { return launch_big_lds<KERN>(dim3(grid_x), dim3(512), lds, st, a); }
 hipError_t mlt_launch_chain(int c, int h, bool with_s2, bool oob_zero, bool w2, const ChainArgs &a, int grid_x, hipStream_t st) {
-  static_assert(CFG_BIG_GT == 3 && CFG_BIG_WCB == 2 && CFG_BIG_WC == 2, "chain_kernel reads the packing of the stand-alone 128->128 / 256->256 layers");
-  constexpr int lds = 64 * 1024 + 2 * (CFG_BIG_GT * 4 * 4 * 1024);  // 64 KiB activation + two 48 KiB weight steps = all of the LDS
-  static DeviceOnce once[13];
+  // chain_kernel streams the weights as the stand-alone stride-1 layers' fast DEFAULT rows pack them
+  constexpr ConvRow r64 = kRows[find_row(64, 64, 1, 1, MLT_CONV_DEFAULT)], r128 = kRows[find_row(128, 128, 1, 1, MLT_CONV_DEFAULT)], r256 = kRows[find_row(256, 256, 1, 1, MLT_CONV_DEFAULT)];
+  static_assert(r64.kc == 64 && r64.wcb == 2 && r64.wc == 1 && r64.gt == 9, "chain_kernel<64,...> reads the packing of the stand-alone 64->64 layer");
+  static_assert(r128.kc == 64 && r128.gt == 3 && r128.wcb == 2 && r128.wc == 2 && r256.kc == 64 && r256.gt == 3 && r256.wcb == 2 && r256.wc == 2,
+                "chain_kernel reads the packing of the stand-alone 128->128 / 256->256 layers: 128-cout tiles, 64-channel chunks, 3 taps per step");
+  constexpr int lds = 64 * 1024 + 2 * (r128.gt * (r128.kc / 16) * r128.cbt() * 1024);  // 64 KiB activation + two 48 KiB weight steps = all of the LDS
   if (w2) {  // hi+lo-weights forms (MLT_MODEL_W2 packing: the fast tiling, two planes): one tap per ring step, conv padding from beyond the LDS only
     if (!oob_zero || with_s2 || a.nconv != 3) return hipErrorInvalidValue;
     // ring step = hi fp16 plane + FP8 lo plane (LO8): 8 + 4 KiB per tap (64 channels), 16 + 8 KiB (128 / 256)
     if (c == 64 && h == 32)   // 128 KiB sample + 2 steps of two fp16 planes (8 + 8 KiB)
-      return launch_chain_t(chain_kernel<64, 5, 0, 2, 4, 1, 8, 1, 2, 1, 2, 3, true, false, false, true, true, false>, once[10], a, grid_x, 512, 128 * 1024 + 2 * 16 * 1024, st);
+      return launch_chain_t<chain_kernel<64, 5, 0, 2, 4, 1, 8, 1, 2, 1, 2, 3, true, false, false, true, true, false>>(a, grid_x, 128 * 1024 + 2 * 16 * 1024, st);
     if (c == 128 && h == 16)  // 64 KiB sample + 2 ring steps + the 32 KiB e4m3 image of the sample
-      return launch_chain_t(chain_kernel<128, 4, 0, 2, 2, 2, 4, 1, 2, 1, 2, 3, true, false, true, true, true, true>, once[11], a, grid_x, 512, (64 + 2 * 24 + 32) * 1024, st);
+      return launch_chain_t<chain_kernel<128, 4, 0, 2, 2, 2, 4, 1, 2, 1, 2, 3, true, false, true, true, true, true>>(a, grid_x, (64 + 2 * 24 + 32) * 1024, st);
     if (c == 256 && h == 8)   // (64 KiB sample + 2 ring steps + the 32 KiB e4m3 image of the sample)
-      return launch_chain_t(chain_kernel<256, 3, 1, 2, 1, 2, 4, 1, 2, 1, 2, 3, true, false, true, true, true, true>, once[12], a, grid_x, 512, (64 + 2 * 24 + 32) * 1024, st);
+      return launch_chain_t<chain_kernel<256, 3, 1, 2, 1, 2, 4, 1, 2, 1, 2, 3, true, false, true, true, true, true>>(a, grid_x, (64 + 2 * 24 + 32) * 1024, st);
     return hipErrorInvalidValue;
   }
   // oob_zero: conv padding from DS reads beyond the LDS allocation (the probed default) or from zero masks; the kernels off the default path
   // (chains without the stride-2 front conv, MLT_NO_CHAIN_S2) exist in the masked form only
-  if (c == 64 && h == 32 && a.nconv == 3 && !with_s2) {  // 8 waves x (64 couts x 128 pixels), one 128 KiB sample per workgroup, 2 x 16 KiB weight ring
-    static_assert(CFG_64_WCB == 2 && CFG_64_WC == 1 && CFG_64_GT == 9, "chain_kernel<64,...> reads the packing of the stand-alone 64->64 layer");
-    constexpr int RB64 = CFG_CHAIN64_GT == 1 ? 4 : 2, lds64 = 128 * 1024 + 4 * 8 * 1024;
-    if (oob_zero) return launch_chain_t(chain_kernel<64, 5, 0, 2, 4, 1, 8, CFG_CHAIN64_GT, RB64, 1, 2, 3, true, false, false, true>, once[6], a, grid_x, 512, lds64, st);
-    return launch_chain_t(chain_kernel<64, 5, 0, 2, 4, 1, 8, CFG_CHAIN64_GT, RB64, 1, 2, 3, true, false, false, false>, once[7], a, grid_x, 512, lds64, st);
+  if (c == 64 && h == 32 && a.nconv == 3 && !with_s2) {  // 8 waves x (64 couts x 128 pixels), one 128 KiB sample per workgroup, 2 taps per weight step: 2 x 16 KiB ring, 5 barriers per conv
+    constexpr int lds64 = 128 * 1024 + 4 * 8 * 1024;
+    if (oob_zero) return launch_chain_t<chain_kernel<64, 5, 0, 2, 4, 1, 8, 2, 2, 1, 2, 3, true, false, false, true>>(a, grid_x, lds64, st);
+    return launch_chain_t<chain_kernel<64, 5, 0, 2, 4, 1, 8, 2, 2, 1, 2, 3, true, false, false, false>>(a, grid_x, lds64, st);
   }
   if (c == 128 && h == 16) {  // 8 waves x (64 couts x 64 pixels), one sample per workgroup
     if (with_s2 && a.nconv == 3) {
-      if (oob_zero) return launch_chain_t(chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, CFG_CHAIN_FD, 2, 3, true, true, true, true>, once[4], a, grid_x, 512, lds, st);
-      return launch_chain_t(chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, CFG_CHAIN_FD, 2, 3, true, true, true, false>, once[8], a, grid_x, 512, lds, st);
+      if (oob_zero) return launch_chain_t<chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, 2, 2, 3, true, true, true, true>>(a, grid_x, lds, st);
+      return launch_chain_t<chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, 2, 2, 3, true, true, true, false>>(a, grid_x, lds, st);
     }
-    if (a.nconv == 3) return launch_chain_t(chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, CFG_CHAIN_FD, 2, 3, CFG_CHAIN_SPLIT != 0>, once[0], a, grid_x, 512, lds, st);
-    if (a.nconv == 2) return launch_chain_t(chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, CFG_CHAIN_FD, 2, 2, CFG_CHAIN_SPLIT != 0>, once[1], a, grid_x, 512, lds, st);
+    if (a.nconv == 3) return launch_chain_t<chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, 2, 2, 3, true>>(a, grid_x, lds, st);
+    if (a.nconv == 2) return launch_chain_t<chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, 2, 2, 2, true>>(a, grid_x, lds, st);
   }
   if (c == 256 && h == 8) {   // 8 waves x (64 couts x 32 pixels) x 2 cout passes, two samples per workgroup
     if (with_s2 && a.nconv == 3) {
-      if (oob_zero) return launch_chain_t(chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, CFG_CHAIN_FD, 2, 3, true, true, true, true>, once[5], a, grid_x, 512, lds, st);
-      return launch_chain_t(chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, CFG_CHAIN_FD, 2, 3, true, true, true, false>, once[9], a, grid_x, 512, lds, st);
+      if (oob_zero) return launch_chain_t<chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 3, true, true, true, true>>(a, grid_x, lds, st);
+      return launch_chain_t<chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 3, true, true, true, false>>(a, grid_x, lds, st);
     }
-    if (a.nconv == 3) return launch_chain_t(chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, CFG_CHAIN_FD, 2, 3, CFG_CHAIN_SPLIT != 0>, once[2], a, grid_x, 512, lds, st);
-    if (a.nconv == 2) return launch_chain_t(chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, CFG_CHAIN_FD, 2, 2, CFG_CHAIN_SPLIT != 0>, once[3], a, grid_x, 512, lds, st);
+    if (a.nconv == 3) return launch_chain_t<chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 3, true>>(a, grid_x, lds, st);
+    if (a.nconv == 2) return launch_chain_t<chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 2, true>>(a, grid_x, lds, st);
   }
   return hipErrorInvalidValue;
 }
@@ -769,73 +670,44 @@ hipError_t mlt_launch_stem5(const Stem5Args &a, int nsplit, int grid_x, int lds,
 }
 
 hipError_t mlt_launch_block32(const Block32Args &a, bool w2, int grid_x, hipStream_t st) {
-  static DeviceOnce once[2];
-  if (w2) {  // 8 x 32 tiles: X 12 x 36, T 10 x 34 pixels at 80 B + two weight planes per conv
-    constexpr int lds = (12 * 36 + 10 * 34) * 80 + 4 * 18 * 1024;
-    if (hipError_t e = ensure_big_lds(block32_kernel<3, true>, once[1]); e != hipSuccess) return e;
-    hipLaunchKernelGGL((block32_kernel<3, true>), dim3(grid_x), dim3(512), lds, st, a);
-    return hipGetLastError();
-  }
-  constexpr int lds = (20 * 36 + 18 * 34) * 80 + 2 * 18 * 1024;
-  if (hipError_t e = ensure_big_lds(block32_kernel<4, false>, once[0]); e != hipSuccess) return e;
-  hipLaunchKernelGGL((block32_kernel<4, false>), dim3(grid_x), dim3(512), lds, st, a);
-  return hipGetLastError();
+  if (w2)  // 8 x 32 tiles: X 12 x 36, T 10 x 34 pixels at 80 B + two weight planes per conv
+    return launch_big_lds<block32_kernel<3, true>>(dim3(grid_x), dim3(512), (12 * 36 + 10 * 34) * 80 + 4 * 18 * 1024, st, a);
+  return launch_big_lds<block32_kernel<4, false>>(dim3(grid_x), dim3(512), (20 * 36 + 18 * 34) * 80 + 2 * 18 * 1024, st, a);
 }
 
 hipError_t mlt_launch_stem_block(const StemBlockArgs &a, bool w2, int grid_x, hipStream_t st) {
   // 3 raw + 2 T buffers + conv2 weights (hi+lo-weights form: its LO plane -- the hi plane lives in the consumer waves' registers) + biases +
   // border k-steps (one or two planes) = 149 / 151 KiB
   constexpr int lds = 3 * (39 * 72 * 4 + 16) + 2 * (18 * 34 * 80) + 18 * 1024 + 256 + 2 * 1024;
-  static DeviceOnce once[2];
-  if (w2) {
-    if (hipError_t e = ensure_big_lds(stem_block_kernel<true>, once[1]); e != hipSuccess) return e;
-    hipLaunchKernelGGL(stem_block_kernel<true>, dim3(grid_x), dim3(128 * CFG_SB_NWS), lds + 2 * 1024, st, a);
-    return hipGetLastError();
-  }
-  if (hipError_t e = ensure_big_lds(stem_block_kernel<false>, once[0]); e != hipSuccess) return e;
-  hipLaunchKernelGGL(stem_block_kernel<false>, dim3(grid_x), dim3(128 * CFG_SB_NWS), lds, st, a);  // one workgroup per CU, two pipeline stages inside
-  return hipGetLastError();
+  const dim3 grid(grid_x), block(128 * CFG_SB_NWS);  // one workgroup per CU, two pipeline stages inside
+  if (w2) return launch_big_lds<stem_block_kernel<true>>(grid, block, lds + 2 * 1024, st, a);
+  return launch_big_lds<stem_block_kernel<false>>(grid, block, lds, st, a);
 }
 
-template <bool F5, bool M16> static hipError_t launch_layer0_stream_t(const Layer0Args &a, int grid_x, hipStream_t st) {
-  static DeviceOnce once;
-  if (hipError_t e = ensure_big_lds(layer0_stream_kernel<F5, M16>, once); e != hipSuccess) return e;
-  hipLaunchKernelGGL((layer0_stream_kernel<F5, M16>), dim3(grid_x), dim3(1024), F5 ? MLT_L0F_LDS_BYTES : MLT_L0_LDS_BYTES, st, a);  // one persistent workgroup per CU slot
-  return hipGetLastError();
-}
 // fuse5: + layer1's stride-2 conv and shortcut as a fifth stage; mfma32: round 5's MFMA shape (MLT_TUNING=1 MLT_L0_MFMA32=1: same-box A/B; same bits).
 // The four-stage form (fuse5 = false: weight sets whose layer1 does not open on the single pass) stays on 32x32x16: its 16x16x32 build reloads three of S2's
 // weight fragments from scratch every row (S2 carries two accumulator sets; the five-stage form's register allocation comes out without that), and it
 // was the five-stage form the A/B measured.
 // xs: the five-stage 16x16x32 form that hands layer1_stream_xs_kernel the shortcut's input instead of the shortcut (a new symbol over the shared body).
 hipError_t mlt_launch_layer0_stream(const Layer0Args &a, bool fuse5, bool mfma32, bool xs, int grid_x, hipStream_t st) {
+  const dim3 grid(grid_x), block(1024);  // one persistent workgroup per CU slot
   if (xs) {
     if (!fuse5 || mfma32) return hipErrorInvalidValue;
-    static DeviceOnce once;
-    if (hipError_t e = ensure_big_lds(layer0_stream_xs_kernel, once); e != hipSuccess) return e;
-    hipLaunchKernelGGL(layer0_stream_xs_kernel, dim3(grid_x), dim3(1024), MLT_L0F_LDS_BYTES, st, a);
-    return hipGetLastError();
+    return launch_big_lds<layer0_stream_xs_kernel>(grid, block, MLT_L0F_LDS_BYTES, st, a);
   }
-  if (fuse5) return mfma32 ? launch_layer0_stream_t<true, false>(a, grid_x, st) : launch_layer0_stream_t<true, true>(a, grid_x, st);
-  return launch_layer0_stream_t<false, false>(a, grid_x, st);
+  if (fuse5) return mfma32 ? launch_big_lds<layer0_stream_kernel<true, false>>(grid, block, MLT_L0F_LDS_BYTES, st, a) : launch_big_lds<layer0_stream_kernel<true, true>>(grid, block, MLT_L0F_LDS_BYTES, st, a);
+  return launch_big_lds<layer0_stream_kernel<false, false>>(grid, block, MLT_L0_LDS_BYTES, st, a);
 }
 
 hipError_t mlt_launch_layer1_stream(const Layer1Args &a, bool mfma32, bool xs, int grid_x, hipStream_t st) {
-  static DeviceOnce once[3];
+  const dim3 grid(grid_x), block(1024);
   if (xs) {      // behind layer0_stream_xs_kernel: a.sc holds the shortcut's input, the loader waves compute the shortcut (32x32x16 form)
     if (!mfma32 || !a.w_sc || !a.bias_sc) return hipErrorInvalidValue;
-    if (hipError_t e = ensure_big_lds(layer1_stream_xs_kernel, once[2]); e != hipSuccess) return e;
-    hipLaunchKernelGGL(layer1_stream_xs_kernel, dim3(grid_x), dim3(1024), MLT_L1X_LDS_BYTES, st, a);
-    return hipGetLastError();
+    return launch_big_lds<layer1_stream_xs_kernel>(grid, block, MLT_L1X_LDS_BYTES, st, a);
   }
-  if (mfma32) {  // the default: round 5's form on v_mfma_f32_32x32x16_f16 (MLT_TUNING=1 MLT_L1_MFMA16=1 selects the other; same bits)
-    if (hipError_t e = ensure_big_lds(layer1_stream_kernel<false>, once[0]); e != hipSuccess) return e;
-    hipLaunchKernelGGL(layer1_stream_kernel<false>, dim3(grid_x), dim3(1024), MLT_L1_LDS_BYTES, st, a);
-    return hipGetLastError();
-  }
-  if (hipError_t e = ensure_big_lds(layer1_stream_kernel<true>, once[1]); e != hipSuccess) return e;
-  hipLaunchKernelGGL(layer1_stream_kernel<true>, dim3(grid_x), dim3(1024), MLT_L1_LDS_BYTES, st, a);
-  return hipGetLastError();
+  // mfma32 is the default: round 5's form on v_mfma_f32_32x32x16_f16 (MLT_TUNING=1 MLT_L1_MFMA16=1 selects the other; same bits)
+  if (mfma32) return launch_big_lds<layer1_stream_kernel<false>>(grid, block, MLT_L1_LDS_BYTES, st, a);
+  return launch_big_lds<layer1_stream_kernel<true>>(grid, block, MLT_L1_LDS_BYTES, st, a);
 }
 
 hipError_t mlt_launch_heads(const HeadArgs &a, int n, hipStream_t st) {

@@ -576,6 +576,10 @@ int mlt_abi_version(void);
  * derived.source_sig and what the Python host side checks against the tree before it uses the library ("unsigned-build!!" for a build outside build.py). */
 const char *mlt_build_signature(void);
 
+/* Debug hook (host only: no device, no context): the per-conv kernels' launch table as text -- what the library would launch for every layer shape,
+ * arithmetic and variant, and the packing view the host derives from it.  Returns the length written (NUL-terminated), or -1 when `cap` is too small. */
+int mlt_debug_conv_table(char *out, size_t cap);
+
 /* Release everything (natural home: EncCu::destroy, EncCu.cpp:160-206). NULL is allowed. */
 void mlt_shutdown(mlt_ctx *ctx);
 

@@ -9,7 +9,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 VDIR = os.path.join(ROOT, "fastintercu-vvc_amd", "_variants")
-VARIANTS = {  # name -> -D defines (the CFG_* knobs in csrc/mlt_kernels.hip); run each twice for box noise
+VARIANTS = {  # name -> -D defines (the CFG_* knobs of the kernel includes in csrc/; the per-conv tilings are rows of kRows in mlt_kernels.hip, edited there); run each twice for box noise
     "base": [],
     # round 4: taps per weight step of the exact arithmetic's per-conv kernels (SWEEP_ARGS="--weight-seed 22" = the exact 128 model, "--size 64")
     # (gte_s2_2 / gte_s2_5 / gte_s1_3: profiles/r04h_sweep_exact*.txt -- CFG_GTE_S2 = 2 became the default)
