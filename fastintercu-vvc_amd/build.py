@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmltcnn_hip.so")
 ABI_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "mltcnn.h"))
-SOURCES = ["mlt_kernels.hip", "mlt_model.cpp", "mlt_dispatch.cpp", "mlt_guards.cpp", "mlt_calibrate.cpp", "mlt_api.cpp", "mlt_pictures.cpp", "mlt_tree.cpp"]
+SOURCES = ["mlt_kernels.hip", "mlt_model.cpp", "mlt_dispatch.cpp", "mlt_guards.cpp", "mlt_calibrate.cpp", "mlt_api.cpp", "mlt_pictures.cpp", "mlt_tree.cpp", "mlt_motion.cpp"]
 SOURCE_EXTS = (".hip", ".inc", ".cpp", ".h")
 SIG_MARKER = b"MLTCNN_SOURCE_SIG="
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden",

@@ -35,6 +35,7 @@ EXPORTS = ["mlt_abi_version", "mlt_build_signature", "mlt_init", "mlt_num_device
            "mlt_picture_create", "mlt_picture_upload", "mlt_picture_wrap_device", "mlt_picture_destroy", "mlt_predict_at", "mlt_grid_positions",
            "mlt_tree_max_nodes", "mlt_tree_roots", "mlt_predict_tree", "mlt_predict_trees",
            "mlt_predict_batch_device_sweep", "mlt_predict_at_sweep", "mlt_predict_tree_sweep", "mlt_predict_trees_sweep",
+           "mlt_motion_blocks", "mlt_picture_download", "mlt_picture_compensate", "mlt_picture_predict",
            "mlt_debug_conv_table"]
 SWEEP_MAX_QPS = 32  # MLT_SWEEP_MAX_QPS
 TREES_MAX_PICTURES = 256  # MLT_TREES_MAX_PICTURES
@@ -84,6 +85,11 @@ class MltTreeConfig(C.Structure):
 class MltTreePicture(C.Structure):
     """`struct mlt_tree_picture` (include/mltcnn.h): 24 bytes -- one entry of mlt_predict_trees."""
     _fields_ = [("org", C.c_void_p), ("pred", C.c_void_p), ("poc", C.c_int32), ("qp", C.c_int32)]
+
+
+class MltMotionConfig(C.Structure):
+    """`struct mlt_motion_config` (include/mltcnn.h): 20 bytes."""
+    _fields_ = [("struct_size", C.c_uint32), ("block", C.c_int32), ("range", C.c_int32), ("lambda_", C.c_int32), ("flags", C.c_uint32)]
 
 
 # `struct mlt_tree_node` (include/mltcnn.h): 32 bytes, no padding
@@ -170,6 +176,10 @@ def load_library():
     lib.mlt_predict_trees.argtypes = [vp, i32, C.POINTER(MltTreePicture), C.POINTER(MltTreeConfig), vp, i32, vp, vp, vp, i32, vp, vp]
     lib.mlt_predict_tree_sweep.argtypes = [vp, vp, vp, C.POINTER(MltTreeConfig), vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp]
     lib.mlt_predict_trees_sweep.argtypes = [vp, i32, C.POINTER(MltTreePicture), C.POINTER(MltTreeConfig), vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp]
+    lib.mlt_motion_blocks.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+    lib.mlt_picture_download.argtypes = [vp, vp, vp, i32]
+    lib.mlt_picture_compensate.argtypes = [vp, vp, C.POINTER(MltMotionConfig), vp, vp]
+    lib.mlt_picture_predict.argtypes = [vp, vp, vp, C.POINTER(MltMotionConfig), vp, vp, vp]
     lib.mlt_synchronize.argtypes = [vp]
     lib.mlt_set_stream.argtypes = [vp, vp]
     lib.mlt_alloc_pinned.restype = vp
@@ -211,6 +221,21 @@ def tree_roots(width: int, height: int, top: int, size: int) -> np.ndarray:
     return xy
 
 
+def motion_blocks(width: int, height: int, block: int = 16):
+    """(bx, by) = the blocks per row and per column of a width x height picture cut into block x block blocks, border blocks clipped (mlt_motion_blocks; pure
+    host); (0, 0) on bad arguments."""
+    bx, by = C.c_int(0), C.c_int(0)
+    n = load_library().mlt_motion_blocks(int(width), int(height), int(block), C.byref(bx), C.byref(by))
+    return (bx.value, by.value) if n else (0, 0)
+
+
+def motion_config(block: int = 16, search_range: int = 0, lam: int = 0, flags: int = 0) -> MltMotionConfig:
+    cfg = MltMotionConfig()
+    cfg.struct_size = C.sizeof(MltMotionConfig)
+    cfg.block, cfg.range, cfg.lambda_, cfg.flags = int(block), int(search_range), int(lam), int(flags)
+    return cfg
+
+
 class Picture:
     """`mlt_picture`: one int16 luma plane in device memory, owned by the context it was made on (MltCnn.picture / MltCnn.wrap_picture)."""
 
@@ -223,6 +248,15 @@ class Picture:
         assert plane.dtype == np.int16 and plane.shape == (self.height, self.width) and plane.strides[1] == 2 and plane.strides[0] % 2 == 0
         self._ctx._check(self._ctx._lib.mlt_picture_upload(self._ctx._h, self._h, plane.ctypes.data, plane.strides[0] // 2))
         return self
+
+    def download(self, out: np.ndarray | None = None) -> np.ndarray:
+        """devices[0]'s plane -> int16 [height, width] (mlt_picture_download; after the context stream's earlier work, synchronous).  out: an int16 array of that
+        shape with unit column stride and any row stride to fill instead of a new one."""
+        if out is None:
+            out = np.zeros((self.height, self.width), np.int16)
+        assert out.dtype == np.int16 and out.shape == (self.height, self.width) and out.strides[1] == 2 and out.strides[0] % 2 == 0
+        self._ctx._check(self._ctx._lib.mlt_picture_download(self._ctx._h, self._h, out.ctypes.data, out.strides[0] // 2))
+        return out
 
     def close(self):
         if self._h and self._ctx._h:
@@ -492,6 +526,31 @@ class MltCnn:
         h = C.c_void_p()
         self._check(self._lib.mlt_picture_wrap_device(self._h, ptr, int(stride), int(width), int(height), C.byref(h)))
         return Picture(self, h, int(width), int(height), keep)
+
+    # -- prediction pictures: block motion search + compensation on the device -------------------------
+    def compensate(self, ref_pic: Picture, mv, dst_pic: Picture, block: int = 16):
+        """dst_pic <- the quarter-sample compensation of ref_pic with the field mv, int16 [by, bx, 2] {mvx, mvy} (mlt_picture_compensate; motion.compensate is the
+        rule).  Returns once mv may be reused."""
+        mv = np.ascontiguousarray(mv, np.int16)
+        bx, by = motion_blocks(dst_pic.width, dst_pic.height, block or 16)
+        assert (bx, by) == (0, 0) or mv.shape == (by, bx, 2), (mv.shape, (by, bx, 2))   # (a bad block: the library's error)
+        cfg = motion_config(block)
+        self._check(self._lib.mlt_picture_compensate(self._h, ref_pic._h, C.byref(cfg), mv.ctypes.data, dst_pic._h))
+        return dst_pic
+
+    def predict_picture(self, cur_pic: Picture, ref_pic: Picture, dst_pic: Picture, block: int = 16, search_range: int = 16, lam: int = 0,
+                        want_field: bool = True) -> dict:
+        """dst_pic <- the prediction of cur_pic from ref_pic: integer-sample block search, then compensation (mlt_picture_predict; motion.search and
+        motion.compensate are the rule).  want_field: -> {"mv": int16 [by, bx, 2], "cost": uint32 [by, bx]} and the call is synchronous; else {} and it returns
+        after enqueueing -- later calls on this context see dst_pic in stream order."""
+        cfg = motion_config(block, search_range, lam)
+        out = {}
+        if want_field:
+            bx, by = motion_blocks(dst_pic.width, dst_pic.height, block or 16)
+            out = {"mv": np.zeros((by, bx, 2), np.int16), "cost": np.zeros((by, bx), np.uint32)}
+        self._check(self._lib.mlt_picture_predict(self._h, cur_pic._h, ref_pic._h, C.byref(cfg), dst_pic._h,
+                                                  out["mv"].ctypes.data if want_field else None, out["cost"].ctypes.data if want_field else None))
+        return out
 
     def predict_at(self, size: int, org_pic: Picture, pred_pic: Picture, xy, poc, qp, want=("split", "logits", "decisions", "candidates")) -> dict:
         """CUs of size x size at xy[i] = (x, y) of the picture pair (mlt_predict_at) -> {name: array} for the names in `want`."""

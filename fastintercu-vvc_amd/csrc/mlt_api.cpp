@@ -197,7 +197,7 @@ void mlt_shutdown(mlt_ctx *ctx) {
   if (ctx->zero_page) (void)hipFree(ctx->zero_page);
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   for (int b = 0; b < 2; ++b) { if (ctx->ev_h2d[b]) (void)hipEventDestroy(ctx->ev_h2d[b]); if (ctx->ev_done[b]) (void)hipEventDestroy(ctx->ev_done[b]); }
-  for (GrowBuf *buf : {&ctx->stage, &ctx->guard_dev, &ctx->gstage, &ctx->sweep_guard_dev, &ctx->tree_dev, &ctx->h_res}) buf->release();
+  for (GrowBuf *buf : {&ctx->stage, &ctx->guard_dev, &ctx->gstage, &ctx->sweep_guard_dev, &ctx->tree_dev, &ctx->motion_dev, &ctx->h_res}) buf->release();
   if (ctx->tree_host) (void)hipHostFree(ctx->tree_host);
   if (ctx->guard_host) (void)hipHostFree(ctx->guard_host);
   if (ctx->ev_guard) (void)hipEventDestroy(ctx->ev_guard);

@@ -322,6 +322,31 @@ struct PictureGatherArgs {
   int vec_org, vec_pred;       // the plane's extent starts and ends on 16-byte boundaries: aligned 16-byte loads may be used (else 2-byte loads only)
 };
 hipError_t mlt_launch_picture_gather(const PictureGatherArgs &a, hipStream_t st);
+// ---- prediction pictures (mlt_picture_predict, mlt_picture_compensate): block motion search and quarter-sample compensation (mlt_motion_kernels.inc).  Blocks of
+// B = 1 << block_l samples, clipped at the right and bottom border; the field is [by][bx][2] int16 {mvx, mvy} in quarter samples, raster order ----
+struct MotionSearchArgs {
+  const int16_t *cur, *ref;    // sample (0, 0) of the two pictures (independent bases and pitches; 2-byte loads only)
+  long cur_pitch, ref_pitch;   // in elements
+  int width, height;           // of both
+  int block_l, range, lambda;  // candidates dx, dy in [-range, range], cost = SAD + lambda (|dx| + |dy|)
+  int bx;                      // blocks per row (the grid is bx x by workgroups)
+  int16_t *mv;                 // [by][bx][2] out, 4-byte aligned
+  uint32_t *cost;              // [by][bx] out
+};
+struct PictureCompensateArgs {
+  const int16_t *ref;          // sample (0, 0)
+  long ref_pitch;
+  int16_t *dst;                // sample (0, 0) of the prediction picture; width x height as ref
+  long dst_pitch;
+  int vec_dst;                 // dst's base and pitch are multiples of 16 bytes: whole 8-sample items are 16-byte stores
+  int width, height;
+  int block_l, bx, by;
+  int tiles_y;                 // tiles of 16 rows per block (set by the launcher)
+  const int16_t *mv;           // [by][bx][2]
+};
+int mlt_motion_search_lds(int block, int range);   // dynamic LDS bytes of motion_search_kernel: ((block + 2 range)^2 + block^2) x 2 + 32
+hipError_t mlt_launch_motion_search(const MotionSearchArgs &a, int by, hipStream_t st);
+hipError_t mlt_launch_picture_compensate(PictureCompensateArgs a, hipStream_t st);
 // ---- partition trees (mlt_predict_tree, mlt_predict_trees): the quadtree descent between two network levels (mlt_tree_kernels.inc).  The arena is LEVEL-MAJOR
 // over the pictures of the call (mlt_predict_tree: one) -- level l is one node range, picture 0's segment, then picture 1's, ...; a segment in the contract's order
 // (roots, then children in their parents' order) ----

@@ -283,6 +283,7 @@ template <int Q, class ACC = float16v> __device__ __forceinline__ half4 act_quad
 #include "mlt_layer1_kernel.inc"  // layer1_stream_kernel
 #include "mlt_tail_kernels.inc"   // heads_kernel, flat_stat / guard kernels
 #include "mlt_picture_kernels.inc"  // picture_gather_kernel, picture_gather_multi_kernel
+#include "mlt_motion_kernels.inc"  // motion_search_kernel, picture_compensate_kernel
 #include "mlt_tree_kernels.inc"  // tree_expand_kernel, tree_raster_kernel, tree_pack_kernel; tree sweeps: tree_expand_sweep_kernel, tree_sweep_raster / _rank / _pack_kernel
 
 // ---------------------------------------------------------------------------------------------
@@ -767,6 +768,24 @@ hipError_t mlt_launch_picture_gather_multi(const PictureGatherMultiArgs &a, hipS
   const size_t items = (size_t)a.c << (2 * a.s_l - 2);
   if (!items) return hipSuccess;
   hipLaunchKernelGGL(picture_gather_multi_kernel, flat_grid(items), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// one workgroup per block (mlt_motion_kernels.inc); the LDS follows (block, range) -- window and block are 81,920 bytes at (64, 64), so the launch takes the big-LDS
+// path whatever the case
+int mlt_motion_search_lds(int block, int range) { const int wn = block + 2 * range; return (wn * wn + block * block) * 2 + 32; }
+hipError_t mlt_launch_motion_search(const MotionSearchArgs &a, int by, hipStream_t st) {
+  const int block = 1 << a.block_l;
+  if (a.block_l < 3 || a.block_l > 6 || a.range < 0 || a.range > 64 || a.bx < 1 || by < 1) return hipErrorInvalidValue;
+  return launch_big_lds<motion_search_kernel>(dim3((unsigned)a.bx, (unsigned)by), dim3(256), mlt_motion_search_lds(block, a.range), st, a);
+}
+
+// one workgroup per tile of at most 16 rows x 64 columns of a block
+hipError_t mlt_launch_picture_compensate(PictureCompensateArgs a, hipStream_t st) {
+  if (a.block_l < 3 || a.block_l > 6 || a.bx < 1 || a.by < 1) return hipErrorInvalidValue;
+  const int block = 1 << a.block_l;
+  a.tiles_y = block > MLT_MC_TILE_H ? block / MLT_MC_TILE_H : 1;
+  hipLaunchKernelGGL(picture_compensate_kernel, dim3((unsigned)a.bx, (unsigned)(a.by * a.tiles_y)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

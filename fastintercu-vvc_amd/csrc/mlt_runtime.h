@@ -5,6 +5,7 @@
 //   mlt_api.cpp        init / shutdown / stream, the predict entry points, deferred prediction, confidence gate, profile
 //   mlt_pictures.cpp   device-resident pictures: create / upload / wrap / destroy, mlt_predict_at, mlt_grid_positions
 //   mlt_tree.cpp       partition trees of a picture: mlt_predict_tree, mlt_predict_trees, mlt_predict_tree_sweep, mlt_predict_trees_sweep, mlt_tree_roots, mlt_tree_max_nodes
+//   mlt_motion.cpp     prediction pictures: mlt_motion_blocks, mlt_picture_download, mlt_picture_compensate, mlt_picture_predict
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -303,6 +304,7 @@ struct mlt_ctx {
   // mlt_predict_tree's / mlt_predict_trees' device arena (Lay::TreeArena) or mlt_predict_tree_sweep's / mlt_predict_trees_sweep's (Lay::TreeSweepArena), and the pinned count
   GrowBuf tree_dev;
   int32_t *tree_host = nullptr;
+  GrowBuf motion_dev;   // mlt_picture_predict / mlt_picture_compensate (mlt_motion.cpp): this device's motion field [by][bx][2] int16, then the costs [by][bx] uint32
   std::vector<mlt_picture *> pictures;  // every picture created on / wrapped for this context (mlt_pictures.cpp); what is left is released by mlt_shutdown
   std::string err;
   bool profile = false;

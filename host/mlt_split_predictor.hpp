@@ -219,6 +219,25 @@ class SplitPredictor {
     if (!*pic && mlt_picture_create(m_ctx, width, height, pic) != MLT_OK) { *pic = nullptr; return false; }
     return mlt_picture_upload(m_ctx, *pic, plane, stride) == MLT_OK;
   }
+  // Prediction pictures made on the device (include/mltcnn.h: mlt_picture_compensate, mlt_picture_predict) for callers that hold ORIGINALS only: dst, a picture made
+  // by uploadPicture() / mlt_picture_create, receives the quarter-sample compensation of ref with the host field mv ([by][bx][2] {mvx, mvy}, quarter samples,
+  // blocks of `block` samples) -- or, predictPicture(), with the field an integer-sample search of cur in ref finds (candidates in [-range, range]^2, cost = SAD +
+  // lambda (|dx| + |dy|); mvOut [by][bx][2] / costOut [by][bx]: host arrays or nullptr, and with neither the call returns after enqueueing).  dst then serves as
+  // `pred` of predictAt / predictTree and their sweeps, in stream order.  This is a pre-analysis prediction with its own rounding, not the encoder's interpolation.
+  // false on failure, and dst is left alone.
+  bool compensatePicture(const mlt_picture *ref, const int16_t *mv, mlt_picture *dst, int block = 16) {
+    if (!m_ctx) return false;
+    mlt_motion_config cfg{};
+    cfg.struct_size = (uint32_t)sizeof cfg; cfg.block = block;
+    return mlt_picture_compensate(m_ctx, ref, &cfg, mv, dst) == MLT_OK;
+  }
+  bool predictPicture(const mlt_picture *cur, const mlt_picture *ref, mlt_picture *dst, int block = 16, int range = 16, int lambda = 0, int16_t *mvOut = nullptr,
+                      uint32_t *costOut = nullptr) {
+    if (!m_ctx) return false;
+    mlt_motion_config cfg{};
+    cfg.struct_size = (uint32_t)sizeof cfg; cfg.block = block; cfg.range = range; cfg.lambda = lambda;
+    return mlt_picture_predict(m_ctx, cur, ref, &cfg, dst, mvOut, costOut) == MLT_OK;
+  }
   // n CUs of cuw x cuw at xy[i] = {x, y} of the picture pair, one batch: splitModes[i] as predictSplitMode() returns it, and -- candOpt / decOpt != nullptr -- the
   // candidate and decision records beside it.  false on failure: every split mode -1, every candidate record keeps all classes (full RDO), no prediction in the
   // decision records.

@@ -545,6 +545,62 @@ int mlt_predict_trees_sweep(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture
                             uint8_t *leaf_maps_opt /* [n_pictures][n_qps][height/16][width/16] */,
                             float *logits_opt, int logit_stride, mlt_decision *dec_opt, mlt_candidates *cand_opt);
 
+/* ---- Prediction pictures on the device: block motion search + compensation (new exports; MLT_ABI_VERSION stays 4) ----
+ * Every whole-picture call above takes an original AND a prediction picture, and a caller that holds originals only (lookahead, pre-analysis, a GOP in HBM) has no
+ * prediction before an encode.  These calls make one on the device: from the current original and a reference picture by an integer-sample block motion search
+ * followed by quarter-sample motion compensation, or by the compensation alone from a motion field the caller already has.  The result is written into a picture
+ * made by mlt_picture_create, which every call above then takes as `pred`.  Everything is integer arithmetic with ONE stated rule, so the bytes are the same on
+ * every device and equal to the numpy restatement fastintercu-vvc_amd/motion.py.
+ * THIS IS A PRE-ANALYSIS PREDICTION WITH ITS OWN ROUNDING: both filter passes run at full int32 precision and round once, (v + 2048) >> 12.  It is NOT the
+ * encoder's interpolation with its intermediate rounding and shifts, and not its merge / skip prediction.
+ *
+ * BLOCKS    block = 8, 16, 32 or 64 luma samples (0: 16).  bx = ceil(width / block), by = ceil(height / block); block (i, j) covers x in [i * block,
+ *           min((i + 1) * block, width)) and likewise y: border blocks are clipped, every sample belongs to exactly one block.
+ * FIELD     [by][bx][2] int16 {mvx, mvy} in QUARTER luma samples, raster order.  Every int16 value is legal.
+ * REFERENCE SAMPLES are read with clamped coordinates in every rule:  R(x, y) = ref[clamp(y, 0, height - 1)][clamp(x, 0, width - 1)].
+ * COMPENSATION  with the quarter-sample luma taps
+ *             C[0] = {  0, 0,   0, 64,  0,   0, 0,  0 }
+ *             C[1] = { -1, 4, -10, 58, 17,  -5, 1,  0 }
+ *             C[2] = { -1, 4, -11, 40, 40, -11, 4, -1 }
+ *             C[3] = {  0, 1,  -5, 17, 58, -10, 4, -1 }
+ *           and, for a sample (x, y) of a block with vector (mvx, mvy):  ix = mvx >> 2, fx = mvx & 3 (arithmetic shift), likewise iy, fy;
+ *             t_j = sum_k C[fx][k] * R(x + ix + k - 3, y + iy + j - 3)   for j = 0 .. 7
+ *             v   = sum_j C[fy][j] * t_j
+ *             dst(x, y) = clip(0, 1023, (v + 2048) >> 12)                 all in int32: |v| <= 112 * 112 * 32768 < 2^31.
+ *           One formula serves all 16 fractions; for an integer vector it is clip(0, 1023, R(x + ix, y + iy)).
+ * SEARCH    per block, over all (dx, dy) in [-range, range]^2:  SAD = sum over the block's samples of |cur(x, y) - R(x + dx, y + dy)| (the int16 values as they
+ *           are, the sum in uint32), cost = SAD + lambda * (|dx| + |dy|).  The winner has the smallest key (cost, |dx| + |dy|, dy, dx), compared lexicographically
+ *           with dy and dx as signed integers.  Its vector is (4 * dx, 4 * dy), its cost the block's cost.
+ * ORDER     both calls enqueue on the context's stream(s): later calls on the same context see dst in stream order.  On a multi-device context both run on every
+ *           device and dst has its plane on each (mlt_predict_at shards over them); the bytes are identical.  Destroying a picture that an enqueued call still
+ *           reads or writes is safe: releasing a library-owned plane waits for the device, and of a wrapped picture only the handle goes.
+ * ERRORS    everything is checked before anything is enqueued; on an error dst and the host outputs stay untouched.  MLT_ERR_ARG: a NULL ctx, cfg, picture or
+ *           field; a struct_size other than sizeof(mlt_motion_config); block, range, lambda or flags out of range; a picture of another context; pictures of
+ *           unequal width or height; dst equal to ref or cur; a dst made by mlt_picture_wrap_device (that plane is the caller's and const).  No weights are needed.
+ * Not there: sub-sample search, bi-prediction, per-block reference selection, chroma, motion fields that stay in device memory across calls. */
+typedef struct mlt_motion_config {   /* 20 bytes */
+  uint32_t struct_size;  /* = sizeof; anything else -> MLT_ERR_ARG */
+  int32_t block;         /* 8 / 16 / 32 / 64; 0 => 16 */
+  int32_t range;         /* search only: candidates dx, dy in [-range, range], 0 <= range <= 64 */
+  int32_t lambda;        /* search only: cost = SAD + lambda * (|dx| + |dy|), 0 <= lambda <= 65535 */
+  uint32_t flags;        /* 0; anything else -> MLT_ERR_ARG */
+} mlt_motion_config;
+
+/* Pure host, no context: returns bx * by and writes bx / by (either may be NULL); 0 on bad arguments (a block other than 8 / 16 / 32 / 64, a width or height
+ * outside 1 .. 16384). */
+int mlt_motion_blocks(int width, int height, int block, int *bx, int *by);
+/* The inverse of mlt_picture_upload: height rows of width Pels from devices[0]'s plane, after the context stream's earlier work; synchronous.  `stride` >= width
+ * in elements; no host element outside the rows' first `width` entries is written.  Owned and wrapped pictures alike. */
+int mlt_picture_download(mlt_ctx *ctx, const mlt_picture *pic, int16_t *plane, int stride);
+/* dst <- the compensation of ref with the HOST field mv ([by][bx][2], cfg->block; range and lambda are not read).  Returns once mv may be reused, like
+ * mlt_picture_upload. */
+int mlt_picture_compensate(mlt_ctx *ctx, const mlt_picture *ref, const mlt_motion_config *cfg, const int16_t *mv /* HOST */, mlt_picture *dst);
+/* The search of cur in ref, then dst <- the compensation of ref with the found field: dst is byte for byte what mlt_picture_compensate writes for (ref, cfg,
+ * mv_out).  mv_out_opt ([by][bx][2]) and cost_out_opt ([by][bx]) are HOST arrays or NULL; with either the call is synchronous, with neither it returns after
+ * enqueueing. */
+int mlt_picture_predict(mlt_ctx *ctx, const mlt_picture *cur, const mlt_picture *ref, const mlt_motion_config *cfg, mlt_picture *dst,
+                        int16_t *mv_out_opt, uint32_t *cost_out_opt);
+
 int mlt_synchronize(mlt_ctx *ctx);
 
 /* Use an existing hipStream_t (e.g. the caller's) instead of the context's own stream; NULL switches back to a

@@ -30,6 +30,14 @@ frame, default 0 for all; an RA GOP does not code every frame at the base QP); -
 --qps 22,27,32,37 (without --tree): one map set PER QP from ONE sweep call per size (MltCnn.predict_at_sweep: the network runs once, the heads once per QP),
 written as `<out>_<S>_qp<QP>_split.npy` etc.; --qp is not consulted.  Combined with --tree it is refused: trees under several QPs are --tree-qps.
 
+--motion BLOCK,RANGE[,LAMBDA] (with any of the above): the second file is not a prediction but the REFERENCE frame, another original, and the prediction is built
+on the device before the maps or trees (MltCnn.predict_picture: integer-sample block search of the original in the reference over [-RANGE, RANGE]^2 on BLOCK x
+BLOCK blocks, cost SAD + LAMBDA (|dx| + |dy|), then quarter-sample compensation; fastintercu_vvc_amd/motion.py is the rule) -- no prediction plane crosses PCIe.
+With --frames N the second file holds N frames like the first and frame f's reference is its frame f - 1, frame 0's its frame 0 (pass the originals' file twice
+for a GOP of originals: every frame is then predicted from its predecessor and frame 0 from itself).  Without --motion nothing changes.
+
+  python tools/picture_map.py cur.npy ref.npy --motion 16,16 --synthetic 10 --tree --out maps/frame8
+
 File reading and grid logic (read_picture, grid, to_map, histogram) need neither a device nor the library; run_maps needs the MI355X."""
 import argparse
 import contextlib
@@ -114,14 +122,15 @@ def histogram(split: np.ndarray, classes: int) -> dict:
     return h
 
 
-def run_maps(m, org: np.ndarray, pred: np.ndarray, sizes, poc: int, qp: int) -> dict:
-    """m: an MltCnn with `sizes` loaded.  -> {size: {"xy", "split", "confidence", "mask"}} with the three maps shaped [height // size, width // size]."""
+def run_maps(m, org: np.ndarray, pred: np.ndarray, sizes, poc: int, qp: int, motion=None) -> dict:
+    """m: an MltCnn with `sizes` loaded.  -> {size: {"xy", "split", "confidence", "mask"}} with the three maps shaped [height // size, width // size].
+    motion: see uploaded()."""
     from fastintercu_vvc_amd import capi
     assert org.shape == pred.shape
     height, width = org.shape
-    p_org, p_pred = m.picture(width, height).upload(org), m.picture(width, height).upload(pred)
     out = {}
-    try:
+    with uploaded(m, org, pred, motion) as pics:
+        p_org, p_pred = pics[0]
         for size in sizes:
             xy = capi.grid_positions(width, height, size)
             if not len(xy):
@@ -130,20 +139,17 @@ def run_maps(m, org: np.ndarray, pred: np.ndarray, sizes, poc: int, qp: int) -> 
             r = m.predict_at(size, p_org, p_pred, xy, np.full(n, poc, np.int32), np.full(n, qp, np.int32), want=("decisions", "candidates"))
             out[size] = {"xy": xy, "split": to_map(r["decisions"]["split_mode"], width, height, size),
                          "confidence": to_map(r["decisions"]["confidence"], width, height, size), "mask": to_map(r["candidates"]["mask"], width, height, size)}
-    finally:
-        p_org.close()
-        p_pred.close()
     return out
 
 
-def run_maps_sweep(m, org: np.ndarray, pred: np.ndarray, sizes, poc: int, qps) -> dict:
+def run_maps_sweep(m, org: np.ndarray, pred: np.ndarray, sizes, poc: int, qps, motion=None) -> dict:
     """run_maps under every QP of `qps` from one sweep call per size -> {size: {qp: {"xy", "split", "confidence", "mask"}}} (a duplicate QP keeps one entry)."""
     from fastintercu_vvc_amd import capi
     assert org.shape == pred.shape
     height, width = org.shape
-    p_org, p_pred = m.picture(width, height).upload(org), m.picture(width, height).upload(pred)
     out = {}
-    try:
+    with uploaded(m, org, pred, motion) as pics:
+        p_org, p_pred = pics[0]
         for size in sizes:
             xy = capi.grid_positions(width, height, size)
             if not len(xy):
@@ -152,9 +158,6 @@ def run_maps_sweep(m, org: np.ndarray, pred: np.ndarray, sizes, poc: int, qps) -
             out[size] = {int(qp): {"xy": xy, "split": to_map(r["decisions"]["split_mode"][q], width, height, size),
                                    "confidence": to_map(r["decisions"]["confidence"][q], width, height, size),
                                    "mask": to_map(r["candidates"]["mask"][q], width, height, size)} for q, qp in enumerate(qps)}
-    finally:
-        p_org.close()
-        p_pred.close()
     return out
 
 
@@ -181,48 +184,79 @@ def tree_summary(nodes: np.ndarray) -> list:
     return [(int(s), int((nodes["size"] == s).sum()), int(((nodes["size"] == s) & (nodes["first_child"] >= 0)).sum())) for s in SIZES if (nodes["size"] == s).any()]
 
 
+def motion_references(second: np.ndarray) -> list:
+    """--motion: the reference frame of every frame out of the second file's array -- [height, width]: that frame; [frames, height, width]: frame f - 1 for
+    frame f, frame 0 for frame 0."""
+    if second.ndim == 2:
+        return [second]
+    return [second[max(f - 1, 0)] for f in range(second.shape[0])]
+
+
 @contextlib.contextmanager
-def uploaded(m, org: np.ndarray, pred: np.ndarray):
-    """The frames of org / pred ([height, width] or [frames, height, width]) as resident picture pairs [(org_pic, pred_pic), ...], closed on exit."""
+def uploaded(m, org: np.ndarray, pred: np.ndarray, motion=None):
+    """The frames of org / pred ([height, width] or [frames, height, width]) as resident picture pairs [(org_pic, pred_pic), ...], closed on exit.
+    motion = (block, range, lambda): `pred` holds REFERENCE frames instead (motion_references) and every pred_pic is built on the device from the frame's original
+    and its reference (MltCnn.predict_picture, enqueued only: the calls that follow see it in stream order)."""
     assert org.shape == pred.shape
     height, width = org.shape[-2:]
-    pics = [(m.picture(width, height).upload(o), m.picture(width, height).upload(p)) for o, p in zip(org.reshape(-1, height, width), pred.reshape(-1, height, width))]
+    held, pics = [], []
     try:
+        if motion is None:
+            for o, p in zip(org.reshape(-1, height, width), pred.reshape(-1, height, width)):
+                held += [m.picture(width, height).upload(o), m.picture(width, height).upload(p)]
+                pics.append((held[-2], held[-1]))
+        else:
+            block, search_range, lam = motion
+            for o, r in zip(org.reshape(-1, height, width), motion_references(pred)):
+                held += [m.picture(width, height).upload(o), m.picture(width, height).upload(r), m.picture(width, height)]
+                m.predict_picture(held[-3], held[-2], held[-1], block=block, search_range=search_range, lam=lam, want_field=False)
+                pics.append((held[-3], held[-1]))
         yield pics
     finally:
-        for a, b in pics:
-            a.close()
-            b.close()
+        m.synchronize()   # (a prediction may still be in flight when an error unwinds)
+        for p in held:
+            p.close()
 
 
-def run_tree(m, org: np.ndarray, pred: np.ndarray, poc: int, qp: int, min_size: int = 16) -> dict:
+def parse_motion(text: str) -> tuple:
+    """"16,16" or "16,16,4" -> (block, range, lambda): block 8 / 16 / 32 / 64, 0 <= range <= 64, 0 <= lambda <= 65535 (default 0)."""
+    try:
+        v = tuple(int(t) for t in text.split(","))
+    except ValueError:
+        raise ValueError(f"--motion {text}: want BLOCK,RANGE[,LAMBDA] as integers") from None
+    if len(v) not in (2, 3) or v[0] not in (8, 16, 32, 64) or not 0 <= v[1] <= 64 or (len(v) == 3 and not 0 <= v[2] <= 65535):
+        raise ValueError(f"--motion {text}: want BLOCK,RANGE[,LAMBDA] with BLOCK of 8,16,32,64, 0 <= RANGE <= 64, 0 <= LAMBDA <= 65535")
+    return (v[0], v[1], v[2] if len(v) == 3 else 0)
+
+
+def run_tree(m, org: np.ndarray, pred: np.ndarray, poc: int, qp: int, min_size: int = 16, motion=None) -> dict:
     """m: an MltCnn with tree_sizes(min_size) loaded -> {"nodes", "leaf_map"} (MltCnn.predict_tree)."""
     assert org.ndim == 2
-    with uploaded(m, org, pred) as pics:
+    with uploaded(m, org, pred, motion) as pics:
         return m.predict_tree(pics[0][0], pics[0][1], poc, qp, top=128, min_size=min_size, want=("leaf_map",))
 
 
-def run_trees(m, org: np.ndarray, pred: np.ndarray, poc: int, qp: int, min_size: int = 16) -> list:
+def run_trees(m, org: np.ndarray, pred: np.ndarray, poc: int, qp: int, min_size: int = 16, motion=None) -> list:
     """org / pred: [frames, height, width]; m: an MltCnn with tree_sizes(min_size) loaded -> one {"nodes", "leaf_map", "first_node"} per frame, all from ONE
     call (MltCnn.predict_trees); frame f takes poc + f."""
     assert org.ndim == 3
-    with uploaded(m, org, pred) as pics:
+    with uploaded(m, org, pred, motion) as pics:
         return m.predict_trees(pics, [poc + f for f in range(len(pics))], qp, top=128, min_size=min_size, want=("leaf_map",))
 
 
-def run_tree_sweep(m, org: np.ndarray, pred: np.ndarray, poc: int, qps, min_size: int = 16) -> list:
+def run_tree_sweep(m, org: np.ndarray, pred: np.ndarray, poc: int, qps, min_size: int = 16, motion=None) -> list:
     """m: an MltCnn with tree_sizes(min_size) loaded -> one {"nodes", "leaf_map", "first_node", "union_nodes"} per QP of `qps`, all from ONE call
     (MltCnn.predict_tree_sweep)."""
     assert org.ndim == 2
-    with uploaded(m, org, pred) as pics:
+    with uploaded(m, org, pred, motion) as pics:
         return m.predict_tree_sweep(pics[0][0], pics[0][1], poc, qps, top=128, min_size=min_size, want=("leaf_map",))
 
 
-def run_trees_sweep(m, org: np.ndarray, pred: np.ndarray, poc: int, qp_offsets, qps, min_size: int = 16) -> list:
+def run_trees_sweep(m, org: np.ndarray, pred: np.ndarray, poc: int, qp_offsets, qps, min_size: int = 16, motion=None) -> list:
     """org / pred: [frames, height, width]; m: an MltCnn with tree_sizes(min_size) loaded -> result[frame][point], each {"nodes", "leaf_map", "first_node",
     "union_nodes"}, all from ONE call (MltCnn.predict_trees_sweep); frame f takes poc + f and, under point q, QP qp_offsets[f] + qps[q]."""
     assert org.ndim == 3
-    with uploaded(m, org, pred) as pics:
+    with uploaded(m, org, pred, motion) as pics:
         return m.predict_trees_sweep(pics, [poc + f for f in range(len(pics))], list(qp_offsets), qps, top=128, min_size=min_size, want=("leaf_map",))
 
 
@@ -265,6 +299,7 @@ def parse_args(argv=None):
     ap.add_argument("--tree-qps", default=None, help="with --tree: comma-separated QPs, one tree per QP from one call (not with --frames)")
     ap.add_argument("--gop-qps", default=None, help="with --tree --frames N: comma-separated base QPs, one tree per (frame, QP) from one call")
     ap.add_argument("--qp-offsets", default=None, help="with --gop-qps: one QP offset per frame, comma-separated (default 0)")
+    ap.add_argument("--motion", default=None, help="BLOCK,RANGE[,LAMBDA]: the second file is the REFERENCE frame; the prediction is built on the device")
     args = ap.parse_args(argv)
     sizes = tuple(int(s) for s in args.sizes.split(",") if s)
     if not sizes or any(s not in SIZES for s in sizes) or (args.weights_dir is None) == (args.synthetic is None):
@@ -273,6 +308,12 @@ def parse_args(argv=None):
         ap.error("--min-size goes with --tree")
     if args.frames is not None and (not args.tree or not 1 <= args.frames <= 256):
         ap.error("--frames goes with --tree, 1 .. 256")
+    args.motion_cfg = None
+    if args.motion is not None:
+        try:
+            args.motion_cfg = parse_motion(args.motion)
+        except ValueError as e:
+            ap.error(str(e))
     args.qp_list = None
     if args.qps is not None:
         if args.tree:
@@ -334,7 +375,7 @@ def main(argv=None):
             m.set_candidate_policy(s, args.coverage, args.max_modes)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     if args.tree and args.gop_qp_list is not None:
-        res = run_trees_sweep(m, org, pred, args.poc, args.qp_offset_list, args.gop_qp_list, args.min_size)
+        res = run_trees_sweep(m, org, pred, args.poc, args.qp_offset_list, args.gop_qp_list, args.min_size, args.motion_cfg)
         for f, (off, row) in enumerate(zip(args.qp_offset_list, res)):
             for qp, t in zip(args.gop_qp_list, row):
                 save_tree(f"{args.out}_f{f}_qp{qp + off}", t)
@@ -346,14 +387,14 @@ def main(argv=None):
         m.close()
         return 0
     if args.tree and args.frames is not None:
-        for f, t in enumerate(run_trees(m, org, pred, args.poc, args.qp, args.min_size)):
+        for f, t in enumerate(run_trees(m, org, pred, args.poc, args.qp, args.min_size, args.motion_cfg)):
             save_tree(f"{args.out}_f{f}", t)
             print(f"frame {f} (poc {args.poc + f}): {len(t['nodes'])} nodes from node {t['first_node']}  " +
                   "  ".join(f"{size}: {count} ({desc} descend)" for size, count, desc in tree_summary(t["nodes"])))
         m.close()
         return 0
     if args.tree and args.tree_qp_list is not None:
-        trees = run_tree_sweep(m, org, pred, args.poc, args.tree_qp_list, args.min_size)
+        trees = run_tree_sweep(m, org, pred, args.poc, args.tree_qp_list, args.min_size, args.motion_cfg)
         for qp, t in zip(args.tree_qp_list, trees):
             save_tree(f"{args.out}_qp{qp}", t)
             print(f"qp {qp}: {len(t['nodes'])} nodes  " + "  ".join(f"{size}: {count} ({desc} descend)" for size, count, desc in tree_summary(t["nodes"])))
@@ -363,7 +404,7 @@ def main(argv=None):
         m.close()
         return 0
     if args.tree:
-        t = run_tree(m, org, pred, args.poc, args.qp, args.min_size)
+        t = run_tree(m, org, pred, args.poc, args.qp, args.min_size, args.motion_cfg)
         save_tree(args.out, t)
         for size, count, desc in tree_summary(t["nodes"]):
             print(f"size {size}: {count} nodes, {desc} descend")
@@ -372,10 +413,10 @@ def main(argv=None):
         m.close()
         return 0
     if args.qp_list is not None:
-        sweeps = run_maps_sweep(m, org, pred, sizes, args.poc, args.qp_list)
+        sweeps = run_maps_sweep(m, org, pred, sizes, args.poc, args.qp_list, args.motion_cfg)
         maps = {(s, f"_qp{qp}"): r for s, per_qp in sweeps.items() for qp, r in per_qp.items()}
     else:
-        maps = {(s, ""): r for s, r in run_maps(m, org, pred, sizes, args.poc, args.qp).items()}
+        maps = {(s, ""): r for s, r in run_maps(m, org, pred, sizes, args.poc, args.qp, args.motion_cfg).items()}
     for (s, tag), r in maps.items():
         for name in ("split", "confidence", "mask"):
             np.save(f"{args.out}_{s}{tag}_{name}.npy", r[name])
