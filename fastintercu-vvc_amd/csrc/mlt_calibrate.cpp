@@ -645,11 +645,13 @@ int load_one(mlt_ctx *ctx, int size, const void *blob, size_t bytes, const Calib
       force.no_mag_guard = !cal.want_mag;
       force.rounding = env_int("MLT_ROUNDING"); force.w2_mask = env_int("MLT_W2_MASK"); force.x_mask = env_int("MLT_X_MASK");
       force.w2_units = env_int("MLT_W2_UNITS"); force.small_prefix = env_int("MLT_SMALL_PREFIX");
+      force.x_units = env_int("MLT_X_UNITS");
       force.no_roundings = tuning_env("MLT_NO_ROUNDINGS") != nullptr; force.no_w2 = tuning_env("MLT_NO_W2") != nullptr;
       force.no_xmix = tuning_env("MLT_NO_XMIX") != nullptr; force.no_w2_units = tuning_env("MLT_NO_W2_UNITS") != nullptr;
       force.no_x_units = tuning_env("MLT_NO_X_UNITS") != nullptr; force.no_lite = tuning_env("MLT_NO_LITE") != nullptr;
       mlt::TierChoice ch;
       rc = small_mix ? mlt::search_tier_small(pricer, rules, force, st.model.n_stages, ch) : mlt::search_tier_128(pricer, rules, force, mlt::MLT_N_ROUNDINGS, ch);
+      if (rc == mlt::kTierErrIllegalForce) { ctx->err = "MLT_X_UNITS / MLT_W2_UNITS: a single-pass stride-2 conv in front of a two-plane chain"; rc = MLT_ERR_ARG; }
       if (rc) return fail(rc);
       st.calib_cus = cal.n_used; st.calib_caller_cus = cal.n_caller_used;
       st.calib_rms = ch.price.rms; st.calib_max = ch.price.max;
@@ -766,9 +768,9 @@ int mlt_calibration_set_copy(int size, int16_t *org, int16_t *pred, int32_t *poc
 }
 
 // CPU test hook of the tier search (mlt_tier_search.h; not part of include/mltcnn.h): no HIP call on this path
-int mlt_tier_search_run(int kind, int n, float tolerance, float max_frac, const int *force,
-                        int (*price_cb)(void *user, unsigned w2_units, unsigned x_units, int rounding, float *out3), void *user, int *result, float *figures) {
-  if (!price_cb || !result || !figures || n <= 0) return MLT_ERR_ARG;
+int mlt_tier_search_run_n(int kind, int n, float tolerance, float max_frac, const int *force, int n_force,
+                          int (*price_cb)(void *user, unsigned w2_units, unsigned x_units, int rounding, float *out3), void *user, int *result, float *figures) {
+  if (!price_cb || !result || !figures || n <= 0 || (force && n_force < 12)) return MLT_ERR_ARG;
   struct CbPricer : mlt::TierPricer {
     int (*cb)(void *, unsigned, unsigned, int, float *); void *user;
     int price(unsigned w2u, unsigned xu, int r, mlt::TierPrice &out) override {
@@ -788,6 +790,7 @@ int mlt_tier_search_run(int kind, int n, float tolerance, float max_frac, const 
   if (force) {
     f.rounding = force[0]; f.w2_mask = force[1]; f.x_mask = force[2]; f.w2_units = force[3]; f.small_prefix = force[4];
     f.no_roundings = force[5] != 0; f.no_w2 = force[6] != 0; f.no_xmix = force[7] != 0; f.no_w2_units = force[8] != 0; f.no_x_units = force[9] != 0; f.no_lite = force[10] != 0; f.no_mag_guard = force[11] != 0;
+    if (n_force > 12) f.x_units = force[12];
   }
   mlt::TierChoice ch;
   const int rc = kind == 0 ? mlt::search_tier_128(pricer, rules, f, n, ch) : mlt::search_tier_small(pricer, rules, f, n, ch);
@@ -795,6 +798,12 @@ int mlt_tier_search_run(int kind, int n, float tolerance, float max_frac, const 
   result[6] = ch.lite ? 1 : 0; result[7] = ch.mag_thr > 0.f ? 1 : 0;
   figures[0] = ch.price.rms; figures[1] = ch.price.max; figures[2] = ch.price.tail; figures[3] = ch.mag_thr;
   return rc;
+}
+
+// (the hook as it was before MLT_X_UNITS: force[12], the exact unit mask never forced)
+int mlt_tier_search_run(int kind, int n, float tolerance, float max_frac, const int *force,
+                        int (*price_cb)(void *user, unsigned w2_units, unsigned x_units, int rounding, float *out3), void *user, int *result, float *figures) {
+  return mlt_tier_search_run_n(kind, n, tolerance, max_frac, force, 12, price_cb, user, result, figures);
 }
 
 int mlt_arithmetic(mlt_ctx *ctx, int size, mlt_arith_info *out) {

@@ -62,6 +62,7 @@ struct TierForce {
   int w2_mask = -1;        // MLT_W2_MASK: exactly this STAGE mask in hi+lo weights, kept whatever it measures
   int x_mask = -1;         // MLT_X_MASK: exactly this stage mask exact, the others hi+lo weights
   int w2_units = -1;       // MLT_W2_UNITS: exactly this unit mask in hi+lo weights
+  int x_units = -1;        // MLT_X_UNITS: exactly this UNIT mask exact, kept whatever it measures; the other units hi+lo weights, or those of MLT_W2_UNITS among them
   int small_prefix = -1;   // MLT_SMALL_PREFIX: small models, exactly the prefix of k single-pass stages
   bool no_roundings = false, no_w2 = false, no_xmix = false, no_w2_units = false, no_x_units = false, no_lite = false;
   bool no_mag_guard = false;   // MLT_NO_MAG_GUARD: never admit a configuration behind the magnitude guard (the round-5 search)
@@ -106,6 +107,14 @@ inline bool illegal_w2_unit_drop(int unit, unsigned w2_units, unsigned x_units) 
   return (unit == 4 || unit == 6) && ((w2_units | x_units) & (1u << (unit + 1)));
 }
 
+// a forced pair of unit masks that leaves a single-pass stride-2 conv in front of a two-plane chain: the search never prices it, a switch may not ask for it
+inline bool illegal_forced_units(unsigned w2_units, unsigned x_units) {
+  for (int unit = 4; unit <= 6; unit += 2)
+    if (!((w2_units | x_units) & (1u << unit)) && illegal_w2_unit_drop(unit, w2_units, x_units)) return true;
+  return false;
+}
+static const int kTierErrIllegalForce = -2;   // returned for such a pair (no pricer code is negative; mlt_load_weights reports MLT_ERR_ARG)
+
 // The 128 x 128 model.  n_roundings: realisations of the tap-diffused rounding the packer offers (mlt_model.h: MLT_N_ROUNDINGS).
 inline int search_tier_128(TierPricer &pr, const TierRules &R, const TierForce &F, int n_roundings, TierChoice &out) {
   out = TierChoice();
@@ -131,6 +140,7 @@ inline int search_tier_128(TierPricer &pr, const TierRules &R, const TierForce &
   if ((rc = price(0, 0, 0, P))) return rc;
   int r = 0;
   const bool force_mask = F.w2_mask >= 0, force_x = F.x_mask >= 0, force_units = F.w2_units >= 0, force_rounding = F.rounding >= 0;
+  const bool force_xu = F.x_units >= 0;
   // 1. the single pass with another REALISATION of the weights' rounding (draws of one error distribution: a set a little over the line may
   //    have one under it); none admitted -> the lower tiers are searched on the realisation that came closest
   if ((!admit(P) || force_rounding) && !F.no_roundings && !force_mask) {
@@ -168,7 +178,15 @@ inline int search_tier_128(TierPricer &pr, const TierRules &R, const TierForce &
     }
   }
   // 3. the tier below exact: some stages exact, the others hi+lo weights -- cheapest first; then the hi+lo stages behind them dropped greedily
-  if (!ok && !F.no_w2 && !F.no_xmix && (!force_mask || force_x)) {
+  if (!ok && !F.no_w2 && !F.no_xmix && force_xu) {  // a forced UNIT mask: the one state step 5 alone reaches otherwise (an exact chain behind a hi+lo-weights stride-2 conv)
+    const unsigned fx = (unsigned)F.x_units & 0xFFu;
+    if (fx != 0 && fx != 0xFFu) {
+      const unsigned fw = (force_units ? (unsigned)F.w2_units & 0xFFu : units_of_stages(stages_of_units(0xFFu & ~fx))) & ~fx;
+      if (illegal_forced_units(fw, fx)) return kTierErrIllegalForce;
+      if ((rc = price(fw, fx, r, P))) return rc;
+      ok = true; w2u = fw; xu = fx;
+    }
+  } else if (!ok && !F.no_w2 && !F.no_xmix && (!force_mask || force_x)) {
     for (int k = 0; k < 11 && !ok; ++k) {
       const unsigned xm = force_x ? ((unsigned)F.x_mask & 0xFu) : kXStageOrder[k];
       if (xm == 0 || xm == 0xFu) break;
@@ -190,7 +208,7 @@ inline int search_tier_128(TierPricer &pr, const TierRules &R, const TierForce &
     }
   }
   // 4. ... at launch-unit granularity: drop the hi+lo weights unit by unit, the largest saving first
-  if (ok && !F.no_w2_units && ((!force_mask && !force_x) || force_units)) {
+  if (ok && !F.no_w2_units && !(force_xu && xu) && ((!force_mask && !force_x) || force_units)) {
     if (force_units) {
       w2u = (unsigned)F.w2_units & 0xFFu & ~xu;
       if ((rc = price(w2u, xu, r, P))) return rc;
@@ -208,7 +226,7 @@ inline int search_tier_128(TierPricer &pr, const TierRules &R, const TierForce &
     }
   }
   // 5. ... and the exact units back to their hi+lo-weights form, unit by unit
-  if (ok && xu && !F.no_x_units && !force_x && !force_mask && !force_units) {
+  if (ok && xu && !F.no_x_units && !force_x && !force_xu && !force_mask && !force_units) {
     TierPrice kept = P;
     for (int k = 0; k < 8; ++k) {
       const unsigned bit = 1u << kXUnitDrop[k];
@@ -222,7 +240,7 @@ inline int search_tier_128(TierPricer &pr, const TierRules &R, const TierForce &
   (void)x_mask;
   if (ok) { out.w2 = true; out.w2_units = w2u; out.x_units = xu; out.price = figures(P); out.mag_thr = guarded ? thr : 0.f; out.mag_flag = guarded ? flag : 0.f; return 0; }
   // 6. (round 5) the exact-lite arithmetic everywhere, before the exact one
-  if (!F.no_lite && !force_mask && !force_x) {
+  if (!F.no_lite && !force_mask && !force_x && !force_xu) {
     TierPrice PL;
     ++out.priced;
     rc = pr.price_lite(PL);
@@ -288,7 +306,11 @@ inline int search_tier_small(TierPricer &pr, const TierRules &R, const TierForce
 //   unchanged; out arrives zeroed, so a callback that writes the first three figures prices a tier without a magnitude guard); the exact-lite tier is
 //   priced as price_cb(user, ~0u, ~0u, 0, out), where a NEGATIVE return means "no such tier"
 //   force[12] = {rounding, w2_mask, x_mask, w2_units, small_prefix, no_roundings, no_w2, no_xmix, no_w2_units, no_x_units, no_lite, no_mag_guard}; NULL = nothing forced
+//   mlt_tier_search_run_n: the same with n_force >= 12 entries of force[]; entry 12 = x_units (MLT_X_UNITS), read only when it is there
 //   result[8] <- {exact, w2, w2_units, x_units, rounding, priced, lite, behind the magnitude guard}; figures[4] <- {rms, max, tail, magnitude threshold} of the choice
 extern "C" int mlt_tier_search_run(int kind, int n, float tolerance, float max_frac, const int *force,
                                    int (*price_cb)(void *user, unsigned w2_units, unsigned x_units, int rounding, float *out3), void *user,
                                    int *result, float *figures);
+extern "C" int mlt_tier_search_run_n(int kind, int n, float tolerance, float max_frac, const int *force, int n_force,
+                                     int (*price_cb)(void *user, unsigned w2_units, unsigned x_units, int rounding, float *out3), void *user,
+                                     int *result, float *figures);

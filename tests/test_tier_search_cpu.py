@@ -24,6 +24,7 @@ def run(pkg):
     pkg.build.build_lib()
     lib = pkg.capi.load_library()
     lib.mlt_tier_search_run.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int), CB, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]
+    lib.mlt_tier_search_run_n.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int), C.c_int, CB, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]
 
     def go(kind, n, table, default=BAD, force=None, max_frac=0.0, fail_at=None, lite=BAD):
         """table: {(w2_units, x_units, rounding): (rms, max, tail)} or a callable; lite: the figures of the exact-lite tier (priced as w2 = x = ~0, recorded as
@@ -47,9 +48,14 @@ def run(pkg):
         res, fig = (C.c_int * 8)(), (C.c_float * 4)()
         f = None
         if force:
-            f = (C.c_int * 12)(*[force.get(k, d) for k, d in (("rounding", -1), ("w2_mask", -1), ("x_mask", -1), ("w2_units", -1), ("small_prefix", -1),
-                                                            ("no_roundings", 0), ("no_w2", 0), ("no_xmix", 0), ("no_w2_units", 0), ("no_x_units", 0), ("no_lite", 0), ("no_mag_guard", 0))])
-        rc = lib.mlt_tier_search_run(kind, n, TOL, max_frac, f, CB(cb), None, res, fig)
+            f = (C.c_int * 13)(*[force.get(k, d) for k, d in (("rounding", -1), ("w2_mask", -1), ("x_mask", -1), ("w2_units", -1), ("small_prefix", -1),
+                                                            ("no_roundings", 0), ("no_w2", 0), ("no_xmix", 0), ("no_w2_units", 0), ("no_x_units", 0), ("no_lite", 0), ("no_mag_guard", 0),
+                                                            ("x_units", -1))])
+        # (force[12]: the hook as it was; with x_units: the longer array through mlt_tier_search_run_n)
+        if force and "x_units" in force:
+            rc = lib.mlt_tier_search_run_n(kind, n, TOL, max_frac, f, 13, CB(cb), None, res, fig)
+        else:
+            rc = lib.mlt_tier_search_run(kind, n, TOL, max_frac, f, CB(cb), None, res, fig)
         return dict(rc=rc, exact=res[0], w2=res[1], w2_units=res[2], x_units=res[3], rounding=res[4], priced=res[5], lite=res[6], guarded=res[7], rms=fig[0], max=fig[1], tail=fig[2],
                     mag_thr=fig[3]), calls
     return go
@@ -183,6 +189,51 @@ def test_forced_masks_are_kept_whatever_they_measure(run):
     assert calls[-1] == (0x11, 0, 0) and r["w2_units"] == 0x11
     r, calls = run(0, 6, {}, force={"x_mask": 0x2, "no_roundings": 1})
     assert calls[-1] == (units(0xD), units(0x2), 0) and (r["w2_units"], r["x_units"]) == (units(0xD), units(0x2))
+
+
+def test_forced_exact_unit_mask(run):
+    """MLT_X_UNITS: exactly this UNIT mask exact, kept whatever it measures -- the state only step 5 reaches otherwise (an exact chain behind a hi+lo-weights
+    stride-2 conv of the same stage).  Reached like MLT_X_MASK, once the single pass and the fifteen hi+lo-weights subsets have admitted nothing; never refined."""
+    pre = [(0, 0, 0)] + [(units(m), 0, 0) for m in W2_ORDER]
+    # seed 22's shape: layer1's chain, layer2 and layer3 exact, layer0 and layer1's stride-2 conv in hi+lo weights
+    r, calls = run(0, 6, {}, force={"x_units": 0xF8, "w2_units": 0x07, "no_roundings": 1})
+    assert calls == pre + [(0x07, 0xF8, 0)] and (r["rc"], r["exact"], r["w2"], r["w2_units"], r["x_units"], r["lite"]) == (0, 0, 1, 0x07, 0xF8, 0)
+    # MLT_W2_UNITS is taken without the exact units
+    r, calls = run(0, 6, {}, force={"x_units": 0xF8, "w2_units": 0xFF, "no_roundings": 1})
+    assert calls[-1] == (0x07, 0xF8, 0) and (r["w2_units"], r["x_units"]) == (0x07, 0xF8)
+    # without it: every other unit of the stages that are not exact throughout
+    r, calls = run(0, 6, {}, force={"x_units": 0x54, "no_roundings": 1})
+    assert calls == pre + [(0xAB, 0x54, 0)] and (r["w2_units"], r["x_units"]) == (0xAB, 0x54)
+    r, calls = run(0, 6, {}, force={"x_units": 0x30, "no_roundings": 1})
+    assert calls[-1] == (0xCF, 0x30, 0) and (r["w2_units"], r["x_units"]) == (0xCF, 0x30)
+    # single-pass units beside it, where they are legal: layer0 and layer1's stride-2 conv on the single pass
+    r, calls = run(0, 6, {}, force={"x_units": 0xF8, "w2_units": 0, "no_roundings": 1})
+    assert calls[-1] == (0, 0xF8, 0) and (r["w2"], r["w2_units"], r["x_units"]) == (1, 0, 0xF8)
+    # kept whatever it measures, and none of the refinements (steps 4 and 5) runs behind it -- even where every one of them would be admitted
+    r, calls = run(0, 6, lambda w, x, rr: BAD if x == 0 else GOOD, force={"x_units": 0xF8, "w2_units": 0x07, "no_roundings": 1})
+    assert calls == pre + [(0x07, 0xF8, 0)] and (r["w2_units"], r["x_units"]) == (0x07, 0xF8) and abs(r["rms"] - GOOD[0]) < 1e-9
+    # reached only when steps 1 and 2 admit nothing
+    r, calls = run(0, 6, {(0, 0, 0): GOOD}, force={"x_units": 0xF8})
+    assert calls == [(0, 0, 0)] and (r["w2"], r["x_units"]) == (0, 0)
+    r, calls = run(0, 6, {(units(0x2), 0, 0): GOOD}, force={"x_units": 0xF8, "no_roundings": 1, "no_w2_units": 1})
+    assert (r["w2_units"], r["x_units"]) == (units(0x2), 0)
+    # the empty and the full mask force nothing: the model runs exact, as under MLT_X_MASK = 0 / 15
+    for m in (0, 0xFF):
+        r, calls = run(0, 6, {}, force={"x_units": m, "no_roundings": 1})
+        assert (r["rc"], r["exact"], r["x_units"]) == (0, 1, 0) and calls == pre
+
+
+def test_forced_exact_unit_mask_refuses_the_illegal_pair(run):
+    """A single-pass stride-2 conv of layer2 / layer3 in front of a two-plane chain is the pair illegal_w2_unit_drop keeps the search from: a forced mask that
+    asks for it is refused (before it is priced), with a code of its own."""
+    pre = 1 + 15
+    for x, w in ((0x20, 0), (0x80, 0x0F), (0xA8, 0x03), (0x08, 0x20), (0x20, 0x40)):
+        r, calls = run(0, 6, {}, force={"x_units": x, "w2_units": w, "no_roundings": 1})
+        assert r["rc"] == -2 and len(calls) == pre and all(c[1] == 0 for c in calls), (x, w, r)
+    # the same chains with their stride-2 conv on two planes, or the stride-2 conv alone in front of a single-pass chain, are legal
+    for x, w in ((0x20, 0x10), (0x30, 0), (0x80, 0x40), (0x10, 0), (0x40, 0x03), (0x08, 0)):
+        r, calls = run(0, 6, {}, force={"x_units": x, "w2_units": w, "no_roundings": 1})
+        assert r["rc"] == 0 and calls[-1] == (w, x, 0) and (r["w2_units"], r["x_units"]) == (w, x), (x, w, r)
 
 
 def test_small_models_prefixes_then_layer0_variants(run):
