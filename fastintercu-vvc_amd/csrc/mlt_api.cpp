@@ -357,10 +357,10 @@ static int predict_batch_single(mlt_ctx *ctx, int n, int size, const int16_t *or
     HIP_TRY(ctx, hipEventSynchronize(ctx->ev_done[b]));
     if (guards) {
       const int k = *gs[b].h_count;
-      if (k < 0 || k > pend_c[b]) { ctx->err = "guard: bad flagged-CU count"; return MLT_ERR_HIP; }
+      int r = check_flagged_count(ctx, k, pend_c[b]);
+      if (r) return r;
       if (k > 0) {  // the set's inputs are still in place (the next H2D into it is issued after this flush)
-        int r = guard_fixup_async(ctx, *st, k, io_of(set_of(b)), gs[b]);
-        if (r) return r;
+        if ((r = guard_fixup_async(ctx, *st, k, io_of(set_of(b)), gs[b]))) return r;
         if ((r = fetch(b, pend_c[b]))) return r;
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       }
@@ -585,9 +585,8 @@ int deferred_guard_fixup(mlt_ctx *ctx, SizeState *st, Deferred &df, int b) {
   // (the set's two selection counters came back with the results: the launch counted on one and zeroed the other -- GuardSlot.phase -- so their sum is the count)
   const int k = d.g.h_count[0] + d.g.h_count[1];
   if (k == 0) return MLT_OK;
-  if (k < 0 || k > df.n_launched[b] || !st->guards()) { ctx->err = "guard: bad flagged-CU count"; return MLT_ERR_HIP; }
-  int rc = guard_fixup_async(ctx, *st, k, d.io, d.g);
-  if (rc) return rc;
+  int rc = check_flagged_count(ctx, st->guards() ? k : -1, df.n_launched[b]);   // (a non-zero count for a size that has no guards any more is as bad)
+  if (rc || (rc = guard_fixup_async(ctx, *st, k, d.io, d.g))) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(df.h_out + (size_t)b * df.out.bytes(), df.d_out + (size_t)b * df.out.bytes(), df.out.fetch_bytes(df.has_cand[b]), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return MLT_OK;

@@ -260,8 +260,8 @@ struct CalibSession {
     t.d_lg = t.d_mag + count;
     return MLT_OK;
   }
-  // which CUs of t[first ..) the flat-content guard re-evaluates exactly at run time (flat_stat_kernel's statistic, guard_select_kernel's
-  // thresholds): those never see the arithmetic being priced
+  // which CUs of t[first ..) the flat-content guard re-evaluates exactly at run time (flat_stat_kernel's statistic under the flat test of guard_rule,
+  // mlt_tail_kernels.inc -- its one host-side restatement, at the thresholds of guard_thresholds): those never see the arithmetic being priced
   int drop_flat(Set &t, int first, int div = 8, std::vector<char> *mask = nullptr) {
     const int S = st.size, cnt = t.n - first;
     const size_t cs = (size_t)S * S;

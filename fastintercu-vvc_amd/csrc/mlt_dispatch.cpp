@@ -668,10 +668,9 @@ int run_network(mlt_ctx *ctx, SizeState &st, const NetCfg &c, int n, const PassI
       ha.cand = io.cand; ha.cand_cov = st.cand_cov; ha.cand_max = st.cand_max;
       const GuardTail *tail = go.tail;
       if (tail && (n == 1 || tail->next)) {
-        ha.g_conf_band = tail->conf_band; ha.g_cand_band = tail->cand_band;
+        ha.rule = tail->rule;
+        ha.g_count = tail->count; ha.g_idx = tail->idx; ha.g_flat = tail->flat;
         ha.g_next = tail->next;   // (NULL: mlt_predict's slot -- one CU, the count is set outright)
-        ha.g_count = tail->count; ha.g_idx = tail->idx; ha.g_flat = tail->flat; ha.g_flat_thr = tail->flat_thr; ha.g_near_thr = tail->near_thr; ha.g_margin = tail->margin;
-        ha.g_mag_thr = tail->mag_thr;
       }
       hipEvent_t e0 = nullptr, e1 = nullptr;
       if (io.sweep.n_qps > 0) {   // QP sweep: the same arguments, the heads under every point (fix-up mode: io.sweep.idx)

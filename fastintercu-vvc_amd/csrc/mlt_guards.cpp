@@ -1,10 +1,13 @@
 // mlt_guards.cpp -- the parity guards of the host runtime (include/mltcnn.h: flat guard, decision guard, magnitude guard).
 #include "mlt_runtime.h"
 
-// ---- parity guards (include/mltcnn.h: flat guard, decision guard, magnitude guard) ---------------------------------
-// Per batch: [flat_stat_kernel] -> fast network, whose heads kernel ends with the selection (an unordered list of the flagged CUs + their count; mlt_predict's one CU
-// likewise) -> 4-byte D2H of the count.  MLT_GUARD_SELECT_KERNEL: the selection as guard_select_kernel, a launch of its own (ascending list) -- the A/B form.  Once
-// the host knows the count k it enqueues, for k > 0: gather of the flagged CUs' planes -> exact network on k CUs -> scatter of their results over the fast ones.
+// ---- parity guards ---------------------------------
+// A guarded pass: [flat_stat_kernel] -> fast network, whose heads kernel ends with the selection (an unordered list of the flagged CUs + their count) -> 4-byte D2H
+// of the count.  Which CUs are flagged is decided by ONE device function (mlt_tail_kernels.inc: guard_rule) under the size's GuardRule (guard_thresholds).  The
+// pass itself has three forms: run_selecting -- batches (run_fast_async) and QP sweeps (run_checked_sweep) on their slot's counter pair; mlt_predict's one CU, whose
+// result copy carries the count (g.single); and MLT_GUARD_SELECT_KERNEL, the selection as guard_select_kernel, a launch of its own (ascending list) -- the A/B
+// form.  Once the host knows the count k (check_flagged_count) it enqueues, for k > 0: gather of the flagged CUs' planes (gather_flagged) -> exact network on k
+// CUs -> scatter of their results over the fast ones (sweeps: the exact pass's heads step writes them in place).
 
 int guard_slot(mlt_ctx *ctx, int which, int n, int nl, GuardSlot *g) {
   Lay::GuardLay &lay = ctx->guard_lay;
@@ -18,17 +21,46 @@ int guard_slot(mlt_ctx *ctx, int which, int n, int nl, GuardSlot *g) {
 
 namespace {
 
-// the thresholds of the size's guards: what the selection -- as a tail of the heads kernel or as guard_select_kernel -- compares against (no pointers yet)
-GuardTail guard_thresholds(const mlt_ctx *ctx, const SizeState &st) {
+// the thresholds of the size's guards: what the selection compares against
+GuardRule guard_thresholds(const mlt_ctx *ctx, const SizeState &st) {
   const int quads = st.size * st.size / 4;
-  GuardTail t{};
-  t.flat_thr = quads / st.flat_div;  // >= 1/8 (tiers behind the magnitude guard, exact-lite tier: 1/16) of the quads exactly flat (constant / exactly linear in both planes)
-  t.near_thr = quads / 2;            // or >= 1/2 of them near-flat (mlt_kernels.h: MLT_FLAT_RANGE)
-  t.margin = st.margin_guard ? st.guard_margin : 0.f;
-  t.mag_thr = st.mag_thr;
-  t.conf_band = st.conf_band(ctx->tolerance);
-  t.cand_band = st.cand_band(ctx->tolerance);
-  return t;
+  GuardRule r{};
+  r.flat_thr = quads / st.flat_div;  // >= 1/8 (tiers behind the magnitude guard, exact-lite tier: 1/16) of the quads exactly flat (constant / exactly linear in both planes)
+  r.near_thr = quads / 2;            // or >= 1/2 of them near-flat (mlt_kernels.h: MLT_FLAT_RANGE)
+  r.margin = st.margin_guard ? st.guard_margin : 0.f;
+  r.mag_thr = st.mag_thr;
+  r.conf_band = st.conf_band(ctx->tolerance);
+  r.cand_band = st.cand_band(ctx->tolerance);
+  return r;
+}
+
+// The size's main arithmetic on n CUs with the selection as the tail of its heads kernel, on the slot's counter pair: an unordered list of the flagged CUs through
+// an atomic append on a counter that is zero on entry; the launch zeroes the slot's OTHER counter for the next one (whose predecessor's count has left the device
+// by then: same stream).  Then the 4-byte copy of the count to g.h_count.  (A first version counted finished workgroups to let the last one publish and re-arm a
+// single counter: 4096 same-address atomics and release fences made the heads launch 0.123 ms instead of 0.030 -- more than the selection launch it saved.)
+int run_selecting(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io, const GuardSlot &g) {
+  const GuardTail tail{guard_thresholds(ctx, st), g.d.count + *g.phase, g.d.idx, st.flat_guard ? g.d.flat : nullptr, g.d.count + (*g.phase ^ 1)};
+  GuardOut go;
+  go.d_flat = tail.flat; go.tail = &tail;
+  if (const int rc = run_network(ctx, st, st.main_cfg(), n, io, go)) {
+    // a pass that failed (e.g. no memory for the workspace of an oversized batch -- the caller may come back with a smaller one) may or may not have run its heads
+    // kernel: both counters back to zero, the phase stays -- whichever counter the next launch counts on is zero on entry
+    (void)hipMemsetAsync(g.d.count, 0, 8, ctx->stream);
+    return rc;
+  }
+  *g.phase ^= 1;
+  HIP_TRY(ctx, hipMemcpyAsync(g.h_count, tail.count, 4, hipMemcpyDeviceToHost, ctx->stream));
+  return MLT_OK;
+}
+
+// The k flagged CUs idx[0 .. k) of a pass, out of its planes into the dense staging set gs, their poc and qp beside them.
+int gather_flagged(mlt_ctx *ctx, int S, const Planes &pl, const int32_t *poc, const int32_t *qp, const int32_t *idx, int k, const StageSet::Ptrs &gs) {
+  GuardGatherArgs ga{};
+  pl.fill(ga);
+  ga.poc = poc; ga.qp = qp; ga.idx = idx; ga.k = k; ga.s_l = ilog2(S);
+  ga.g_org = gs.d_org; ga.g_pred = gs.d_pred; ga.g_poc = gs.d_poc; ga.g_qp = gs.d_qp;
+  HIP_TRY(ctx, mlt_launch_guard_gather(ga, ctx->stream));
+  return MLT_OK;
 }
 
 }  // namespace
@@ -38,49 +70,30 @@ GuardTail guard_thresholds(const mlt_ctx *ctx, const SizeState &st) {
 // caller then re-evaluates them with guard_fixup_async.  io.logits may be NULL.
 int run_fast_async(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io, const GuardSlot &g) {
   if (!st.guards()) return run_network(ctx, st, st.main_cfg(), n, io);
-  GuardTail tail = guard_thresholds(ctx, st);
   int rc;
   PassIO fast = io;
   if (!fast.logits && st.margin_guard) fast.logits = g.d.lg;
   GuardOut go;
   go.d_flat = st.flat_guard ? g.d.flat : nullptr;
-  tail.idx = g.d.idx; tail.flat = go.d_flat;
   if (g.single && n == 1) {
     // one CU (mlt_predict's captured graph): the selection is a tail of the heads kernel -- no guard_select launch, no memset of the
     // statistic (the tail clears it for the next call; it is only consumed when the first kernel is the one that produces it: aligned planes,
     // S >= 64 -- else flat_stat_kernel overwrites it), no separate copy of the count (the caller's result copy carries it)
-    tail.count = g.d.count;
+    const GuardTail tail{guard_thresholds(ctx, st), g.d.count, g.d.idx, go.d_flat, nullptr};
     go.tail = &tail; go.flat_is_clear = true;
     return run_network(ctx, st, st.main_cfg(), 1, fast, go);
   }
-  if (!ctx->guard_select_kernel && g.phase) {
-    // round 6: the selection is a tail of the heads kernel for batches as well -- an unordered list of the flagged CUs through an atomic append on a counter that is
-    // zero on entry; the launch zeroes the slot's OTHER counter for the next one (whose predecessor's count has left the device by then: same stream).  One launch and
-    // one launch gap less per step.  (A first version counted finished workgroups to let the last one publish and re-arm a single counter: 4096 same-address atomics
-    // and release fences made the heads launch 0.123 ms instead of 0.030 -- more than the launch it saved.)
-    tail.count = g.d.count + *g.phase; tail.next = g.d.count + (*g.phase ^ 1);
-    go.tail = &tail;
-    if ((rc = run_network(ctx, st, st.main_cfg(), n, fast, go))) {
-      // a pass that failed (e.g. no memory for the workspace of an oversized batch -- the caller may come back with a smaller one) may or may not have run its heads
-      // kernel: both counters back to zero, the phase stays -- whichever counter the next launch counts on is zero on entry
-      (void)hipMemsetAsync(g.d.count, 0, 8, ctx->stream);
-      return rc;
-    }
-    *g.phase ^= 1;
-    HIP_TRY(ctx, hipMemcpyAsync(g.h_count, tail.count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    return MLT_OK;
-  }
+  if (!ctx->guard_select_kernel && g.phase) return run_selecting(ctx, st, n, fast, g);   // (one launch and one launch gap less per step than a selection launch)
   go.d_mag = st.mag_thr > 0.f ? g.d.mag : nullptr;
   if ((rc = run_network(ctx, st, st.main_cfg(), n, fast, go))) return rc;
   GuardSelectArgs sa{};
-  sa.mag = go.d_mag; sa.mag_thr = tail.mag_thr;
+  sa.rule = guard_thresholds(ctx, st);
+  sa.mag = go.d_mag;
   sa.flat = go.d_flat;
   sa.logits = st.margin_guard ? fast.logits : nullptr;
   sa.idx = g.d.idx; sa.count = g.d.count; sa.n = n; sa.n_logits = st.model.n_logits;
   sa.head_off = st.head_off(); sa.head_classes = st.head_classes();
-  sa.flat_thr = tail.flat_thr; sa.near_thr = tail.near_thr; sa.margin = tail.margin;
-  sa.min_conf = st.min_conf; sa.conf_band = tail.conf_band;
-  sa.cand_cov = st.cand_cov; sa.cand_max = st.cand_max; sa.cand_band = tail.cand_band;
+  sa.min_conf = st.min_conf; sa.cand_cov = st.cand_cov; sa.cand_max = st.cand_max;
   Launch L{ctx};
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if ((rc = L.prof_begin("guard_select", 0.0, 0.0, e0, e1))) return rc;
@@ -97,11 +110,7 @@ int guard_fixup_async(mlt_ctx *ctx, SizeState &st, int k, const PassIO &io, cons
   int rc = ctx->gstage.reserve(ctx, lay.bytes(), "guard staging");
   if (rc) return rc;
   const StageSet::Ptrs gs = lay.at(ctx->gstage.p);
-  GuardGatherArgs ga{};
-  io.pl.fill(ga);
-  ga.poc = io.poc; ga.qp = io.qp; ga.idx = g.d.idx; ga.k = k; ga.s_l = ilog2(S);
-  ga.g_org = gs.d_org; ga.g_pred = gs.d_pred; ga.g_poc = gs.d_poc; ga.g_qp = gs.d_qp;
-  HIP_TRY(ctx, mlt_launch_guard_gather(ga, ctx->stream));
+  if ((rc = gather_flagged(ctx, S, io.pl, io.poc, io.qp, g.d.idx, k, gs))) return rc;
   // (the re-run's heads kernel applies the size's confidence gate to the gathered split modes and fills the flagged CUs' records -- decision and candidate -- from the exact logits)
   rc = run_network(ctx, st, st.exact_cfg(), k, PassIO{Planes::dense(gs.d_org, gs.d_pred, S), gs.d_poc, gs.d_qp, gs.d_split, gs.d_lg, gs.d_dec, gs.d_cand});
   if (rc) return rc;
@@ -170,7 +179,7 @@ int run_checked(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io) {
   if ((rc = run_fast_async(ctx, st, n, io, g)) || !guards) return rc;
   if ((rc = wait_count(ctx, st, n))) return rc;
   const int k = *g.h_count;
-  if (k < 0 || k > n) { ctx->err = "guard: bad flagged-CU count"; return MLT_ERR_HIP; }
+  if ((rc = check_flagged_count(ctx, k, n))) return rc;
   return k ? guard_fixup_async(ctx, st, k, io, g) : MLT_OK;
 }
 
@@ -186,40 +195,22 @@ int run_checked_sweep(mlt_ctx *ctx, SizeState &st, int n, const PassIO &io) {
   int rc;
   if ((rc = ctx->sweep_guard_dev.reserve(ctx, lay.bytes(), "sweep guard slot", true))) return rc;   // (the counters must start at zero)
   if (!ctx->guard_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->guard_host, 64, hipHostMallocDefault));
-  const Lay::GuardFields::Ptrs d = lay.at(ctx->sweep_guard_dev.p);
-  uint32_t *d_mask = lay.mask.in<uint32_t>(ctx->sweep_guard_dev.p);
-  int32_t *h_count = ctx->guard_host + 2;
-  GuardTail tail = guard_thresholds(ctx, st);
-  GuardOut go;
-  go.d_flat = st.flat_guard ? d.flat : nullptr;
-  tail.idx = d.idx; tail.flat = go.d_flat;
-  tail.count = d.count + ctx->sweep_phase; tail.next = d.count + (ctx->sweep_phase ^ 1);
-  go.tail = &tail;
+  const GuardSlot g{lay.at(ctx->sweep_guard_dev.p), &ctx->sweep_phase, ctx->guard_host + 2};   // the sweep's one slot ...
+  uint32_t *d_mask = lay.mask.in<uint32_t>(ctx->sweep_guard_dev.p);                             // ... and, beside it, the CUs' masks
   PassIO fast = io;
   fast.sweep.idx = nullptr; fast.sweep.mask = d_mask;
-  if ((rc = run_network(ctx, st, st.main_cfg(), n, fast, go))) {
-    (void)hipMemsetAsync(d.count, 0, 8, ctx->stream);   // (run_fast_async: the pass may or may not have run its heads kernel)
-    return rc;
-  }
-  ctx->sweep_phase ^= 1;
-  HIP_TRY(ctx, hipMemcpyAsync(h_count, tail.count, 4, hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = wait_count(ctx, st, n))) return rc;
-  const int k = *h_count;
-  if (k < 0 || k > n) { ctx->err = "guard: bad flagged-CU count"; return MLT_ERR_HIP; }
-  if (!k) return MLT_OK;
+  if ((rc = run_selecting(ctx, st, n, fast, g)) || (rc = wait_count(ctx, st, n))) return rc;
+  const int k = *g.h_count;
+  if ((rc = check_flagged_count(ctx, k, n)) || !k) return rc;
   const int S = st.size;
   const StageSet gl(S, k, st.model.n_logits, false, false);
   if ((rc = ctx->gstage.reserve(ctx, gl.bytes(), "guard staging"))) return rc;
   const StageSet::Ptrs gs = gl.at(ctx->gstage.p);
-  GuardGatherArgs ga{};
-  io.pl.fill(ga);
-  ga.poc = io.poc; ga.qp = io.qp ? io.qp : io.poc;   // the CUs' qp offsets follow them into the re-run; without offsets the column is a copy of poc and is not read
-  ga.idx = d.idx; ga.k = k; ga.s_l = ilog2(S);
-  ga.g_org = gs.d_org; ga.g_pred = gs.d_pred; ga.g_poc = gs.d_poc; ga.g_qp = gs.d_qp;
-  HIP_TRY(ctx, mlt_launch_guard_gather(ga, ctx->stream));
+  // (the CUs' qp offsets follow them into the re-run; without offsets the column is a copy of poc and is not read)
+  if ((rc = gather_flagged(ctx, S, io.pl, io.poc, io.qp ? io.qp : io.poc, g.d.idx, k, gs))) return rc;
   PassIO exact = io;   // the caller's outputs: the heads step writes row idx[j] of the slabs in mask[idx[j]]
   exact.pl = Planes::dense(gs.d_org, gs.d_pred, S); exact.poc = gs.d_poc; exact.qp = io.qp ? gs.d_qp : nullptr;
-  exact.sweep.idx = d.idx; exact.sweep.mask = d_mask;
+  exact.sweep.idx = g.d.idx; exact.sweep.mask = d_mask;
   if ((rc = run_network(ctx, st, st.exact_cfg(), k, exact))) return rc;
   st.reruns += (uint64_t)k;
   return MLT_OK;

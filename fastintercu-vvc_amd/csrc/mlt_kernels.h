@@ -212,6 +212,18 @@ struct CandRec {
   float prob[MLT_MAX_CAND_K];
 };
 
+// The thresholds of the parity guards' selection rule (guard_rule, mlt_tail_kernels.inc -- the one statement of the rule; the host fills them in guard_thresholds).
+// A CU is flagged -- re-evaluated with the exact arithmetic -- when
+//   its count of EXACTLY flat quads (statistic >> MLT_FLAT_EXACT_SHIFT) >= flat_thr or its count of near-flat quads (statistic & 0xFFFF) >= near_thr (flat guard), or,
+//   margin > 0: top1 - top2 of the decision head is not >= margin or a logit is NaN (decision guard), and with it
+//     conf_band > 0: |confidence - min_conf| is not >= conf_band (the gate guard, MLT_CONF_BAND_FRAC), and
+//     cand_band > 0: a proper prefix sum lies within cand_band of cand_cov, or classes are dropped over a logit gap below margin (the candidate guard), or,
+//   mag_thr > 0: its logit magnitude is not <= mag_thr (round 6: the magnitude guard, mlt_runtime.h: SizeState.mag_thr).
+struct GuardRule {
+  int flat_thr, near_thr;
+  float margin, mag_thr, conf_band, cand_band;
+};
+
 struct HeadArgs {
   const float *gap[MLT_MAX_HEADS_K];  // GAP partial sums [n][slots][C] fp32 (written by the stage's last conv)
   int slots[MLT_MAX_HEADS_K];
@@ -224,41 +236,34 @@ struct HeadArgs {
   int32_t *split;  // [n] (NULL: not wanted -- the record carries it)
   // Decision records and the confidence gate (NULL / 0: not wanted, and then no softmax is computed).  dec[n] <- the record of CU n (every head's
   // first-max argmax and its fp32 softmax probability; the decision head's margin).  min_conf > 0: split[n] (and dec[n].split_mode) = -1 unless the
-  // decision head's confidence >= min_conf (a NaN confidence gates).  g_conf_band > 0 (with the guard selection, g_margin > 0): the CU is also
-  // flagged when |confidence - min_conf| < g_conf_band (MLT_CONF_BAND_FRAC).
+  // decision head's confidence >= min_conf (a NaN confidence gates).
   DecisionRec *dec;
-  float min_conf, g_conf_band;
+  float min_conf;
   // Candidate sets (heads_cand_kernel: mlt_launch_heads picks it when cand != NULL or the policy is not the default (0, 0); every other launch runs heads_kernel).
-  // cand[n] <- the candidate record of CU n under (cand_cov, cand_max).  g_cand_band > 0 (with the guard selection, g_margin > 0): the CU is also flagged when a
-  // proper prefix sum lies within g_cand_band of cand_cov, or when classes are dropped over a logit gap below g_margin (the candidate guard).
+  // cand[n] <- the candidate record of CU n under (cand_cov, cand_max).
   CandRec *cand;
-  float cand_cov, g_cand_band;
+  float cand_cov;
   int cand_max;
-  // Single-CU launches (n == 1, mlt_predict's captured graph): the guard selection rides on this kernel instead of a launch of its own
-  // (guard_select_kernel: 5 us of a 160 us call).  g_count != NULL: g_count[0] = 1 and g_idx[0] = 0 when CU 0 is flagged by the
-  // flat-content statistic (g_flat, thresholds as GuardSelectArgs) or by the decision-head margin (g_margin > 0), else g_count[0] = 0;
-  // g_flat[0] is CLEARED afterwards (consume-and-clear: the next call's first kernel adds into it, no memset node in the graph).
-  int32_t *g_count, *g_idx, *g_flat;
-  int g_flat_thr, g_near_thr;
-  float g_margin;
-  // Round 6, the MAGNITUDE guard (mlt_runtime.h: SizeState.mag_thr): mag[n] <- max over all logits of sum_k |w_ck feat_k| -- the size of the
-  // feature-driven part of the logits, which is what the fp16 pipeline's RELATIVE error acts on (poc, qp and the bias enter exactly).  NULL: not
-  // wanted.  g_mag_thr > 0 (single-CU launches): CU 0 is also flagged when its magnitude exceeds the threshold (NaN included).
+  // Round 6, the MAGNITUDE guard's statistic: mag[n] <- max over all logits of sum_k |w_ck feat_k| -- the size of the feature-driven part of the logits, which is
+  // what the fp16 pipeline's RELATIVE error acts on (poc, qp and the bias enter exactly).  NULL: not wanted.
   float *mag;
-  float g_mag_thr;
-  // Round 6: the selection rides on this kernel for BATCHES too (g_next != NULL; guard_select_kernel -- a launch of its own, 23 us + a launch gap of a 4 ms step --
-  // stays behind MLT_TUNING=1 MLT_GUARD_SELECT_KERNEL=1).  g_count[0] is then a running count, ZERO on entry: a workgroup whose CU is flagged appends it to g_idx
-  // (the list is UNORDERED -- the exact re-run treats every CU independently, so the results do not depend on the order); workgroup 0 zeroes g_next[0], the counter
-  // the slot's next launch will count on (the runtime alternates between two counters: the one zeroed here was read by the previous launch's count copy, which
-  // precedes this kernel in stream order).  No atomics, no fences on the unflagged path.
-  int32_t *g_next;
+  // The guards' selection as the tail of this kernel (g_count != NULL; `rule` is all zeros otherwise): CU n is flagged when guard_rule says so under `rule`, on its
+  // flat-content statistic g_flat[n] (NULL: no flat guard), which is CLEARED afterwards (consume-and-clear: the next pass's first kernel adds into it, no memset).
+  // Single-CU launches (n == 1, g_next == NULL: mlt_predict's captured graph): g_count[0] = 1 and g_idx[0] = 0 when CU 0 is flagged, else g_count[0] = 0.
+  // Batches (g_next != NULL; guard_select_kernel -- a launch of its own, 23 us + a launch gap of a 4 ms step -- stays behind MLT_TUNING=1 MLT_GUARD_SELECT_KERNEL=1):
+  // g_count[0] is a running count, ZERO on entry: a workgroup whose CU is flagged appends it to g_idx (the list is UNORDERED -- the exact re-run treats every CU
+  // independently, so the results do not depend on the order); workgroup 0 zeroes g_next[0], the counter the slot's next launch will count on (the runtime
+  // alternates between two counters: the one zeroed here was read by the previous launch's count copy, which precedes this kernel in stream order).  No atomics,
+  // no fences on the unflagged path.
+  int32_t *g_count, *g_idx, *g_flat, *g_next;
+  GuardRule rule;
 };
 
 // QP sweep (sweep_heads_kernel, mlt_tail_kernels.inc): the heads of one pass under n_qps values of qp.  `h` is read as by heads_kernel except h.qp (NULL: point
 // q takes qps[q] for every CU; else a per-CU OFFSET: CU n takes qps[q] + h.qp[n], added as integers -- fix-up launches read it per CU of the re-run, like
 // h.poc) and h.mag (unused); the outputs of point q start `slab` CUs behind those of point q - 1 (h.logits: slab x sum-classes floats).
 // Fast pass (fix_idx == NULL): workgroup i is CU i and row i, every point is written; with the selection (h.g_next != NULL) mask[i] <- bit q set when CU i is
-// flagged under qps[q] (heads_kernel's rule), and a CU with a non-zero mask is appended to h.g_idx.  Fix-up (fix_idx != NULL, no selection): workgroup j is CU j of
+// flagged under qps[q] (guard_rule), and a CU with a non-zero mask is appended to h.g_idx.  Fix-up (fix_idx != NULL, no selection): workgroup j is CU j of
 // the exact re-run, its row is fix_idx[j], and only the points whose bit is set in mask[fix_idx[j]] are written.
 #define MLT_SWEEP_MAX_QPS_K 32
 struct HeadSweepArgs {
@@ -279,18 +284,15 @@ struct FlatStatArgs {
   int n, s_l;                  // CU size S = 1 << s_l
 };
 struct GuardSelectArgs {
-  const int32_t *flat;         // [n] (FlatStatArgs.flat) or NULL
-  const float *logits;         // [n][n_logits] or NULL (margin test off)
+  const int32_t *flat;         // [n] (FlatStatArgs.flat) or NULL: no flat guard
+  const float *logits;         // [n][n_logits] or NULL (the decision guard and what rides on it are off)
   int32_t *idx;                // [n] out: indices of the selected CUs, ascending
   int32_t *count;              // [1] out
   int n, n_logits, head_off, head_classes;
-  int flat_thr;                // select when the count of EXACTLY flat quads (flat >> MLT_FLAT_EXACT_SHIFT) >= flat_thr (flat != NULL) ...
-  int near_thr;                // ... or the count of near-flat quads (flat & 0xFFFF) >= near_thr
-  float margin;                // select when top1 - top2 of the decision head < margin (logits != NULL, margin > 0)
-  const float *mag;            // [n] (HeadArgs.mag) or NULL: select when mag > mag_thr (round 6: the magnitude guard)
-  float mag_thr;
-  float min_conf, conf_band;   // conf_band > 0 (with the margin test): select when |confidence - min_conf| < conf_band (HeadArgs.g_conf_band)
-  float cand_cov, cand_band;   // cand_band > 0 (with the margin test): the candidate guard under the policy (cand_cov, cand_max) (HeadArgs.g_cand_band)
+  const float *mag;            // [n] (HeadArgs.mag) or NULL: no magnitude guard
+  GuardRule rule;              // CU i is selected when guard_rule says so, on flat[i], mag[i] and -- recomputed from logits[i] -- the decision head's confidence and candidate flag
+  float min_conf;              // the gate and the candidate policy the heads kernel ran under (HeadArgs)
+  float cand_cov;
   int cand_max;
 };
 struct GuardGatherArgs {

@@ -193,17 +193,18 @@ struct SizeState {
   NetCfg exact_cfg() { NetCfg c; c.S = size; c.m = &model_exact; return c; }
 };
 
-// guard state of one in-flight batch (mlt_kernels.hip: flat_stat / guard_select kernels): any layout's guard fields on the device, {fields.at(base), phase, h_count[, single]}
+// guard state of one in-flight pass -- a batch, a QP sweep, mlt_predict's one CU: any layout's guard fields on the device, {fields.at(base), phase, h_count[, single]}
 struct GuardSlot {
   Lay::GuardFields::Ptrs d{};
-  int *phase = nullptr;        // batches with the selection inside the heads kernel: d.count[*phase] is the launch's running count (zero on entry), d.count[*phase ^ 1] the
-                               // one it zeroes for the NEXT launch of the slot; toggled per launch (run_guarded_async).  NULL: no such pair (the slot serves one-CU launches)
-  int32_t *h_count = nullptr;  // pinned
+  int *phase = nullptr;        // passes with the selection as the heads kernel's tail on a counter pair: d.count[*phase] is the launch's running count (zero on entry),
+                               // d.count[*phase ^ 1] the one it zeroes for the NEXT launch of the slot; toggled per launch (mlt_guards.cpp: run_selecting).  NULL: no such pair
+  int32_t *h_count = nullptr;  // pinned: where the count comes back
   bool single = false;         // mlt_predict's slot: one CU, d.flat zero on entry and cleared by the heads kernel (consume-and-clear), the
                                // selection rides on the heads kernel, and the caller's own result copy brings the count back
 };
-// the thresholds of a size's guards (guard_thresholds) and, with the pointers set, the selection as a tail of the heads kernel (HeadArgs.g_*)
-struct GuardTail { int32_t *count, *idx, *flat; int flat_thr, near_thr; float margin, mag_thr; int32_t *next; float conf_band, cand_band; };  // next != NULL: batches (HeadArgs.g_next)
+// the selection as the tail of a pass's heads kernel: the size's rule (mlt_kernels.h: GuardRule) and where the tail counts, lists and reads the flat statistic
+// (HeadArgs.rule, g_count, g_idx, g_flat, g_next; next != NULL: a counter pair -- batches and sweeps)
+struct GuardTail { GuardRule rule; int32_t *count, *idx, *flat, *next; };
 
 using Lay::StageSet;
 
@@ -298,7 +299,7 @@ struct mlt_ctx {
   int guard_phase[2] = {0, 0};    // which counter of a slot's pair the next batch launch counts on (GuardSlot.phase)
   hipEvent_t ev_guard = nullptr;  // "count of flagged CUs has landed" (device-pointer entry)
   GrowBuf gstage;
-  GrowBuf sweep_guard_dev;              // QP sweeps: one slot of sweep_guard_lay (zero when allocated), its counter phase; the count lands in guard_host[2]
+  GrowBuf sweep_guard_dev;              // QP sweeps: one slot of sweep_guard_lay (zero when allocated), its counter phase (GuardSlot.phase); the count lands in guard_host[2]
   Lay::SweepGuardLay sweep_guard_lay;
   int sweep_phase = 0;
   // mlt_predict_tree's / mlt_predict_trees' device arena (Lay::TreeArena) or mlt_predict_tree_sweep's / mlt_predict_trees_sweep's (Lay::TreeSweepArena), and the pinned count
@@ -352,6 +353,11 @@ inline int check_size(mlt_ctx *ctx, int size, SizeState **out) {
   SizeState &st = ctx->sz[si];
   if (!st.enabled || !st.loaded) { ctx->err = "CU size not enabled or weights not loaded"; return MLT_ERR_SIZE_DISABLED; }
   *out = &st;
+  return MLT_OK;
+}
+// a flagged-CU count that came back from a guarded pass on n CUs
+inline int check_flagged_count(mlt_ctx *ctx, int k, int n) {
+  if (k < 0 || k > n) { ctx->err = "guard: bad flagged-CU count"; return MLT_ERR_HIP; }
   return MLT_OK;
 }
 

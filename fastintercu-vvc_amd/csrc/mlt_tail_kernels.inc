@@ -4,10 +4,14 @@
 // feat = (sum of the GAP partial sums written by the stage's last conv) / HW
 // logits_k = W_k . [feat (C floats), poc, qp] + b_k ; split = first maximal index (torch.argmax).
 // Every class of a head runs the identical operation sequence, so identical rows tie exactly.
+// Each piece that more than one kernel runs is ONE device function here: gap_features (a head's features), head_decision / head_candidates (a head's argmax,
+// confidence, margin / candidate set), decision_tail (split mode under the gate + record of one (CU, point)), max_magnitude, and guard_rule -- the parity guards'
+// selection rule, stated once.  heads_kernel<DEC> / heads_cand_kernel (heads_body) run them per CU, sweep_heads_kernel per (CU, point); guard_select_kernel runs
+// guard_rule on logits read back from memory.
 // ---------------------------------------------------------------------------------------------
-// Decision of one head from its K logits: first-max argmax (torch.argmax), top-1 minus top-2 logit (the decision guard's statistic, same comparisons), and the
+// Decision of one head from its K logits: first-max argmax (torch.argmax), top-1 minus top-2 logit (margin_guard's scan), and the
 // softmax probability of the argmax -- fp32, max-subtracted, the full-precision expf, every class through the same operations and summed in class order, so tied
-// rows give tied probabilities (the argmax's own term is expf(0) = 1).  A NaN logit gives a NaN confidence.  Shared by heads_kernel and guard_select_kernel.
+// rows give tied probabilities (the argmax's own term is expf(0) = 1).  A NaN logit gives a NaN confidence.
 __device__ __forceinline__ void head_decision(const float *l, int K, int &best, float &conf, float &margin) {
   best = 0;
   for (int k = 1; k < K; ++k)
@@ -25,7 +29,7 @@ __device__ __forceinline__ void head_decision(const float *l, int K, int &best, 
 
 // The decision guard's rule on one head's K logits: the top-2 margin (head_decision's scan) is not >= thr, or a logit is NaN.  The NaN needs its own test: a NaN
 // loses both comparisons of the scan, which then reports the margin of the OTHER classes, and !(t1 - t2 >= thr) alone catches only a head whose logits are ALL
-// NaN.  Shared by the heads kernels' tail (batches and mlt_predict's one-CU launches) and guard_select_kernel.
+// NaN.  (guard_rule's decision guard.)
 __device__ __forceinline__ bool margin_guard(const float *l, int K, float thr) {
   float t1 = -3.4e38f, t2 = -3.4e38f;
   bool nan = false;
@@ -41,7 +45,7 @@ __device__ __forceinline__ bool margin_guard(const float *l, int K, float thr) {
 // after unrolling, nothing lives in scratch); the fp32 softmax of every class -- the operations of head_decision, so prob[argmax] is its confidence bit for bit --
 // prefix sums in rank order; the shortest prefix that reaches `coverage` is kept, every class when that needs more than max_modes > 0 of them or a logit is NaN.
 // flag (band > 0: the candidate guard): a proper prefix sum lies within `band` of the coverage, or classes are dropped over a logit gap below gap_thr -- in the
-// !(x >= y) form, so a NaN flags.  Shared by heads_cand_kernel and guard_select_kernel.
+// !(x >= y) form, so a NaN flags.
 __device__ __forceinline__ void head_candidates(const float *l, int K, float coverage, int max_modes, float band, float gap_thr, CandRec &r, bool &flag) {
   int best = 0;
   for (int k = 1; k < K; ++k)
@@ -100,6 +104,73 @@ __device__ __forceinline__ void head_candidates(const float *l, int K, float cov
   flag = band > 0.f && (near || !(gap >= gap_thr));
 }
 
+// The magnitude guard's statistic of a CU: the largest of its logits' sums of |w_ck feat_k| (a NaN sticks).
+__device__ __forceinline__ float max_magnitude(const float *lgm, int n_logits) {
+  float mag = 0.f;
+  for (int k = 0; k < n_logits; ++k) mag = !(lgm[k] <= mag) ? lgm[k] : mag;
+  return mag;
+}
+
+// THE selection rule of the parity guards (mlt_kernels.h: GuardRule states it in words): whether one CU is re-evaluated with the exact arithmetic.  Every
+// floating-point comparison is in the negated !(x >= y) form, so a NaN -- logit, confidence or magnitude -- flags.  flat_on / flat: the CU's flat-content statistic (off: no
+// flat guard); l, K: the decision head's logits (NULL: the decision guard and what rides on it are off); dec_on, conf, min_conf: the head's confidence and the
+// gate it met (dec_on false: the launch computed neither records nor gate); cflag: head_candidates' flag (false where no candidate set was computed); mag: the
+// CU's max_magnitude (0 where there is none: never above a threshold).  Called by the tail of the heads kernels, by sweep_heads_kernel per point and by
+// guard_select_kernel; what follows the verdict (append, ballot, scan) is the caller's.
+__device__ __forceinline__ bool guard_rule(const GuardRule &r, bool flat_on, int flat, const float *l, int K, bool dec_on, float conf, float min_conf, bool cflag, float mag) {
+  bool s = flat_on && ((flat >> MLT_FLAT_EXACT_SHIFT) >= r.flat_thr || (flat & 0xFFFF) >= r.near_thr);
+  if (l && r.margin > 0.f) {
+    s = s || margin_guard(l, K, r.margin);
+    if (dec_on && r.conf_band > 0.f) s = s || !(fabsf(conf - min_conf) >= r.conf_band);   // the gate guard (mlt_kernels.h: MLT_CONF_BAND_FRAC)
+    s = s || cflag;   // the candidate guard (head_candidates: off unless cand_band > 0)
+  }
+  if (r.mag_thr > 0.f) s = s || !(mag <= r.mag_thr);
+  return s;
+}
+
+// GAP features of head hd of CU n, one thread per channel: the partial sums of the stage's last conv added in slot order (eight loads in flight), / (float)hw.
+__device__ __forceinline__ void gap_features(const HeadArgs &a, int hd, int n, int tid, float *feat) {
+  const int C = a.c[hd], slots = a.slots[hd];
+  if (tid < C) {
+    const float *g = a.gap[hd] + (size_t)n * slots * C + tid;
+    float s = 0.f;
+    for (int i = 0; i < slots; i += 8) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = i + u < slots ? g[(size_t)(i + u) * C] : 0.f;
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (i + u < slots) s += v[u];
+    }
+    feat[tid] = s / (float)a.hw[hd];
+  }
+}
+
+// Decision tail of one (CU, point), one thread: first-max argmax of the decision head's logits l; with dec_on the head's confidence (conf, else 0), the gate
+// (a NaN confidence gates) and -- dec != NULL -- the record, from the point's per-head rows hmode / hconf / hmarg (head_decision).  Returns the split mode.
+__device__ __forceinline__ int decision_tail(const HeadArgs &a, const float *l, bool dec_on, const int *hmode, const float *hconf, const float *hmarg, DecisionRec *dec, float &conf) {
+  int best = 0;
+  for (int k = 1; k < a.classes[a.decision_head]; ++k)
+    if (l[k] > l[best]) best = k;
+  int out = best;
+  conf = 0.f;
+  if (dec_on) {
+    conf = hconf[a.decision_head];
+    if (a.min_conf > 0.f) out = conf >= a.min_conf ? best : -1;
+    if (dec) {
+      DecisionRec r;
+      r.split_mode = out; r.raw_mode = best; r.confidence = conf; r.margin = hmarg[a.decision_head];
+#pragma unroll
+      for (int hd = 0; hd < MLT_MAX_HEADS_K; ++hd) {
+        r.level_mode[hd] = hd < a.n_heads ? hmode[hd] : -1;
+        r.level_conf[hd] = hd < a.n_heads ? hconf[hd] : 0.f;
+      }
+      *dec = r;
+    }
+  }
+  return out;
+}
+
 // DEC: the instantiation that also computes the decision records / applies the confidence gate (HeadArgs.dec != NULL or min_conf > 0: mlt_launch_heads picks it);
 // <false> is the kernel as it was before records existed -- launches that want neither run exactly that code.  CAND: the body of heads_cand_kernel, which also
 // computes the candidate records and the candidate guard (HeadArgs.cand != NULL or a policy other than (0, 0)); heads_kernel<DEC> is the body without them.
@@ -112,25 +183,10 @@ __device__ __forceinline__ void heads_body(const HeadArgs &a) {
   __shared__ float lgm[MLT_MAX_LOGITS_K];   // sum_k |w_ck feat_k| per logit (the magnitude guard's statistic)
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float fpoc = (float)a.poc[n], fqp = (float)a.qp[n];  // EncCu.cpp:881-882 (int -> float, exact)
-  // GAP features of ALL heads first (one barrier instead of two per head: this kernel is pure latency, and it is a
-  // visible share of the one-CU-per-call path).  The partial sums are added in slot order as before -- same rounding --
-  // but eight loads are in flight at a time instead of one.
+  // GAP features of ALL heads first (one barrier instead of two per head: this kernel is pure latency, and it is a visible share of the one-CU-per-call path).
   for (int hd = 0; hd < a.n_heads; ++hd) {
-    const int C = a.c[hd], slots = a.slots[hd];
-    if (tid < C) {
-      const float *g = a.gap[hd] + (size_t)n * slots * C + tid;
-      float s = 0.f;
-      for (int i = 0; i < slots; i += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = i + u < slots ? g[(size_t)(i + u) * C] : 0.f;
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (i + u < slots) s += v[u];
-      }
-      feat[hd][tid] = s / (float)a.hw[hd];
-    }
-    if (tid == 0) { feat[hd][C] = fpoc; feat[hd][C + 1] = fqp; }
+    gap_features(a, hd, n, tid, feat[hd]);
+    if (tid == 0) { feat[hd][a.c[hd]] = fpoc; feat[hd][a.c[hd] + 1] = fqp; }
   }
   __syncthreads();
   int lo = 0;
@@ -164,50 +220,24 @@ __device__ __forceinline__ void heads_body(const HeadArgs &a) {
   if (tid == 0) {
     int off = 0;
     for (int hd = 0; hd < a.decision_head; ++hd) off += a.classes[hd];
-    int best = 0;
-    for (int k = 1; k < a.classes[a.decision_head]; ++k)
-      if (lg[off + k] > lg[off + best]) best = k;
-    int out = best;
-    float conf = 0.f;
-    if constexpr (DEC) {
-      conf = hconf[a.decision_head];
-      if (a.min_conf > 0.f) out = conf >= a.min_conf ? best : -1;   // (a NaN confidence gates)
-      if (a.dec) {
-        DecisionRec r;
-        r.split_mode = out; r.raw_mode = best; r.confidence = conf; r.margin = hmarg[a.decision_head];
-#pragma unroll
-        for (int hd = 0; hd < MLT_MAX_HEADS_K; ++hd) {
-          r.level_mode[hd] = hd < a.n_heads ? hmode[hd] : -1;
-          r.level_conf[hd] = hd < a.n_heads ? hconf[hd] : 0.f;
-        }
-        a.dec[n] = r;
-      }
-    }
+    float conf;
+    const int out = decision_tail(a, lg + off, DEC, hmode, hconf, hmarg, (DEC && a.dec) ? a.dec + n : nullptr, conf);
     bool cflag = false;
     if constexpr (CAND) {
       CandRec cr;
-      head_candidates(lg + off, a.classes[a.decision_head], a.cand_cov, a.cand_max, a.g_cand_band, a.g_margin, cr, cflag);
+      head_candidates(lg + off, a.classes[a.decision_head], a.cand_cov, a.cand_max, a.rule.cand_band, a.rule.margin, cr, cflag);
       if (a.cand) a.cand[n] = cr;
     }
     if (!DEC || a.split) a.split[n] = out;   // (only a launch that writes records may come without a split buffer)
     float mag = 0.f;
-    if (a.mag || a.g_mag_thr > 0.f) {
-      for (int k = 0; k < lo; ++k) mag = !(lgm[k] <= mag) ? lgm[k] : mag;   // (a NaN sticks)
+    if (a.mag || a.rule.mag_thr > 0.f) {
+      mag = max_magnitude(lgm, lo);
       if (a.mag) a.mag[n] = mag;
     }
-    if (a.g_count && (n == 0 || a.g_next)) {  // guard_select_kernel's test for this CU (same comparisons, same NaN behaviour): mlt_predict's one-CU launches, and every launch of a slot with a counter pair (g_next)
-      bool s = false;
-      if (a.g_flat) {
-        const int f = a.g_flat[n];
-        s = (f >> MLT_FLAT_EXACT_SHIFT) >= a.g_flat_thr || (f & 0xFFFF) >= a.g_near_thr;
-        a.g_flat[n] = 0;
-      }
-      if (a.g_margin > 0.f) {
-        s = s || margin_guard(lg + off, a.classes[a.decision_head], a.g_margin);
-        if (DEC && a.g_conf_band > 0.f) s = s || !(fabsf(conf - a.min_conf) >= a.g_conf_band);   // the gate guard (mlt_kernels.h: MLT_CONF_BAND_FRAC); also catches NaN
-        if (CAND) s = s || cflag;   // the candidate guard (head_candidates; off unless g_cand_band > 0)
-      }
-      if (a.g_mag_thr > 0.f) s = s || !(mag <= a.g_mag_thr);
+    if (a.g_count && (n == 0 || a.g_next)) {  // the selection: mlt_predict's one-CU launches, and every launch of a slot with a counter pair (g_next)
+      int flat = 0;
+      if (a.g_flat) { flat = a.g_flat[n]; a.g_flat[n] = 0; }   // consume-and-clear
+      const bool s = guard_rule(a.rule, a.g_flat != nullptr, flat, lg + off, a.classes[a.decision_head], DEC, conf, a.min_conf, cflag, mag);
       if (a.g_next) {   // unordered append to a count that was zero on entry; workgroup 0 re-arms the slot's other counter for the next launch
         if (n == 0) a.g_next[0] = 0;
         if (s) a.g_idx[atomicAdd(a.g_count, 1)] = n;
@@ -228,8 +258,8 @@ __global__ __launch_bounds__(256) void heads_cand_kernel(const HeadArgs a) { hea
 // QP sweep (HeadSweepArgs): the heads of ONE pass under n_qps values of qp -- slab q holds what heads_kernel / heads_cand_kernel give with every qp[i] = qps[q],
 // bit for bit.  qp enters a logit as the LAST element of one lane's fmaf chain (index C + 1 of [feat, poc, qp]: lane (C + 1) & 63), so the per-lane partial sums
 // over [feat, poc] are computed once per (head, class) with heads_body's chain; a point adds its one fmaf in that lane and repeats the shuffle tree and the bias.
-// The magnitude statistic does not see qp: once.  The tails run on one thread per (point, head) -- head_decision -- and one per point -- split under the gate,
-// records, the guards' rule (heads_body's, same comparisons): the points of wave 0 vote the CU's mask.  Fix-up launches (sa.fix_idx) write only the masked points.
+// The magnitude statistic does not see qp: once.  The tails run on one thread per (point, head) -- head_decision -- and one per point -- decision_tail, the
+// candidate set, guard_rule: the points of wave 0 vote the CU's mask.  Fix-up launches (sa.fix_idx) write only the masked points.
 // a.qp != NULL: CU n's point q is qps[q] + a.qp[n] -- added as integers before the one conversion, so the slab holds the bytes of a CU whose qp is that sum.
 __global__ __launch_bounds__(256) void sweep_heads_kernel(const HeadSweepArgs sa) {
   const HeadArgs &a = sa.h;
@@ -246,22 +276,9 @@ __global__ __launch_bounds__(256) void sweep_heads_kernel(const HeadSweepArgs sa
   const bool select = !sa.fix_idx && a.g_count && a.g_next;
   const float fpoc = (float)a.poc[n];
   const int qp_off = a.qp ? a.qp[n] : 0;
-  for (int hd = 0; hd < a.n_heads; ++hd) {   // heads_body's features: slot-order sums, / (float)hw
-    const int C = a.c[hd], slots = a.slots[hd];
-    if (tid < C) {
-      const float *g = a.gap[hd] + (size_t)n * slots * C + tid;
-      float s = 0.f;
-      for (int i = 0; i < slots; i += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = i + u < slots ? g[(size_t)(i + u) * C] : 0.f;
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (i + u < slots) s += v[u];
-      }
-      feat[hd][tid] = s / (float)a.hw[hd];
-    }
-    if (tid == 0) feat[hd][C] = fpoc;
+  for (int hd = 0; hd < a.n_heads; ++hd) {
+    gap_features(a, hd, n, tid, feat[hd]);
+    if (tid == 0) feat[hd][a.c[hd]] = fpoc;   // (qp: per point, below)
   }
   if (tid == 0 && select && a.g_flat) { sflat = a.g_flat[n]; a.g_flat[n] = 0; }   // consume-and-clear, once for all points
   __syncthreads();
@@ -317,45 +334,18 @@ __global__ __launch_bounds__(256) void sweep_heads_kernel(const HeadSweepArgs sa
       const float *l = lg[q];
       int off = 0;
       for (int hd = 0; hd < a.decision_head; ++hd) off += a.classes[hd];
-      int best = 0;
-      for (int k = 1; k < a.classes[a.decision_head]; ++k)
-        if (l[off + k] > l[off + best]) best = k;
-      int out = best;
-      float conf = 0.f;
-      if (dec_on) {
-        conf = hconf[q][a.decision_head];
-        if (a.min_conf > 0.f) out = conf >= a.min_conf ? best : -1;   // (a NaN confidence gates)
-        if (a.dec && wq_on) {
-          DecisionRec r;
-          r.split_mode = out; r.raw_mode = best; r.confidence = conf; r.margin = hmarg[q][a.decision_head];
-#pragma unroll
-          for (int hd = 0; hd < MLT_MAX_HEADS_K; ++hd) {
-            r.level_mode[hd] = hd < a.n_heads ? hmode[q][hd] : -1;
-            r.level_conf[hd] = hd < a.n_heads ? hconf[q][hd] : 0.f;
-          }
-          a.dec[dst] = r;
-        }
-      }
+      float conf;
+      const int out = decision_tail(a, l + off, dec_on, hmode[q], hconf[q], hmarg[q], (a.dec && wq_on) ? a.dec + dst : nullptr, conf);
       bool cflag = false;
       if (cand_on) {
         CandRec cr;
-        head_candidates(l + off, a.classes[a.decision_head], a.cand_cov, a.cand_max, a.g_cand_band, a.g_margin, cr, cflag);
+        head_candidates(l + off, a.classes[a.decision_head], a.cand_cov, a.cand_max, a.rule.cand_band, a.rule.margin, cr, cflag);
         if (a.cand && wq_on) a.cand[dst] = cr;
       }
       if (a.split && wq_on) a.split[dst] = out;
-      if (select) {   // heads_body's rule for this CU under qps[q]
-        if (a.g_flat) s = (sflat >> MLT_FLAT_EXACT_SHIFT) >= a.g_flat_thr || (sflat & 0xFFFF) >= a.g_near_thr;
-        if (a.g_margin > 0.f) {
-          s = s || margin_guard(l + off, a.classes[a.decision_head], a.g_margin);
-          if (dec_on && a.g_conf_band > 0.f) s = s || !(fabsf(conf - a.min_conf) >= a.g_conf_band);
-          if (cand_on) s = s || cflag;
-        }
-        if (a.g_mag_thr > 0.f) {
-          float mag = 0.f;
-          for (int k = 0; k < lo; ++k) mag = !(lgm[k] <= mag) ? lgm[k] : mag;   // (a NaN sticks)
-          s = s || !(mag <= a.g_mag_thr);
-        }
-      }
+      if (select)   // this CU under qps[q]
+        s = guard_rule(a.rule, a.g_flat != nullptr, a.g_flat ? sflat : 0, l + off, a.classes[a.decision_head], dec_on, conf, a.min_conf, cflag,
+                       a.rule.mag_thr > 0.f ? max_magnitude(lgm, lo) : 0.f);
     }
     const uint32_t mask = (uint32_t)__ballot(s) & all & (sa.active ? sa.active[n] : 0xFFFFFFFFu);   // (tree sweeps: only the points whose tree holds this CU)
     if (tid == 0 && select) {
@@ -372,9 +362,9 @@ __global__ __launch_bounds__(256) void sweep_heads_kernel(const HeadSweepArgs sa
 // neighbouring pixels DIFFER: on exactly-constant areas every pixel carries the same rounding error (measured: a constant
 // 128x128 CU reaches |dlogit| 1.3e-3, ordinary content 2-7e-4), and nearly so where they differ by a few LSB (dither, low
 // contrast, gentle ramps: rms 1.2-1.5x the textured one, measured per content class in round 3).  flat_stat_kernel counts,
-// per CU, the aligned 4-pixel quads whose org values and whose |org - pred| values each span <= MLT_FLAT_RANGE; guard_select_kernel lists the CUs whose count reaches the
-// threshold (and, optionally, those whose decision-head margin is small); the host runtime re-evaluates exactly those
-// CUs with the exact (hi, lo) arithmetic (gather -> exact network -> scatter).  Integer statistics: deterministic.
+// per CU, the aligned 4-pixel quads whose org values and whose |org - pred| values each span <= MLT_FLAT_RANGE; the selection (guard_rule above: as the tail of the
+// heads kernels, or as guard_select_kernel) lists the CUs whose count reaches the threshold and those the other guards flag; the host runtime re-evaluates exactly
+// those CUs with the exact (hi, lo) arithmetic (gather -> exact network -> scatter).  Integer statistics: deterministic.
 // ---------------------------------------------------------------------------------------------
 template <bool ALIGNED>
 __global__ __launch_bounds__(256) void flat_stat_kernel(const FlatStatArgs a) {
@@ -411,23 +401,14 @@ __global__ __launch_bounds__(1024) void guard_select_kernel(const GuardSelectArg
   __shared__ int part[1024];
   const int tid = threadIdx.x, per = (a.n + 1023) / 1024, lo = tid * per, hi = lo + per < a.n ? lo + per : a.n;
   auto selected = [&](int i) -> bool {
-    bool s = a.flat && ((a.flat[i] >> MLT_FLAT_EXACT_SHIFT) >= a.flat_thr || (a.flat[i] & 0xFFFF) >= a.near_thr);
-    if (a.logits && a.margin > 0.f) {
-      const float *l = a.logits + (size_t)i * a.n_logits + a.head_off;
-      s = s || margin_guard(l, a.head_classes, a.margin);
-      if (a.conf_band > 0.f) {   // the gate guard, on the confidence heads_kernel computed from these logits (same function, same operations)
-        int bm; float cf, mg;
-        head_decision(l, a.head_classes, bm, cf, mg);
-        s = s || !(fabsf(cf - a.min_conf) >= a.conf_band);
-      }
-      if (a.cand_band > 0.f) {   // the candidate guard, on the set heads_cand_kernel computed from these logits (same function)
-        CandRec cr; bool cf;
-        head_candidates(l, a.head_classes, a.cand_cov, a.cand_max, a.cand_band, a.margin, cr, cf);
-        s = s || cf;
-      }
+    const float *l = a.logits ? a.logits + (size_t)i * a.n_logits + a.head_off : nullptr;
+    float conf = 0.f;
+    bool cflag = false;
+    if (l && a.rule.margin > 0.f) {   // what the heads kernel had at hand, recomputed from the logits it left in memory (head_decision, head_candidates: its own functions)
+      if (a.rule.conf_band > 0.f) { int bm; float mg; head_decision(l, a.head_classes, bm, conf, mg); }
+      if (a.rule.cand_band > 0.f) { CandRec cr; head_candidates(l, a.head_classes, a.cand_cov, a.cand_max, a.rule.cand_band, a.rule.margin, cr, cflag); }
     }
-    if (a.mag && a.mag_thr > 0.f) s = s || !(a.mag[i] <= a.mag_thr);
-    return s;
+    return guard_rule(a.rule, a.flat != nullptr, a.flat ? a.flat[i] : 0, l, a.head_classes, true, conf, a.min_conf, cflag, a.mag ? a.mag[i] : 0.f);
   };
   int c = 0;
   for (int i = lo; i < hi; ++i) c += selected(i) ? 1 : 0;
