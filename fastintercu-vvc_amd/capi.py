@@ -36,7 +36,9 @@ EXPORTS = ["mlt_abi_version", "mlt_build_signature", "mlt_init", "mlt_num_device
            "mlt_tree_max_nodes", "mlt_tree_roots", "mlt_predict_tree", "mlt_predict_trees",
            "mlt_predict_batch_device_sweep", "mlt_predict_at_sweep", "mlt_predict_tree_sweep", "mlt_predict_trees_sweep",
            "mlt_motion_blocks", "mlt_picture_download", "mlt_picture_compensate", "mlt_picture_predict",
+           "mlt_picture_compensate_refs", "mlt_picture_predict_refs",
            "mlt_debug_conv_table"]
+MOTION_MAX_REFS = 4  # MLT_MOTION_MAX_REFS
 SWEEP_MAX_QPS = 32  # MLT_SWEEP_MAX_QPS
 TREES_MAX_PICTURES = 256  # MLT_TREES_MAX_PICTURES
 TREE_BY_CANDIDATES = 0x1  # mlt_tree_config.flags: descend on cand_mask & descend_mask instead of on split_mode
@@ -90,6 +92,11 @@ class MltTreePicture(C.Structure):
 class MltMotionConfig(C.Structure):
     """`struct mlt_motion_config` (include/mltcnn.h): 20 bytes."""
     _fields_ = [("struct_size", C.c_uint32), ("block", C.c_int32), ("range", C.c_int32), ("lambda_", C.c_int32), ("flags", C.c_uint32)]
+
+
+class MltMotionRefsConfig(C.Structure):
+    """`struct mlt_motion_refs_config` (include/mltcnn.h): 24 bytes."""
+    _fields_ = [("struct_size", C.c_uint32), ("block", C.c_int32), ("range", C.c_int32), ("lambda_", C.c_int32), ("subpel", C.c_int32), ("flags", C.c_uint32)]
 
 
 # `struct mlt_tree_node` (include/mltcnn.h): 32 bytes, no padding
@@ -180,6 +187,8 @@ def load_library():
     lib.mlt_picture_download.argtypes = [vp, vp, vp, i32]
     lib.mlt_picture_compensate.argtypes = [vp, vp, C.POINTER(MltMotionConfig), vp, vp]
     lib.mlt_picture_predict.argtypes = [vp, vp, vp, C.POINTER(MltMotionConfig), vp, vp, vp]
+    lib.mlt_picture_compensate_refs.argtypes = [vp, C.POINTER(vp), i32, C.POINTER(MltMotionRefsConfig), vp, vp, vp]
+    lib.mlt_picture_predict_refs.argtypes = [vp, vp, C.POINTER(vp), i32, C.POINTER(MltMotionRefsConfig), vp, vp, vp, vp]
     lib.mlt_synchronize.argtypes = [vp]
     lib.mlt_set_stream.argtypes = [vp, vp]
     lib.mlt_alloc_pinned.restype = vp
@@ -234,6 +243,18 @@ def motion_config(block: int = 16, search_range: int = 0, lam: int = 0, flags: i
     cfg.struct_size = C.sizeof(MltMotionConfig)
     cfg.block, cfg.range, cfg.lambda_, cfg.flags = int(block), int(search_range), int(lam), int(flags)
     return cfg
+
+
+def motion_refs_config(block: int = 16, search_range: int = 0, lam: int = 0, subpel: int = 0, flags: int = 0) -> MltMotionRefsConfig:
+    cfg = MltMotionRefsConfig()
+    cfg.struct_size = C.sizeof(MltMotionRefsConfig)
+    cfg.block, cfg.range, cfg.lambda_, cfg.subpel, cfg.flags = int(block), int(search_range), int(lam), int(subpel), int(flags)
+    return cfg
+
+
+def _picture_handles(pics):
+    """A list of Pictures as the `const mlt_picture *const *` of the _refs calls."""
+    return (C.c_void_p * max(len(pics), 1))(*[p._h for p in pics])
 
 
 class Picture:
@@ -550,6 +571,36 @@ class MltCnn:
             out = {"mv": np.zeros((by, bx, 2), np.int16), "cost": np.zeros((by, bx), np.uint32)}
         self._check(self._lib.mlt_picture_predict(self._h, cur_pic._h, ref_pic._h, C.byref(cfg), dst_pic._h,
                                                   out["mv"].ctypes.data if want_field else None, out["cost"].ctypes.data if want_field else None))
+        return out
+
+    def compensate_refs(self, ref_pics, mv, ref_idx, dst_pic: Picture, block: int = 16):
+        """dst_pic <- block by block the compensation of ref_pics[ref_idx[block]] with the field mv (mlt_picture_compensate_refs; motion.compensate_refs is the
+        rule).  ref_idx: uint8 [by, bx], or None for reference 0 everywhere.  Returns once mv and ref_idx may be reused."""
+        mv = np.ascontiguousarray(mv, np.int16)
+        bx, by = motion_blocks(dst_pic.width, dst_pic.height, block or 16)
+        assert (bx, by) == (0, 0) or mv.shape == (by, bx, 2), (mv.shape, (by, bx, 2))   # (a bad block: the library's error)
+        if ref_idx is not None:
+            ref_idx = np.ascontiguousarray(ref_idx, np.uint8)
+            assert (bx, by) == (0, 0) or ref_idx.shape == (by, bx), (ref_idx.shape, (by, bx))
+        cfg = motion_refs_config(block)
+        self._check(self._lib.mlt_picture_compensate_refs(self._h, _picture_handles(ref_pics), len(ref_pics), C.byref(cfg), mv.ctypes.data,
+                                                          None if ref_idx is None else ref_idx.ctypes.data, dst_pic._h))
+        return dst_pic
+
+    def predict_picture_refs(self, cur_pic: Picture, ref_pics, dst_pic: Picture, block: int = 16, search_range: int = 16, lam: int = 0, subpel: int = 2,
+                             want_field: bool = True) -> dict:
+        """dst_pic <- the prediction of cur_pic from up to MOTION_MAX_REFS references: an integer search per reference, the quarter-sample refinement of each
+        winner (subpel 0 / 1 / 2: integer / half / quarter window) and the per-block choice among them, then compensation (mlt_picture_predict_refs;
+        motion.predict_refs is the rule).  want_field: -> {"mv": int16 [by, bx, 2], "ref": uint8 [by, bx], "cost": uint32 [by, bx] (cost_q)} and the call is
+        synchronous; else {} and it returns after enqueueing -- later calls on this context see dst_pic in stream order."""
+        cfg = motion_refs_config(block, search_range, lam, subpel)
+        out = {}
+        if want_field:
+            bx, by = motion_blocks(dst_pic.width, dst_pic.height, block or 16)
+            out = {"mv": np.zeros((by, bx, 2), np.int16), "ref": np.zeros((by, bx), np.uint8), "cost": np.zeros((by, bx), np.uint32)}
+        self._check(self._lib.mlt_picture_predict_refs(self._h, cur_pic._h, _picture_handles(ref_pics), len(ref_pics), C.byref(cfg), dst_pic._h,
+                                                       out["mv"].ctypes.data if want_field else None, out["ref"].ctypes.data if want_field else None,
+                                                       out["cost"].ctypes.data if want_field else None))
         return out
 
     def predict_at(self, size: int, org_pic: Picture, pred_pic: Picture, xy, poc, qp, want=("split", "logits", "decisions", "candidates")) -> dict:

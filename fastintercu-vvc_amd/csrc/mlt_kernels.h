@@ -326,6 +326,7 @@ struct PictureGatherArgs {
 hipError_t mlt_launch_picture_gather(const PictureGatherArgs &a, hipStream_t st);
 // ---- prediction pictures (mlt_picture_predict, mlt_picture_compensate): block motion search and quarter-sample compensation (mlt_motion_kernels.inc).  Blocks of
 // B = 1 << block_l samples, clipped at the right and bottom border; the field is [by][bx][2] int16 {mvx, mvy} in quarter samples, raster order ----
+#define MLT_MOTION_MAX_REFS_K 4   // include/mltcnn.h: MLT_MOTION_MAX_REFS (mlt_runtime.h asserts it)
 struct MotionSearchArgs {
   const int16_t *cur, *ref;    // sample (0, 0) of the two pictures (independent bases and pitches; 2-byte loads only)
   long cur_pitch, ref_pitch;   // in elements
@@ -345,9 +346,30 @@ struct PictureCompensateArgs {
   int block_l, bx, by;
   int tiles_y;                 // tiles of 16 rows per block (set by the launcher)
   const int16_t *mv;           // [by][bx][2]
+  const uint8_t *ref_idx;      // NULL: every block reads `ref`; else [by][bx], block b reads refs[ref_idx[b]] (every entry < the number of references set)
+  const int16_t *refs[MLT_MOTION_MAX_REFS_K];   // sample (0, 0) of the references of the table form, width x height each
+  long ref_pitches[MLT_MOTION_MAX_REFS_K];
+};
+// mlt_picture_predict_refs: quarter-sample refinement of every reference's integer winner and the per-block choice among the references
+struct MotionRefineArgs {
+  const int16_t *cur;          // sample (0, 0) (2-byte loads only, as the references)
+  long cur_pitch;
+  const int16_t *refs[MLT_MOTION_MAX_REFS_K];
+  long ref_pitches[MLT_MOTION_MAX_REFS_K];
+  int n_refs;                  // 1 .. 4
+  int width, height;
+  int block_l, subpel, lambda; // subpel 0 / 1 / 2: candidates q in {0}, {-2, 0, 2}, {-3 .. 3} a side around 4 x the integer winner
+  int bx;                      // blocks per row (the grid is bx x by workgroups)
+  const int16_t *mv_int;       // the integer winners {4 dx, 4 dy}: slice r = mv_int + r * mv_int_slice, [by][bx][2]
+  size_t mv_int_slice;         // in elements
+  int16_t *mv;                 // [by][bx][2] out, 4-byte aligned
+  uint32_t *cost;              // [by][bx] out: cost_q
+  uint8_t *ref_out;            // [by][bx] out
 };
 int mlt_motion_search_lds(int block, int range);   // dynamic LDS bytes of motion_search_kernel: ((block + 2 range)^2 + block^2) x 2 + 32
+int mlt_motion_refine_lds(int block);              // ... of motion_refine_kernel: (block + 8) block x 4 + 128 + ((block + 8)^2 + block^2) x 2
 hipError_t mlt_launch_motion_search(const MotionSearchArgs &a, int by, hipStream_t st);
+hipError_t mlt_launch_motion_refine(const MotionRefineArgs &a, int by, hipStream_t st);
 hipError_t mlt_launch_picture_compensate(PictureCompensateArgs a, hipStream_t st);
 // ---- partition trees (mlt_predict_tree, mlt_predict_trees): the quadtree descent between two network levels (mlt_tree_kernels.inc).  The arena is LEVEL-MAJOR
 // over the pictures of the call (mlt_predict_tree: one) -- level l is one node range, picture 0's segment, then picture 1's, ...; a segment in the contract's order

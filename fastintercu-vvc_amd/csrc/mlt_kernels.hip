@@ -780,6 +780,14 @@ hipError_t mlt_launch_motion_search(const MotionSearchArgs &a, int by, hipStream
   return launch_big_lds<motion_search_kernel>(dim3((unsigned)a.bx, (unsigned)by), dim3(256), mlt_motion_search_lds(block, a.range), st, a);
 }
 
+// one workgroup per block; 37,120 bytes of LDS at block 64, 3,328 at block 16: the plain launch path
+int mlt_motion_refine_lds(int block) { const int wp = block + 8; return wp * block * 4 + 128 + (wp * wp + block * block) * 2; }
+hipError_t mlt_launch_motion_refine(const MotionRefineArgs &a, int by, hipStream_t st) {
+  if (a.block_l < 3 || a.block_l > 6 || a.subpel < 0 || a.subpel > 2 || a.n_refs < 1 || a.n_refs > MLT_MOTION_MAX_REFS_K || a.bx < 1 || by < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(motion_refine_kernel, dim3((unsigned)a.bx, (unsigned)by), dim3(256), mlt_motion_refine_lds(1 << a.block_l), st, a);
+  return hipGetLastError();
+}
+
 // one workgroup per tile of at most 16 rows x 64 columns of a block
 hipError_t mlt_launch_picture_compensate(PictureCompensateArgs a, hipStream_t st) {
   if (a.block_l < 3 || a.block_l > 6 || a.bx < 1 || a.by < 1) return hipErrorInvalidValue;

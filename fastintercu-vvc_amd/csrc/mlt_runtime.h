@@ -5,7 +5,7 @@
 //   mlt_api.cpp        init / shutdown / stream, the predict entry points, deferred prediction, confidence gate, profile
 //   mlt_pictures.cpp   device-resident pictures: create / upload / wrap / destroy, mlt_predict_at, mlt_grid_positions
 //   mlt_tree.cpp       partition trees of a picture: mlt_predict_tree, mlt_predict_trees, mlt_predict_tree_sweep, mlt_predict_trees_sweep, mlt_tree_roots, mlt_tree_max_nodes
-//   mlt_motion.cpp     prediction pictures: mlt_motion_blocks, mlt_picture_download, mlt_picture_compensate, mlt_picture_predict
+//   mlt_motion.cpp     prediction pictures: mlt_motion_blocks, mlt_picture_download, mlt_picture_compensate, mlt_picture_predict and their _refs forms
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -305,7 +305,7 @@ struct mlt_ctx {
   // mlt_predict_tree's / mlt_predict_trees' device arena (Lay::TreeArena) or mlt_predict_tree_sweep's / mlt_predict_trees_sweep's (Lay::TreeSweepArena), and the pinned count
   GrowBuf tree_dev;
   int32_t *tree_host = nullptr;
-  GrowBuf motion_dev;   // mlt_picture_predict / mlt_picture_compensate (mlt_motion.cpp): this device's motion field [by][bx][2] int16, then the costs [by][bx] uint32
+  GrowBuf motion_dev;   // mlt_picture_predict / mlt_picture_compensate and their _refs forms (mlt_motion.cpp: FieldBuf, RefsFieldBuf): this device's motion field(s)
   std::vector<mlt_picture *> pictures;  // every picture created on / wrapped for this context (mlt_pictures.cpp); what is left is released by mlt_shutdown
   std::string err;
   bool profile = false;
@@ -331,6 +331,7 @@ static_assert(sizeof(mlt_tree_node) == 32 && sizeof(TreeNodeRec) == 32 && offset
 static_assert(sizeof(mlt_tree_config) == 40, "mlt_tree_config is 40 bytes");
 static_assert(sizeof(mlt_tree_picture) == 24 && MLT_TREES_ROW == MLT_MAX_LOGITS && MLT_TREES_LEVELS == Lay::TreeArena::kLevels && sizeof(TreesEntry) == 48, "mlt_predict_trees layouts");
 
+static_assert(MLT_MOTION_MAX_REFS == MLT_MOTION_MAX_REFS_K && sizeof(mlt_motion_refs_config) == 24, "the motion kernels' reference arrays hold the ABI's maximum");
 static_assert(MLT_SWEEP_MAX_QPS == MLT_SWEEP_MAX_QPS_K, "the sweep kernel's point array holds the ABI's maximum");
 static_assert(sizeof(mlt_candidates) == 40 && sizeof(CandRec) == sizeof(mlt_candidates) && offsetof(mlt_candidates, order) == offsetof(CandRec, order) &&
               offsetof(mlt_candidates, prob) == offsetof(CandRec, prob) && offsetof(mlt_candidates, prob) == 16, "mlt_candidates layout");

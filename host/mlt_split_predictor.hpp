@@ -238,6 +238,23 @@ class SplitPredictor {
     cfg.struct_size = (uint32_t)sizeof cfg; cfg.block = block; cfg.range = range; cfg.lambda = lambda;
     return mlt_picture_predict(m_ctx, cur, ref, &cfg, dst, mvOut, costOut) == MLT_OK;
   }
+  // ... with quarter-sample refinement and a per-block choice among nRefs (1 .. MLT_MOTION_MAX_REFS) references (include/mltcnn.h: mlt_picture_predict_refs,
+  // mlt_picture_compensate_refs): every reference's integer winner is refined over the half (subpel 1) or quarter (subpel 2) sample window (0: none) and each block
+  // takes the best (reference, vector) by cost_q = 4 SADP + lambda (|mvx| + |mvy|).  refOut / refIdx [by][bx]: the blocks' reference indices (refIdx nullptr:
+  // refs[0] everywhere); costOut is cost_q.  false on failure, and dst is left alone.
+  bool compensatePictureRefs(const mlt_picture *const *refs, int nRefs, const int16_t *mv, const uint8_t *refIdx, mlt_picture *dst, int block = 16) {
+    if (!m_ctx) return false;
+    mlt_motion_refs_config cfg{};
+    cfg.struct_size = (uint32_t)sizeof cfg; cfg.block = block;
+    return mlt_picture_compensate_refs(m_ctx, refs, nRefs, &cfg, mv, refIdx, dst) == MLT_OK;
+  }
+  bool predictPictureRefs(const mlt_picture *cur, const mlt_picture *const *refs, int nRefs, mlt_picture *dst, int block = 16, int range = 16, int lambda = 0,
+                          int subpel = 2, int16_t *mvOut = nullptr, uint8_t *refOut = nullptr, uint32_t *costOut = nullptr) {
+    if (!m_ctx) return false;
+    mlt_motion_refs_config cfg{};
+    cfg.struct_size = (uint32_t)sizeof cfg; cfg.block = block; cfg.range = range; cfg.lambda = lambda; cfg.subpel = subpel;
+    return mlt_picture_predict_refs(m_ctx, cur, refs, nRefs, &cfg, dst, mvOut, refOut, costOut) == MLT_OK;
+  }
   // n CUs of cuw x cuw at xy[i] = {x, y} of the picture pair, one batch: splitModes[i] as predictSplitMode() returns it, and -- candOpt / decOpt != nullptr -- the
   // candidate and decision records beside it.  false on failure: every split mode -1, every candidate record keeps all classes (full RDO), no prediction in the
   // decision records.

@@ -577,7 +577,8 @@ int mlt_predict_trees_sweep(mlt_ctx *ctx, int n_pictures, const mlt_tree_picture
  * ERRORS    everything is checked before anything is enqueued; on an error dst and the host outputs stay untouched.  MLT_ERR_ARG: a NULL ctx, cfg, picture or
  *           field; a struct_size other than sizeof(mlt_motion_config); block, range, lambda or flags out of range; a picture of another context; pictures of
  *           unequal width or height; dst equal to ref or cur; a dst made by mlt_picture_wrap_device (that plane is the caller's and const).  No weights are needed.
- * Not there: sub-sample search, bi-prediction, per-block reference selection, chroma, motion fields that stay in device memory across calls. */
+ * Sub-sample refinement and a per-block choice among several references: mlt_picture_predict_refs / mlt_picture_compensate_refs below.
+ * Not there: bi-prediction, chroma, motion fields that stay in device memory across calls. */
 typedef struct mlt_motion_config {   /* 20 bytes */
   uint32_t struct_size;  /* = sizeof; anything else -> MLT_ERR_ARG */
   int32_t block;         /* 8 / 16 / 32 / 64; 0 => 16 */
@@ -600,6 +601,52 @@ int mlt_picture_compensate(mlt_ctx *ctx, const mlt_picture *ref, const mlt_motio
  * enqueueing. */
 int mlt_picture_predict(mlt_ctx *ctx, const mlt_picture *cur, const mlt_picture *ref, const mlt_motion_config *cfg, mlt_picture *dst,
                         int16_t *mv_out_opt, uint32_t *cost_out_opt);
+
+/* ---- Quarter-sample refinement and per-block reference choice (new exports; MLT_ABI_VERSION stays 4; nothing above changes) ----
+ * mlt_picture_predict stops at an integer-sample vector into one reference.  These two calls add the next rungs with ONE selection rule: the integer winner of
+ * every reference is refined over a window of fractional vectors, evaluated on the COMPENSATION RULE'S OWN OUTPUT, and each block takes the best (reference,
+ * vector).  Integer arithmetic only: the bytes are the same on every device and equal to motion.refine / motion.compensate_refs / motion.predict_refs.
+ * Blocks, the field layout, R(x, y) (clamped), the taps C[f] and  P_mv(x, y) = clip(0, 1023, (v + 2048) >> 12)  are exactly those of COMPENSATION above;
+ * P_mv^r is P_mv computed from refs[r].
+ *
+ * REFERENCES  refs[0 .. n_refs), 1 <= n_refs <= MLT_MOTION_MAX_REFS.  The same picture may be listed more than once.
+ * STEP 1      integer search, per reference r: SEARCH above, unchanged (its own rule, key and cost) -> (dx_r, dy_r).
+ * STEP 2      refinement, per reference r: the candidates mv = (4 dx_r + qx, 4 dy_r + qy) with qx, qy in Wd(subpel),
+ *               Wd(0) = { 0 }     Wd(1) = { -2, 0, 2 }     Wd(2) = { -3, ..., 3 }
+ *             -- 1, 9 or 49 candidates, exhaustive, no staged descent: no evaluation order can matter.
+ *               SADP   = sum over the block's clipped samples of |cur(x, y) - P_mv^r(x, y)|   (cur: the int16 values as they are)
+ *               cost_q = 4 * SADP + lambda * (|mvx| + |mvy|)   in uint32: 4 * 4096 * 33791 + 65535 * 518 < 2^32.
+ * STEP 3      the winner over all (r, mv) has the smallest (cost_q, |mvx| + |mvy|, r, mvy, mvx), compared lexicographically with mvy and mvx signed -- as one
+ *             unsigned 64-bit key: cost_q << 32 | l1 << 22 | r << 20 | (mvy + 512) << 10 | (mvx + 512)   (|mv| <= 259, l1 <= 518).
+ *             Outputs: the block's vector, its reference index, its cost_q.
+ * STEP 4      dst is, block by block, P_mv^r of the winner.
+ * CONSEQUENCES  cost_q is in QUARTER units and on CLIPPED samples: it equals 4 x the integer search's cost only while every reference sample the block touches
+ *             lies in 0 .. 1023.  With subpel = 0 and n_refs = 1 the vector field and dst are byte for byte mlt_picture_predict's.
+ * CONTRACTS   dst of mlt_picture_predict_refs is byte for byte mlt_picture_compensate_refs(refs, mv_out, ref_out); with n_refs = 1 also
+ *             mlt_picture_compensate(refs[0], mv_out).
+ * ORDER       as above: a call with a host output is synchronous, one without returns after enqueueing, in stream order; every device of a multi-device context
+ *             runs the call and produces identical bytes.  No weights are needed.
+ * ERRORS      everything is checked before anything is enqueued; on an error dst and the host outputs stay untouched.  MLT_ERR_ARG: everything the calls above
+ *             refuse, for EVERY reference; a struct_size other than sizeof(mlt_motion_refs_config); n_refs outside 1 .. MLT_MOTION_MAX_REFS; subpel outside
+ *             0 .. 2; a ref_idx entry >= n_refs (mlt_last_error names the block); dst equal to cur or to any reference.
+ * Not there: bi-prediction, chroma, motion fields that stay in device memory across calls. */
+#define MLT_MOTION_MAX_REFS 4
+typedef struct mlt_motion_refs_config {   /* 24 bytes */
+  uint32_t struct_size;  /* = sizeof; anything else -> MLT_ERR_ARG */
+  int32_t block;         /* as mlt_motion_config */
+  int32_t range;         /* search only, as mlt_motion_config */
+  int32_t lambda;        /* search only: the integer search's lambda AND cost_q's, 0 <= lambda <= 65535 */
+  int32_t subpel;        /* search only: 0 integer / 1 half / 2 quarter refinement window */
+  uint32_t flags;        /* 0; anything else -> MLT_ERR_ARG */
+} mlt_motion_refs_config;
+/* Steps 1 - 4.  mv_out_opt ([by][bx][2]), ref_out_opt ([by][bx]) and cost_out_opt ([by][bx], cost_q) are HOST arrays or NULL; with any of them the call is
+ * synchronous, with none it returns after enqueueing. */
+int mlt_picture_predict_refs(mlt_ctx *ctx, const mlt_picture *cur, const mlt_picture *const *refs, int n_refs, const mlt_motion_refs_config *cfg,
+                             mlt_picture *dst, int16_t *mv_out_opt, uint8_t *ref_out_opt, uint32_t *cost_out_opt);
+/* Step 4 alone: dst <- block by block the compensation of refs[ref_idx[block]] with the HOST field mv (cfg->block; range, lambda and subpel are not read).
+ * ref_idx_opt: HOST [by][bx], NULL = every block reads refs[0].  Returns once mv and ref_idx_opt may be reused. */
+int mlt_picture_compensate_refs(mlt_ctx *ctx, const mlt_picture *const *refs, int n_refs, const mlt_motion_refs_config *cfg, const int16_t *mv /* HOST */,
+                                const uint8_t *ref_idx_opt /* HOST */, mlt_picture *dst);
 
 int mlt_synchronize(mlt_ctx *ctx);
 

@@ -36,6 +36,10 @@ BLOCK blocks, cost SAD + LAMBDA (|dx| + |dy|), then quarter-sample compensation;
 With --frames N the second file holds N frames like the first and frame f's reference is its frame f - 1, frame 0's its frame 0 (pass the originals' file twice
 for a GOP of originals: every frame is then predicted from its predecessor and frame 0 from itself).  Without --motion nothing changes.
 
+--motion-refine SUBPEL[,NREFS] (with --motion only): the prediction comes from MltCnn.predict_picture_refs instead -- the integer winner refined over the half
+(SUBPEL 1) or quarter (SUBPEL 2) sample window (0: none), each block choosing among NREFS (1 .. 4, default 1) references: with --frames N frame f's references
+are frames f - 1, f - 2, ... of the second file, clipped at frame 0; a single frame is listed NREFS times.
+
   python tools/picture_map.py cur.npy ref.npy --motion 16,16 --synthetic 10 --tree --out maps/frame8
 
 File reading and grid logic (read_picture, grid, to_map, histogram) need neither a device nor the library; run_maps needs the MI355X."""
@@ -192,11 +196,20 @@ def motion_references(second: np.ndarray) -> list:
     return [second[max(f - 1, 0)] for f in range(second.shape[0])]
 
 
+def motion_reference_lists(second: np.ndarray, n_refs: int) -> list:
+    """--motion-refine: the n_refs reference frames of every frame -- [frames, height, width]: frames f - 1, f - 2, ..., clipped at frame 0; [height, width]:
+    that frame n_refs times."""
+    if second.ndim == 2:
+        return [[second] * n_refs]
+    return [[second[max(f - 1 - k, 0)] for k in range(n_refs)] for f in range(second.shape[0])]
+
+
 @contextlib.contextmanager
 def uploaded(m, org: np.ndarray, pred: np.ndarray, motion=None):
     """The frames of org / pred ([height, width] or [frames, height, width]) as resident picture pairs [(org_pic, pred_pic), ...], closed on exit.
     motion = (block, range, lambda): `pred` holds REFERENCE frames instead (motion_references) and every pred_pic is built on the device from the frame's original
-    and its reference (MltCnn.predict_picture, enqueued only: the calls that follow see it in stream order)."""
+    and its reference (MltCnn.predict_picture, enqueued only: the calls that follow see it in stream order); motion = (block, range, lambda, subpel, n_refs):
+    from its n_refs references (motion_reference_lists) with refinement (MltCnn.predict_picture_refs)."""
     assert org.shape == pred.shape
     height, width = org.shape[-2:]
     held, pics = [], []
@@ -205,6 +218,13 @@ def uploaded(m, org: np.ndarray, pred: np.ndarray, motion=None):
             for o, p in zip(org.reshape(-1, height, width), pred.reshape(-1, height, width)):
                 held += [m.picture(width, height).upload(o), m.picture(width, height).upload(p)]
                 pics.append((held[-2], held[-1]))
+        elif len(motion) == 5:
+            block, search_range, lam, subpel, n_refs = motion
+            for o, refs in zip(org.reshape(-1, height, width), motion_reference_lists(pred, n_refs)):
+                first = len(held)
+                held += [m.picture(width, height).upload(o)] + [m.picture(width, height).upload(r) for r in refs] + [m.picture(width, height)]
+                m.predict_picture_refs(held[first], held[first + 1:-1], held[-1], block=block, search_range=search_range, lam=lam, subpel=subpel, want_field=False)
+                pics.append((held[first], held[-1]))
         else:
             block, search_range, lam = motion
             for o, r in zip(org.reshape(-1, height, width), motion_references(pred)):
@@ -227,6 +247,17 @@ def parse_motion(text: str) -> tuple:
     if len(v) not in (2, 3) or v[0] not in (8, 16, 32, 64) or not 0 <= v[1] <= 64 or (len(v) == 3 and not 0 <= v[2] <= 65535):
         raise ValueError(f"--motion {text}: want BLOCK,RANGE[,LAMBDA] with BLOCK of 8,16,32,64, 0 <= RANGE <= 64, 0 <= LAMBDA <= 65535")
     return (v[0], v[1], v[2] if len(v) == 3 else 0)
+
+
+def parse_motion_refine(text: str) -> tuple:
+    """"2" or "2,3" -> (subpel, n_refs): subpel 0 / 1 / 2, 1 <= n_refs <= 4 (default 1)."""
+    try:
+        v = tuple(int(t) for t in text.split(","))
+    except ValueError:
+        raise ValueError(f"--motion-refine {text}: want SUBPEL[,NREFS] as integers") from None
+    if len(v) not in (1, 2) or v[0] not in (0, 1, 2) or (len(v) == 2 and not 1 <= v[1] <= 4):
+        raise ValueError(f"--motion-refine {text}: want SUBPEL[,NREFS] with SUBPEL of 0,1,2 and 1 <= NREFS <= 4")
+    return (v[0], v[1] if len(v) == 2 else 1)
 
 
 def run_tree(m, org: np.ndarray, pred: np.ndarray, poc: int, qp: int, min_size: int = 16, motion=None) -> dict:
@@ -300,6 +331,7 @@ def parse_args(argv=None):
     ap.add_argument("--gop-qps", default=None, help="with --tree --frames N: comma-separated base QPs, one tree per (frame, QP) from one call")
     ap.add_argument("--qp-offsets", default=None, help="with --gop-qps: one QP offset per frame, comma-separated (default 0)")
     ap.add_argument("--motion", default=None, help="BLOCK,RANGE[,LAMBDA]: the second file is the REFERENCE frame; the prediction is built on the device")
+    ap.add_argument("--motion-refine", default=None, help="with --motion: SUBPEL[,NREFS] -- half (1) / quarter (2) sample refinement, per-block choice among NREFS references")
     args = ap.parse_args(argv)
     sizes = tuple(int(s) for s in args.sizes.split(",") if s)
     if not sizes or any(s not in SIZES for s in sizes) or (args.weights_dir is None) == (args.synthetic is None):
@@ -312,6 +344,13 @@ def parse_args(argv=None):
     if args.motion is not None:
         try:
             args.motion_cfg = parse_motion(args.motion)
+        except ValueError as e:
+            ap.error(str(e))
+    if args.motion_refine is not None:
+        if args.motion_cfg is None:
+            ap.error("--motion-refine goes with --motion")
+        try:
+            args.motion_cfg += parse_motion_refine(args.motion_refine)
         except ValueError as e:
             ap.error(str(e))
     args.qp_list = None
