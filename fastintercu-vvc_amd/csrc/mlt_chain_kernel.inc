@@ -74,6 +74,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a) {
   constexpr int CBT = WCB * WAVES_C, CT = 32 * CBT, NPASS = C / CT, NW = WAVES_C * WAVES_P;
   constexpr int H = 1 << HL, HW = H * H, M = HW << SPW_L;
   static_assert(C % CT == 0 && NPASS <= 2 && M == 32 * WAVES_P * WPB && HW >= 32 && C % KC == 0, "tiling");
+  static_assert(NCONV == 3, "the chain is a stage's three stride-1 convs (mlt_launch_chain launches no other)");
   static_assert(GT_LAST == GT || RB == 2, "a shorter last tap group issues fewer ring pieces: only with the uncounted vmcnt(0) wait of a 2-deep ring");
   constexpr int WP = (W2 && !LO8) ? 2 : 1, WPLANE = GT * KS * CBT * 1024;  // fp16 weight planes per step, bytes of one plane of a step
   constexpr int WLO8 = LO8 ? GT * CBT * 2048 : 0;                           // FP8 lo plane of a step: 2 KiB per (tap, 32-cout block)
@@ -194,11 +195,11 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a) {
           glds16(wsrc + (size_t)((ps * NCHUNK + r_ci) * (TAPS * KS) + r_gi * WI) * (CBT * 1024) + pw * 1024 + lane16, dst + pi * 1024);
         }
       } else {
-        const char *wsrc = (const char *)(r_cv == 0 ? a.cv[0].w : r_cv == 1 ? a.cv[1].w : a.cv[NCONV > 2 ? 2 : 1].w);
+        const char *wsrc = (const char *)(r_cv == 0 ? a.cv[0].w : r_cv == 1 ? a.cv[1].w : a.cv[2].w);
         const char *src = wsrc + (size_t)((r_ps * NCHUNK + r_ci) * TAPS + r_gi * GT) * (KS * CBT * 1024);
         char *dst = ring + slot_wr * WCHUNK;
         const int npiece = (GT_LAST != GT && r_gi == NG - 1) ? GT_LAST * KS * CBT : NPIECE;  // (never read behind the layer's last tap)
-        const size_t wlo = W2 ? (r_cv == 0 ? a.cv[0].w_lo_off : r_cv == 1 ? a.cv[1].w_lo_off : a.cv[NCONV > 2 ? 2 : 1].w_lo_off) : 0;
+        const size_t wlo = W2 ? (r_cv == 0 ? a.cv[0].w_lo_off : r_cv == 1 ? a.cv[1].w_lo_off : a.cv[2].w_lo_off) : 0;
 #pragma unroll
         for (int k = 0; k < PPWR; ++k) {
           int pi = wave + k * NWR;
@@ -606,12 +607,11 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a) {
       constexpr int cvi = decltype(kc)::value;
       constexpr bool lastc = cvi == NCONV - 1;
       const ChainConv &cv = a.cv[cvi];
-      // the two chains there are (host: run_chain): NCONV == 3: conv2(+sc from HBM, saved) -> conv1 -> conv2(+saved tile);
-      // NCONV == 2: conv1 -> conv2(+x from HBM); every conv is followed by a ReLU
+      // the chain (host: run_chain3): conv2(+sc from HBM, saved) -> conv1 -> conv2(+saved tile); every conv is followed by a ReLU
       // (S2: conv 0's residual sc is not in HBM but in the registers the stride-2 phase left it in)
       // (KEEP = false: b0 goes through HBM instead of the registers: conv 0 stores it, the last conv loads it as cv.res)
-      constexpr int RES = NCONV == 3 ? (cvi == 0 ? (S2 ? 2 : 1) : cvi == 2 ? (KEEP ? 2 : 1) : 0) : (cvi == 1 ? 1 : 0);
-      constexpr bool SAVE = KEEP && NCONV == 3 && cvi == 0;
+      constexpr int RES = cvi == 0 ? (S2 ? 2 : 1) : cvi == 2 ? (KEEP ? 2 : 1) : 0;
+      constexpr bool SAVE = KEEP && cvi == 0;
       constexpr bool RES_LATE = !KEEP;  // residual loads after the last step's MFMA loop (the fragment registers are free then)
       uint4v hold[WCB][WPB][2];  // NPASS == 2: pass 0's activated tile until pass 1 has finished reading the buffer
       // epilogue of the stage's last conv for cout pass kp: + bias + residual, ReLU -> HBM and / or GAP sums

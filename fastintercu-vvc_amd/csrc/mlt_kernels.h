@@ -61,7 +61,7 @@ struct ConvArgs {
                                // B operand lanes 32-63 (e4m3 Xl: 127 - MLT_XL_LO_EXP); B lanes 0-31 (e4m3 Xh) are unscaled
 };
 
-struct ConvCfg { int kc, ct, mt, gt, dma, mt_dma, lat, gt_w2; };  // gt_w2 (exact packing only): taps per weight step of the hi+lo-WEIGHTS tier (NSPLIT = 3)  // cin chunk, couts / pixels per workgroup, taps per weight step, LDS-DMA staging variant (0 none, 1 resident, 2 ring) and its pixels per workgroup
+struct ConvCfg { int kc, ct, mt, gt, dma, mt_dma, lat, gt_w2; };  // gt_w2: taps per weight step of the layer's (nsplit 4, DEFAULT) row -- the hi+lo-WEIGHTS tier on the fast tiling --, 0 where the layer has none  // cin chunk, couts / pixels per workgroup, taps per weight step, LDS-DMA staging variant (0 none, 1 resident, 2 ring) and its pixels per workgroup
 
 struct Stem5Args {
   const int16_t *org, *pred;   // Pel planes
@@ -171,7 +171,7 @@ struct ChainArgs {
   float s2_scale;
   const void *zero;    // >= 64 KiB of zeros (padding source of the patch DMA)
   ChainConv cv[3];
-  int nconv;           // 2 or 3
+  int nconv;           // 3: the launchers refuse any other, no kernel reads it
   void *y;             // [n][H][H][C] fp16 output of the last conv, or NULL (only the GAP sums are needed)
   int y_c16;           // y chunk-major (ConvArgs.y_c16)
   int x_c16;           // S2: the stage input x is chunk-major
@@ -502,7 +502,7 @@ hipError_t mlt_launch_guard_scatter(const GuardScatterArgs &a, hipStream_t st);
 
 enum { MLT_CONV_DEFAULT = 0, MLT_CONV_DMA = 1, MLT_CONV_LATENCY = 2, MLT_CONV_CENTRE = 3 };  // kernel variant of a layer shape
 bool mlt_conv_has_centre_variant(int cin, int cout);  // 1x1 (centre-tap) instantiation for stride-1 layers on 1x1 maps
-hipError_t mlt_launch_conv(int cin, int cout, int stride, int nsplit, int variant, const ConvArgs &a, int grid_x, int extra_lds, hipStream_t st);  // nsplit: 1 fast, 2 exact, 3 weights hi+lo only (exact tiling), 4 weights hi+lo on the FAST tiling (MLT_MODEL_W2)
+hipError_t mlt_launch_conv(int cin, int cout, int stride, int nsplit, int variant, const ConvArgs &a, int grid_x, hipStream_t st);  // nsplit: 1 fast, 2 exact, 4 weights hi+lo on the FAST tiling (MLT_MODEL_W2), 6 exact-lite; any other, or a key without a row, is refused
 bool mlt_conv_cfg(int cin, int cout, int stride, int exact, ConvCfg *out);
 int mlt_conv_ring_bytes(int cin, int cout, int stride, int nsplit, int variant);  // LDS bytes of the weight ring of the kernel mlt_launch_conv selects for the key (-1: none)
 hipError_t mlt_launch_stem5(const Stem5Args &a, int nsplit, int grid_x, int lds, hipStream_t st);  // nsplit as mlt_launch_conv

@@ -324,8 +324,8 @@ template <auto KERN, class ARGS> static hipError_t launch_big_lds(dim3 grid, dim
 // the host reads and is not copied from them, table_consistent() checks at compile time.
 // Measurement history of the tilings: docs/KERNEL_NOTES.md ("Per-conv tilings").
 struct ConvRow {
-  int cin, cout, stride, nsplit, variant;  // key.  nsplit: 1 fast, 2 exact (weights and activations hi+lo), 3 weights hi+lo on the exact packing,
-                                           // 4 weights hi+lo on the FAST packing (MLT_MODEL_W2), 6 exact-lite; variant: MLT_CONV_*
+  int cin, cout, stride, nsplit, variant;  // key.  nsplit: 1 fast, 2 exact (weights and activations hi+lo), 4 weights hi+lo on the FAST packing (MLT_MODEL_W2),
+                                           // 6 exact-lite; variant: MLT_CONV_*
   bool ring;                               // conv_ring_dma_kernel (else conv_mfma_kernel)
   int taps; bool sc; int kc, kn, wcb, wpb, wc, wp, gt, rb, un, minw; bool dma; int cbp; bool kmaj;  // TAPS SC KC NSPLIT WCB WPB WAVES_C WAVES_P GT RB UN|UNP MINW DMA CBP KMAJ
   int nwl, fd;                             // ring only: NWL FD
@@ -342,45 +342,44 @@ constexpr ConvRow ring_row(int cin, int cout, int stride, int nsplit, int varian
 constexpr int DEF = MLT_CONV_DEFAULT, DMA = MLT_CONV_DMA, LAT = MLT_CONV_LATENCY, CEN = MLT_CONV_CENTRE;
 // stride-2 convs always carry their block's projection shortcut (layer0.0's lives in stem5_kernel).
 // A tiling that several instantiations share is written ONCE and copied by add_fast / add_exact:
-//  - the exact tiling of a layer (nsplit 2) also runs exact-lite (6) and hi+lo weights on the exact packing (3): the host sizes tiles and patches of all three
-//    from the nsplit-2 row, so they are one description;
-//  - the hi+lo-weights tier of a layer whose cin chunk is 32 in both packings has a DEFAULT row with the FAST tiling (all taps resident + persistent workgroups for
-//    the 32-channel layers; w2_gt taps per ring step for the two big stride-2 layers: two weight planes, 5 would not fit the ring) -- the host sizes its tiles from
-//    the fast row; the exact tiling's nsplit-3 copy of such a layer is then keyed under DMA (what (nsplit 3, DMA | LATENCY) selects; no plan asks for it).
+//  - the exact tiling of a layer (nsplit 2) also runs exact-lite (6): the host sizes tiles and patches of both from the nsplit-2 row, so they are one description;
+//  - the hi+lo-weights tier (nsplit 4) of a layer whose cin chunk is 32 in both packings has a DEFAULT row with the FAST tiling (all taps resident + persistent
+//    workgroups for the 32-channel layers; w2_gt taps per ring step for the two big stride-2 layers: two weight planes, 5 would not fit the ring) -- the host sizes
+//    its tiles from the fast row.  Its kernel is the NSPLIT = 3 form (weights hi+lo, fp16 lo plane).
+// Every row is a kernel some caller can ask for: mlt_launch_conv is asked with nsplit 1, 2, 4 or 6, and no row has another.
 struct ConvTable {
-  ConvRow r[80] = {};  // (make_table fills 71)
+  ConvRow r[64] = {};  // (make_table fills 61)
   int n = 0;
   constexpr void add(ConvRow x) { r[n++] = x; }
   constexpr const ConvRow *begin() const { return r; }
   constexpr const ConvRow *end() const { return r + n; }
-  constexpr void add_as(ConvRow x, int nsplit, int variant) { x.nsplit = x.kn = nsplit; x.variant = variant; add(x); }
   constexpr void add_fast(ConvRow x, int w2_gt = 0) {  // x: the nsplit-1 DEFAULT row; w2_gt > 0: + the hi+lo-weights tier on this tiling
     add(x);
-    if (w2_gt) { x.gt = w2_gt; add_as(x, 3, MLT_CONV_DEFAULT); }
+    if (w2_gt) { x.nsplit = 4; x.kn = 3; x.gt = w2_gt; add(x); }
   }
-  constexpr void add_exact(ConvRow x, int v3 = MLT_CONV_DEFAULT) {  // x: the nsplit-2 row (DEFAULT or LATENCY); v3: the key of the nsplit-3 copy of a DEFAULT row
+  constexpr void add_exact(ConvRow x) {  // x: the nsplit-2 row (DEFAULT or LATENCY)
     add(x);
-    add_as(x, 6, x.variant);
-    if (x.variant == MLT_CONV_DEFAULT) add_as(x, 3, v3);
+    x.nsplit = x.kn = 6;
+    add(x);
   }
 };
 constexpr ConvTable make_table() {
   ConvTable t;
   // ---- throughput tilings.  Fast: the layer's own tiling.  Exact: 32-channel chunks, two-deep ring; the >= 128-channel stride-1 layers on 128-pixel tiles
   // (these kernels serve the small-CU models, whose maps are tiny).
-  //                  cin cout s  ns var TAPS SC    KC NS WCB WPB WC WP GT RB UN MINW   w2_gt | v3
+  //                  cin cout s  ns var TAPS SC    KC NS WCB WPB WC WP GT RB UN MINW   w2_gt
   t.add_fast(mfma_row(32, 32, 1, 1, DEF, 9, false, 32, 1, 1, 2, 1, 8, 9, 1, 5, 1), 9);       // all nine taps resident, persistent workgroups
-  t.add_exact(mfma_row(32, 32, 1, 2, DEF, 9, false, 32, 2, 1, 2, 1, 8, 3, 2, 5, 1), DMA);    // UN 5: the 128 model's tiles have 4.4 - 4.8 patch items per lane
+  t.add_exact(mfma_row(32, 32, 1, 2, DEF, 9, false, 32, 2, 1, 2, 1, 8, 3, 2, 5, 1));         // UN 5: the 128 model's tiles have 4.4 - 4.8 patch items per lane
   t.add_fast(mfma_row(32, 64, 2, 1, DEF, 9, true, 32, 1, 1, 1, 2, 4, 10, 1, 5, 1), 10);      // all ten weight taps resident
-  t.add_exact(mfma_row(32, 64, 2, 2, DEF, 9, true, 32, 2, 1, 1, 2, 4, 2, 2, 5, 1), DMA);     // 2 taps per step: 5 do not fit the LDS beside two activation planes
+  t.add_exact(mfma_row(32, 64, 2, 2, DEF, 9, true, 32, 2, 1, 1, 2, 4, 2, 2, 5, 1));          // 2 taps per step: 5 do not fit the LDS beside two activation planes
   t.add_fast(mfma_row(64, 64, 1, 1, DEF, 9, false, 64, 1, 2, 1, 1, 8, 9, 2, 6, 1));          // all weights of a 64-channel chunk resident (chain_kernel<64> reads this packing)
   t.add_exact(mfma_row(64, 64, 1, 2, DEF, 9, false, 32, 2, 2, 1, 1, 8, 1, 2, 3, 1));
   t.add_fast(mfma_row(64, 128, 2, 1, DEF, 9, true, 32, 1, 2, 1, 2, 4, 2, 2, 5, 1), 2);
-  t.add_exact(mfma_row(64, 128, 2, 2, DEF, 9, true, 32, 2, 2, 1, 2, 4, 2, 2, 3, 1), DMA);    // UN 3: the 64 / 128-channel stride-2 layers lose with 5
+  t.add_exact(mfma_row(64, 128, 2, 2, DEF, 9, true, 32, 2, 2, 1, 2, 4, 2, 2, 3, 1));         // UN 3: the 64 / 128-channel stride-2 layers lose with 5
   t.add_fast(mfma_row(128, 128, 1, 1, DEF, 9, false, 64, 1, 2, 1, 2, 8, 3, 2, 3, 1));        // one 16-wave workgroup per CU on 256-pixel tiles, 48 KiB weight steps (chain_kernel<128> reads this packing)
   t.add_exact(mfma_row(128, 128, 1, 2, DEF, 9, false, 32, 2, 2, 1, 2, 4, 1, 2, 2, 1));
   t.add_fast(mfma_row(128, 256, 2, 1, DEF, 9, true, 32, 1, 2, 1, 2, 4, 5, 2, 5, 1), 2);
-  t.add_exact(mfma_row(128, 256, 2, 2, DEF, 9, true, 32, 2, 2, 1, 2, 4, 2, 2, 3, 1), DMA);
+  t.add_exact(mfma_row(128, 256, 2, 2, DEF, 9, true, 32, 2, 2, 1, 2, 4, 2, 2, 3, 1));
   t.add_fast(mfma_row(256, 256, 1, 1, DEF, 9, false, 64, 1, 2, 1, 2, 8, 3, 2, 4, 1));        // (chain_kernel<256> reads this packing)
   t.add_exact(mfma_row(256, 256, 1, 2, DEF, 9, false, 32, 2, 2, 1, 2, 4, 1, 2, 2, 1));
   // CU model (planes 32 / 64 / 96 / 128 / 256)
@@ -426,26 +425,18 @@ constexpr ConvTable make_table() {
 }
 constexpr ConvTable kTable = make_table();
 constexpr int kNumRows = kTable.n;
-constexpr const ConvRow (&kRows)[80] = kTable.r;  // (rows kNumRows .. 79 are unused)
+constexpr const ConvRow (&kRows)[64] = kTable.r;  // (rows kNumRows .. 63 are unused)
 
 constexpr int find_row(int cin, int cout, int stride, int nsplit, int variant) {
   for (int i = 0; i < kNumRows; ++i)
     if (kRows[i].cin == cin && kRows[i].cout == cout && kRows[i].stride == stride && kRows[i].nsplit == nsplit && kRows[i].variant == variant) return i;
   return -1;
 }
-// hi+lo weights on the fast packing: every layer but the stride-1 ones with >= 64 channels has ONE tiling for both packings (same kc / ct), so its
-// bytes are those of the exact packing and it runs that tier's (nsplit 3) row
-constexpr bool w2_runs_exact_tier(int cin, int cout, int stride) { return !(stride == 1 && cin == cout && cin >= 64); }
-// The row of a key, or -1: a pure function of the key.  A variant without a row of its own for the key is refused, except that DMA -- and, for nsplit 3,
-// LATENCY, which asks as DMA does -- falls back to the DEFAULT row.
+// The row of a key, or -1: a pure function of the key.  A variant without a row of its own for the key is refused, except that DMA falls back to the
+// DEFAULT row -- but not for nsplit 4: the hi+lo-weights tier has no LDS-DMA staging, and run_conv never asks for it.
 constexpr int select_row(int cin, int cout, int stride, int nsplit, int variant) {
-  if (nsplit == 4 && w2_runs_exact_tier(cin, cout, stride)) {
-    if (variant != MLT_CONV_DEFAULT) return -1;
-    nsplit = 3;
-  }
-  if (nsplit == 3 && variant == MLT_CONV_LATENCY) variant = MLT_CONV_DMA;
   const int i = find_row(cin, cout, stride, nsplit, variant);
-  return (i < 0 && variant == MLT_CONV_DMA) ? find_row(cin, cout, stride, nsplit, MLT_CONV_DEFAULT) : i;
+  return (i < 0 && variant == MLT_CONV_DMA && nsplit != 4) ? find_row(cin, cout, stride, nsplit, MLT_CONV_DEFAULT) : i;
 }
 
 // launch geometry of a row
@@ -457,14 +448,14 @@ constexpr int row_ring_bytes(const ConvRow &r) {  // the weight ring: slots x (w
   const int nbuf = (r.taps + (r.sc ? 1 : 0)) / r.gt > 1 ? r.rb : 1;
   return nbuf * ((r.kn == 2 || r.kn == 3 || r.kn == 6 ? 2 : 1) * plane + (r.kn == 5 ? r.gt * r.cbt() * 2048 : 0));
 }
-constexpr int row_lds(const ConvRow &r, int patch_bytes, int extra_lds) {
+constexpr int row_lds(const ConvRow &r, int patch_bytes) {
   if (r.ring) return 2 * patch_bytes + row_ring_bytes(r) + (r.nwl ? 32 * r.cbt() * 4 * (r.sc ? 2 : 1) : 0);
   // (kernel NSPLIT 5: + the e4m3 copy of the patch, 80 bytes per pixel of the fp16 patch's KC * 2 + 16)
   const int patch8 = r.kn == 5 ? ((patch_bytes / (r.kc * 2 + 16) + 1) * (r.kc + 16) + 1023) / 1024 * 1024 : 0;
-  return ((r.dma || r.kn == 2 || r.kn == 6) ? 2 : 1) * patch_bytes + row_ring_bytes(r) + patch8 + extra_lds;
+  return ((r.dma || r.kn == 2 || r.kn == 6) ? 2 : 1) * patch_bytes + row_ring_bytes(r) + patch8;
 }
-constexpr bool row_accepts(const ConvRow &r, int patch_bytes, int extra_lds) {
-  if (row_lds(r, patch_bytes, extra_lds) > kBigLds) return false;
+constexpr bool row_accepts(const ConvRow &r, int patch_bytes) {
+  if (row_lds(r, patch_bytes) > kBigLds) return false;
   const int nw = r.wc * r.wp, nwp = r.nwl ? r.nwl - r.nwl / 2 : nw - nw / 2;  // ring: the patch waves issue at most UNP 1 KiB pieces each per stage
   return !r.ring || (patch_bytes >> 10) <= r.un * nwp;
 }
@@ -475,7 +466,7 @@ constexpr bool row_accepts(const ConvRow &r, int patch_bytes, int extra_lds) {
 constexpr bool weights_resident(const ConvRow &r, int gt) { return gt == r.taps + (r.sc ? 1 : 0) && r.cin == r.kc; }  // (the kernels' W_RESIDENT: persistent workgroups)
 constexpr bool table_consistent() {
   for (const ConvRow &r : kTable) {
-    // -- the weights: every row reads them as the DEFAULT row of its packing (fast: nsplit 1 and 4; exact: 2, 3 and 6) tiles them -- same cin chunk, same
+    // -- the weights: every row reads them as the DEFAULT row of its packing (fast: nsplit 1 and 4; exact: 2 and 6) tiles them -- same cin chunk, same
     //    32-cout blocks per tile; a latency row's narrower tile names the packed tile's blocks in CBP (128-cout tiles, 64 for the 64-channel layer)
     const bool fast_packing = r.nsplit == 1 || r.nsplit == 4;
     const int b = find_row(r.cin, r.cout, r.stride, fast_packing ? 1 : 2, MLT_CONV_DEFAULT);
@@ -489,39 +480,38 @@ constexpr bool table_consistent() {
       const int d = find_row(r.cin, r.cout, r.stride, r.nsplit, MLT_CONV_DEFAULT);
       if (d < 0 || r.gt != 1 || r.mt() != kRows[d].mt()) return false;
     } else if (!r.ring) {
-      // (nsplit 3 is asked for through nsplit 4 -- hi+lo weights on the fast packing --, so its tiles are the fast row's; its taps per step reach the host
-      //  as gt_w2, read from the row itself)
-      const int v = find_row(r.cin, r.cout, r.stride, r.nsplit == 6 ? 2 : (r.nsplit == 3 && w2_runs_exact_tier(r.cin, r.cout, r.stride)) ? 1 : fast_packing ? 1 : 2, MLT_CONV_DEFAULT);
-      if (v < 0 || r.mt() != kRows[v].mt() || (r.nsplit != 3 && r.gt != kRows[v].gt)) return false;
+      // (the tiles of a hi+lo-weights row -- nsplit 4 -- are the fast row's; its taps per step reach the host as gt_w2, read from the row itself)
+      if (r.mt() != kRows[b].mt() || (r.nsplit != 4 && r.gt != kRows[b].gt)) return false;
     }
     if (r.variant == MLT_CONV_DEFAULT && r.nsplit == 1) {
-      // -- every layer has all four arithmetics, and the hi+lo-weights tier of the fast packing (nsplit 4 -> 3) finds the bytes it expects
-      const int e = find_row(r.cin, r.cout, r.stride, 2, MLT_CONV_DEFAULT), w = select_row(r.cin, r.cout, r.stride, 3, MLT_CONV_DEFAULT);
-      if (e < 0 || w < 0 || find_row(r.cin, r.cout, r.stride, 6, MLT_CONV_DEFAULT) < 0) return false;
-      if (w2_runs_exact_tier(r.cin, r.cout, r.stride) && (r.kc != kRows[e].kc || r.cbt() != kRows[e].cbt())) return false;
+      // -- every layer has the fast, the exact and the exact-lite arithmetic; where the hi+lo-weights tier runs on this tiling (a (nsplit 4, DEFAULT) row), the
+      //    layer has ONE tiling of the weights for both packings (same kc / ct), so that tier finds the bytes it expects in either
+      const int e = find_row(r.cin, r.cout, r.stride, 2, MLT_CONV_DEFAULT);
+      if (e < 0 || find_row(r.cin, r.cout, r.stride, 6, MLT_CONV_DEFAULT) < 0) return false;
+      if (find_row(r.cin, r.cout, r.stride, 4, MLT_CONV_DEFAULT) >= 0 && (r.kc != kRows[e].kc || r.cbt() != kRows[e].cbt())) return false;
     }
   }
   return true;
 }
 static_assert(table_consistent(), "a conv row disagrees with the packing or the tile of the rows the host reads for its layer (see table_consistent)");
 
-template <int I> static hipError_t launch_row(const ConvArgs &a, int grid_x, int extra_lds, hipStream_t st) {
+template <int I> static hipError_t launch_row(const ConvArgs &a, int grid_x, hipStream_t st) {
   constexpr ConvRow r = kRows[I];
-  if (!row_accepts(r, a.patch_bytes, extra_lds)) return hipErrorInvalidValue;
+  if (!row_accepts(r, a.patch_bytes)) return hipErrorInvalidValue;
   const dim3 grid(grid_x, row_grid_y(r)), block(row_threads(r));
-  const int lds = row_lds(r, a.patch_bytes, extra_lds);
+  const int lds = row_lds(r, a.patch_bytes);
   if constexpr (r.ring)
     return launch_big_lds<conv_ring_dma_kernel<r.cin, r.cout, r.stride, r.sc, r.kc, r.wcb, r.wpb, r.wc, r.wp, r.gt, r.rb, r.un, r.minw, r.nwl, r.fd>>(grid, block, lds, st, a);
   else
     return launch_big_lds<conv_mfma_kernel<r.cin, r.cout, r.stride, r.taps, r.sc, r.kc, r.kn, r.wcb, r.wpb, r.wc, r.wp, r.gt, r.rb, r.un, r.minw, r.dma, r.cbp, r.kmaj>>(grid, block, lds, st, a);
 }
-template <size_t... I> static hipError_t launch_rows(int row, std::index_sequence<I...>, const ConvArgs &a, int grid_x, int extra_lds, hipStream_t st) {
+template <size_t... I> static hipError_t launch_rows(int row, std::index_sequence<I...>, const ConvArgs &a, int grid_x, hipStream_t st) {
   hipError_t e = hipErrorInvalidValue;
-  (void)((row == (int)I && ((e = launch_row<(int)I>(a, grid_x, extra_lds, st)), true)) || ...);
+  (void)((row == (int)I && ((e = launch_row<(int)I>(a, grid_x, st)), true)) || ...);
   return e;
 }
-hipError_t mlt_launch_conv(int cin, int cout, int stride, int nsplit, int variant, const ConvArgs &a, int grid_x, int extra_lds, hipStream_t st) {
-  return launch_rows(select_row(cin, cout, stride, nsplit, variant), std::make_index_sequence<kNumRows>(), a, grid_x, extra_lds, st);
+hipError_t mlt_launch_conv(int cin, int cout, int stride, int nsplit, int variant, const ConvArgs &a, int grid_x, hipStream_t st) {
+  return launch_rows(select_row(cin, cout, stride, nsplit, variant), std::make_index_sequence<kNumRows>(), a, grid_x, st);
 }
 
 bool mlt_conv_has_centre_variant(int cin, int cout) {
@@ -543,13 +533,14 @@ bool mlt_conv_cfg(int cin, int cout, int stride, int exact, ConvCfg *out) {
   out->dma = (exact || d < 0) ? 0 : kRows[d].ring ? 2 : 1;
   out->mt_dma = (d >= 0 && kRows[d].ring) ? kRows[d].mt() : out->mt;
   out->lat = find_row(cin, cout, stride, ns, MLT_CONV_LATENCY) >= 0 ? 1 : 0;
-  out->gt_w2 = kRows[select_row(cin, cout, stride, 3, MLT_CONV_DEFAULT)].gt;  // taps per step of the row the hi+lo-weights tier launches
+  const int w = find_row(cin, cout, stride, 4, MLT_CONV_DEFAULT);  // the hi+lo-weights tier on the fast tiling: its own taps per step (0: the layer has no such row)
+  out->gt_w2 = w < 0 ? 0 : kRows[w].gt;
   return true;
 }
 
 // Host-only hook (not a product entry; no HIP call, no device): the table as text -- for the ten layer shapes, nsplit 1 / 2 / 3 / 4 / 6 and the four variants what
 // mlt_launch_conv selects (kernel family <template arguments in parameter order>, threads per workgroup, grid.y, dynamic LDS bytes at patch_bytes 1024 / 32768,
-// ring kernels: the largest patch_bytes, in KiB steps, the launcher accepts) or "rejected", and mlt_conv_cfg's view per shape.  tests/test_conv_table_cpu.py
+// ring kernels: the largest patch_bytes, in KiB steps, the launcher accepts) or "rejected" (nsplit 3, which once had rows, for every key), and mlt_conv_cfg's view per shape.  tests/test_conv_table_cpu.py
 // compares it with the text the launchers produced before they were table-driven.  Returns the length, or -1 when `cap` is too small.
 extern "C" __attribute__((visibility("default"))) int mlt_debug_conv_table(char *out, size_t cap) {
   static const char *const kVariant[] = {"default", "dma", "latency", "centre"};
@@ -574,10 +565,10 @@ extern "C" __attribute__((visibility("default"))) int mlt_debug_conv_table(char 
         const ConvRow &r = kRows[i];
         if (r.ring) put("ring<%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d>", r.cin, r.cout, r.stride, (int)r.sc, r.kc, r.wcb, r.wpb, r.wc, r.wp, r.gt, r.rb, r.un, r.minw, r.nwl, r.fd);
         else put("mfma<%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d>", r.cin, r.cout, r.stride, r.taps, (int)r.sc, r.kc, r.kn, r.wcb, r.wpb, r.wc, r.wp, r.gt, r.rb, r.un, r.minw, (int)r.dma, r.cbp, (int)r.kmaj);
-        put(" threads=%d grid_y=%d lds=%d/%d", row_threads(r), row_grid_y(r), row_lds(r, 1024, 0), row_lds(r, 32768, 0));
+        put(" threads=%d grid_y=%d lds=%d/%d", row_threads(r), row_grid_y(r), row_lds(r, 1024), row_lds(r, 32768));
         if (r.ring) {
           int kib = kBigLds / 1024;
-          while (kib > 0 && !row_accepts(r, kib * 1024, 0)) --kib;
+          while (kib > 0 && !row_accepts(r, kib * 1024)) --kib;
           put(" max_patch=%d", kib * 1024);
         }
         put("%s", "\n");
@@ -615,6 +606,7 @@ template <class K> static hipError_t launch_chain_t(K kern, DeviceOnce &once, co
 }
 template <auto KERN> static hipError_t launch_chain_t(const ChainArgs &a, int grid_x, int lds, hipStream_t st) { return launch_big_lds<KERN>(dim3(grid_x), dim3(512), lds, st, a); }
 hipError_t mlt_launch_chain(int c, int h, bool with_s2, bool oob_zero, bool w2, const ChainArgs &a, int grid_x, hipStream_t st) {
+  if (a.nconv != 3) return hipErrorInvalidValue;  // the chain is a stage's three stride-1 convs (run_chain3)
   // chain_kernel streams the weights as the stand-alone stride-1 layers' fast DEFAULT rows pack them
   constexpr ConvRow r64 = kRows[find_row(64, 64, 1, 1, MLT_CONV_DEFAULT)], r128 = kRows[find_row(128, 128, 1, 1, MLT_CONV_DEFAULT)], r256 = kRows[find_row(256, 256, 1, 1, MLT_CONV_DEFAULT)];
   static_assert(r64.kc == 64 && r64.wcb == 2 && r64.wc == 1 && r64.gt == 9, "chain_kernel<64,...> reads the packing of the stand-alone 64->64 layer");
@@ -622,7 +614,7 @@ hipError_t mlt_launch_chain(int c, int h, bool with_s2, bool oob_zero, bool w2, 
                 "chain_kernel reads the packing of the stand-alone 128->128 / 256->256 layers: 128-cout tiles, 64-channel chunks, 3 taps per step");
   constexpr int lds = 64 * 1024 + 2 * (r128.gt * (r128.kc / 16) * r128.cbt() * 1024);  // 64 KiB activation + two 48 KiB weight steps = all of the LDS
   if (w2) {  // hi+lo-weights forms (MLT_MODEL_W2 packing: the fast tiling, two planes): one tap per ring step, conv padding from beyond the LDS only
-    if (!oob_zero || with_s2 || a.nconv != 3) return hipErrorInvalidValue;
+    if (!oob_zero || with_s2) return hipErrorInvalidValue;
     // ring step = hi fp16 plane + FP8 lo plane (LO8): 8 + 4 KiB per tap (64 channels), 16 + 8 KiB (128 / 256)
     if (c == 64 && h == 32)   // 128 KiB sample + 2 steps of two fp16 planes (8 + 8 KiB)
       return launch_chain_t<chain_kernel<64, 5, 0, 2, 4, 1, 8, 1, 2, 1, 2, 3, true, false, false, true, true, false>>(a, grid_x, 128 * 1024 + 2 * 16 * 1024, st);
@@ -634,26 +626,24 @@ hipError_t mlt_launch_chain(int c, int h, bool with_s2, bool oob_zero, bool w2, 
   }
   // oob_zero: conv padding from DS reads beyond the LDS allocation (the probed default) or from zero masks; the kernels off the default path
   // (chains without the stride-2 front conv, MLT_NO_CHAIN_S2) exist in the masked form only
-  if (c == 64 && h == 32 && a.nconv == 3 && !with_s2) {  // 8 waves x (64 couts x 128 pixels), one 128 KiB sample per workgroup, 2 taps per weight step: 2 x 16 KiB ring, 5 barriers per conv
+  if (c == 64 && h == 32 && !with_s2) {  // 8 waves x (64 couts x 128 pixels), one 128 KiB sample per workgroup, 2 taps per weight step: 2 x 16 KiB ring, 5 barriers per conv
     constexpr int lds64 = 128 * 1024 + 4 * 8 * 1024;
     if (oob_zero) return launch_chain_t<chain_kernel<64, 5, 0, 2, 4, 1, 8, 2, 2, 1, 2, 3, true, false, false, true>>(a, grid_x, lds64, st);
     return launch_chain_t<chain_kernel<64, 5, 0, 2, 4, 1, 8, 2, 2, 1, 2, 3, true, false, false, false>>(a, grid_x, lds64, st);
   }
   if (c == 128 && h == 16) {  // 8 waves x (64 couts x 64 pixels), one sample per workgroup
-    if (with_s2 && a.nconv == 3) {
+    if (with_s2) {
       if (oob_zero) return launch_chain_t<chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, 2, 2, 3, true, true, true, true>>(a, grid_x, lds, st);
       return launch_chain_t<chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, 2, 2, 3, true, true, true, false>>(a, grid_x, lds, st);
     }
-    if (a.nconv == 3) return launch_chain_t<chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, 2, 2, 3, true>>(a, grid_x, lds, st);
-    if (a.nconv == 2) return launch_chain_t<chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, 2, 2, 2, true>>(a, grid_x, lds, st);
+    return launch_chain_t<chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, 2, 2, 3, true>>(a, grid_x, lds, st);
   }
   if (c == 256 && h == 8) {   // 8 waves x (64 couts x 32 pixels) x 2 cout passes, two samples per workgroup
-    if (with_s2 && a.nconv == 3) {
+    if (with_s2) {
       if (oob_zero) return launch_chain_t<chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 3, true, true, true, true>>(a, grid_x, lds, st);
       return launch_chain_t<chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 3, true, true, true, false>>(a, grid_x, lds, st);
     }
-    if (a.nconv == 3) return launch_chain_t<chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 3, true>>(a, grid_x, lds, st);
-    if (a.nconv == 2) return launch_chain_t<chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 2, true>>(a, grid_x, lds, st);
+    return launch_chain_t<chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 3, true>>(a, grid_x, lds, st);
   }
   return hipErrorInvalidValue;
 }

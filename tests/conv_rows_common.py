@@ -32,22 +32,9 @@ CASES = [
     ("tiled_nolat", 128, 1, 0, 0x30, 0), ("tiled_nolat", 128, 1, 0, 0xC0, 0), ("tiled_nolat", 128, 1, 1, 0, 0), ("tiled_nolat", 128, 1, 5, 0, 0),
     ("tiled_nolat", 128, 70, 0, 0, 0),
 ]
-# Rows of the table no context can launch.  run_conv (mlt_dispatch.cpp) asks with nsplit = 6 / 2 / 4 / 1 only -- never 3 -- so an nsplit-3 row is reached solely through
-# select_row's alias of nsplit 4 (hi+lo weights on the fast packing), which (a) is taken with the DEFAULT variant only -- run_conv sets dma = 0 for a w2 layer, and its
-# latency flag then holds for stride 1 only -- and (b) excludes the stride-1 layers with >= 64 channels, which have their own nsplit-4 rows:
+# Rows of the table no context can launch.  Only one is left, and it stays in the table because the host reads the layer's packing from it (mlt_conv_cfg) and the
+# layer's hi+lo-weights row is derived from it (add_fast); every other row is launched by the cases above.
 UNREACHABLE = {
-    # (a) the exact tiling of the four layers whose nsplit-3 DEFAULT row has a tiling of its own: selected by (nsplit 3, DMA | LATENCY) only
-    "mfma<32,32,1,9,0,32,3,1,2,1,8,3,2,5,1,0,0,0>", "mfma<32,64,2,9,1,32,3,1,1,2,4,2,2,5,1,0,0,0>",
-    "mfma<64,128,2,9,1,32,3,2,1,2,4,2,2,3,1,0,0,0>", "mfma<128,256,2,9,1,32,3,2,1,2,4,2,2,3,1,0,0,0>",
-    # (b) stride 1, cin == cout >= 64: selected by nsplit 3 only
-    "mfma<64,64,1,9,0,32,3,2,1,1,8,1,2,3,1,0,0,0>", "mfma<96,96,1,9,0,32,3,3,1,1,4,1,2,2,1,0,0,0>",
-    "mfma<128,128,1,9,0,32,3,2,1,2,4,1,2,2,1,0,0,0>", "mfma<256,256,1,9,0,32,3,2,1,2,4,1,2,2,1,0,0,0>",
-    # the CU models' 64->96 and 96->128 stride-2 layers under hi+lo weights (nsplit 4 -> 3): they need a CU model with a w2 launch unit beyond layer0, and no context
-    # gets one -- the small models' tier search (search_tier_small) only ever puts layer0 there, and MLT_W2_MASK forces the 128 model alone.  A plan described for
-    # such a state could not run either: the unit that opens with 64->96 goes on with a 96->96 stride-1 conv, which mlt_launch_conv refuses for nsplit 4 in every
-    # variant; the unit that opens with 96->128 goes on with a 128->128 stride-1 conv on a map of at most 4 x 4 (the CU models' 128-channel stage), where run_conv asks for
-    # (nsplit 4, DEFAULT), which is refused (its latency flag, and with it the only nsplit-4 row of that layer, needs maps from 8 x 8 on)
-    "mfma<64,96,2,9,1,32,3,3,1,1,4,2,2,3,1,0,0,0>", "mfma<96,128,2,9,1,32,3,2,2,2,2,2,2,3,1,0,0,0>",
     # 64->128 stride 2, fast, throughput tiling: only the 128 model has the layer, on 16 x 16 output maps, where run_conv picks the latency row (small launches) or the
     # ring-DMA row (hout >= 8) -- never neither
     "mfma<64,128,2,9,1,32,1,2,1,2,4,2,2,5,1,0,0,0>",

@@ -120,3 +120,26 @@ def test_layer1_stream_kernel_fits_its_waves_without_scratch(stats, form):
     assert st["scratch"] == 0, f"{st['scratch']} scratch ops"
     drains = [w for w in st["waits"] if w[1] >= 1 and "vmcnt(0)" in w[2]]
     assert len(drains) <= 3, f"compiler drains inside loops: {drains}"   # two beside the LDS-clearing loop at the top, one at the end of the loaders' step group
+
+
+# Every kernel built from chain_body, as mlt_launch_chain / mlt_launch_stage256_wide can select it: <C, HL, SPW_L, WCB, WPB, WAVES_C, WAVES_P, GT, RB, FD, MINW,
+# NCONV, SPLIT_ROLES, S2, KEEP, OOBZ, W2, LO8>
+LAUNCHABLE_CHAIN_FORMS = {
+    # hi+lo weights (w2): one form per channel count, conv padding from beyond the LDS only
+    W2_CHAIN_64, W2_STAGE_128, W2_STAGE_256,
+    # 64 channels: conv padding from beyond the LDS / from zero masks
+    CHAIN_64 % "true", CHAIN_64 % "false",
+    # 128 and 256 channels: the whole stage (with the stride-2 front conv) in both padding forms, and the chain without the front conv (masked form only)
+    STAGE_128 % "true", STAGE_128 % "false", "chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, 2, 2, 3, true, false, true, false, false, false>",
+    STAGE_256 % "true", STAGE_256 % "false", "chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 3, true, false, true, false, false, false>",
+    # the 256-channel stage with both cout passes per wave (chain_body<..., WIDE>)
+    "stage256_wide_kernel",
+}
+
+
+def test_only_the_chain_forms_the_launchers_can_select_are_compiled(stats):
+    """The device code holds exactly the twelve kernels made of chain_body that a launcher can select -- eleven chain_kernel<...> forms and stage256_wide_kernel --
+    and no other: an instantiation nothing launches is code every edit of chain_body has to keep compiling."""
+    built = {k.split("(")[0] for k in stats if k.startswith(("chain_kernel<", "stage256_wide_kernel"))}
+    assert len(LAUNCHABLE_CHAIN_FORMS) == 12
+    assert built == LAUNCHABLE_CHAIN_FORMS, f"not launchable: {sorted(built - LAUNCHABLE_CHAIN_FORMS)}; missing: {sorted(LAUNCHABLE_CHAIN_FORMS - built)}"

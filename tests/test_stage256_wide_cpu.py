@@ -18,8 +18,7 @@ OLD = ("chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 3, true, true, true, tru
        "chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 3, true, true, true, false, false, false>",    # devices that fail the LDS probe
        "chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, 2, 2, 3, true, true, true, true, false, false>",
        "chain_kernel<128, 4, 0, 2, 2, 2, 4, 3, 2, 2, 2, 3, true, true, true, false, false, false>",
-       "chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 3, true, false, true, false, false, false>",   # chains behind a stride-2 launch of their own
-       "chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 2, true, false, true, false, false, false>",
+       "chain_kernel<256, 3, 1, 2, 1, 2, 4, 3, 2, 2, 2, 3, true, false, true, false, false, false>",   # the chain behind a stride-2 launch of its own
        "chain_kernel<256, 3, 1, 2, 1, 2, 4, 1, 2, 1, 2, 3, true, false, true, true, true, true>",      # hi+lo weights
        "chain_kernel<64, 5, 0, 2, 4, 1, 8, 2, 2, 1, 2, 3, true, false, false, true, false, false>")
 
