@@ -1,8 +1,11 @@
 """Tracer weights: a positive, ReLU-free weight set whose logits are LINEAR in the two input planes, and the float64 adjoint of that map.
 
-Every other test that holds the convolution kernels to an independent reference does so on pooled logits of seeded random weights at |dlogit| <= 1e-3: global
-average pooling divides a wrong pixel by the map area, and the seeded BN shifts put an O(1) baseline under it.  With the weights of this module nothing hides
-a pixel:
+Three designed weight families hold the convolution kernels to float64 per pixel, in front of the pooling (everything else sees pooled logits of seeded random
+weights at |dlogit| <= 1e-3: global average pooling divides a wrong pixel by the map area, and the seeded BN shifts put an O(1) baseline under it).  This one
+covers the MFMA sums, the taps, strides, padding and tile seams of every path at every pixel position, with every epilogue a no-op; tests/shift_weights.py
+covers every arithmetic tier and every hand-off between them at ~1e-6, on weights for which no tier rounds; tests/gated_weights.py covers what both switch off on
+purpose -- the folded bias and the shortcut's, the order of add and ReLU, the clamp at zero and the BatchNorm fold of negative and far-from-1 scales.  With the
+weights of this module nothing hides a pixel:
 
   tracer_state_dict   the seeded state dict with identity BatchNorm (weight 1, bias 0, mean 0, var 1), every conv weight g (0.5 + u) / (cin kh kw) with u from
                       synth.uniform -- g = GAINS["stride2"] on the stride-2 conv1 of each stage, GAINS["other"] elsewhere --, head feature columns
